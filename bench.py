@@ -18,8 +18,13 @@ all_gather of the (frames,K,4,4) poses over RCCL):
         scaling: --steps frames in total.  --workload c5 (N=262144, K=128: SURVEY 8(d) "assign / fit
         kernels only") always runs this way, with the ICP-style frame (K4 masked ICP + K5 + K2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replay] [--workload allegro|franka|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode replay] [--workload allegro|franka|c5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the --steps steps once and prints the JSON line (`value`, `ms_per_step` = milliseconds of one
+timed step).  --full adds everything else the line has carried: roofline, parity against the oracle, the ICP-style line,
+cpu_baseline, the other single-GPU workloads, the strong-scaling legs at N > 1, the RCCL gather probe and repeats of the timed
+region.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (seeded inputs: comparable across builds).
 """
 import argparse
 import json
@@ -338,6 +343,30 @@ class _Mark:
         return self.ev.elapsed_time(other.ev) if self.ev is not None else (other.t - self.t) * 1e3
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the timed path returned in its last step, one DIR/<name>.npy per array, float64 stays float64 and everything
+    else is written as float32 (integer offsets as float64, exactly).  Inputs are seeded, so two builds run with the same arguments can
+    be compared array for array.  Past DUMP_LIMIT_BYTES in all, the largest array is cut to a fixed, seeded sample of its rows (rows =
+    its last axis; the sampled row numbers go to <name>_rows.npy)."""
+    os.makedirs(path, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype in (np.float64, np.int64, np.int32) else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        name = max(out, key=lambda k: out[k].nbytes)
+        rows = out[name].reshape(-1, out[name].shape[-1])
+        keep = max(1, (out[name].nbytes - (total - DUMP_LIMIT_BYTES)) // (rows[0].nbytes + 8))      # + 8: the row number
+        idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], keep, replace=False))
+        out[name], out[name + "_rows"] = rows[idx], idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def frames_of(robot, sid, n_frames, n_points):
     """The frames of sequence `sid`: synthetic capsule chains (autourdf_amd.synthetic.make_sequence) or, for a `*_real` workload, the
     committed frames of the real robot (2 sequences x 10 frames; sequence ids wrap)."""
@@ -611,7 +640,7 @@ def run_c5(args, ctx, robot, n_points, k_clusters, wl_tag):
     t0 = time.perf_counter()
     marks[0].record()
     for i, it in enumerate(mine):
-        M_new, _, n_it = register(it)
+        M_new, dq, n_it = register(it)
         poses[i].copy_(M_new)
         iters.append(n_it)
         marks[i + 1].record()
@@ -629,9 +658,14 @@ def run_c5(args, ctx, robot, n_points, k_clusters, wl_tag):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(gathered).all() and gathered.shape[0] == args.steps
+    if args.dump_outputs and rank == 0 and mine:
+        d = {"poses": M_new, "icp_iterations": n_it}                          # (K,4,4) float64, (K) per-cluster ICP iterations
+        if not STUB:
+            d.update(dual_quaternions=dq, clusters_local=worker.local, cluster_offsets=worker.off)   # (K,8) float32, (N,3) float64, (K+1)
+        dump_outputs(args.dump_outputs, d)
     out = None
-    if rank == 0 and (STUB or getattr(args, "brief", False)):
-        # a strong-scaling leg of the default --gpus N line: value, what every rank ran, the gather -- no kernel-level legs
+    if rank == 0 and (STUB or getattr(args, "brief", False) or not args.full):
+        # a plain run, or a strong-scaling leg of the --gpus N --full line: value, what every rank ran, the gather -- no kernel-level legs
         out = {"metric": f"ICP-style registered frames/sec (N={n_points} pts, K={k_clusters} clusters): K4 masked ICP + K5 DQ + K2 Lloyd resample",
                "value": round(args.steps / elapsed, 4), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "strong", "dtype": "f64", "data": "synthetic",
@@ -871,15 +905,23 @@ def build_parser():
     ap.add_argument("--no-icp-variant", action="store_true", help="skip the ICP-style second line (SURVEY 8(d))")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the parity summary against the oracle (first timed frame of sequence 0, outside the timed region)")
-    ap.add_argument("--force-strong-scaling", action="store_true", help="run the strong-scaling legs at world 1 too (the single-GPU divisors of the N > 1 line, and a test of that path)")
+    ap.add_argument("--force-strong-scaling", action="store_true", help="with --full: run the strong-scaling legs at world 1 too (the single-GPU divisors of the N > 1 line, and a test of that path)")
     ap.add_argument("--no-strong-scaling", action="store_true",
                     help="world > 1: skip the strong-scaling legs (BASELINE configs[3]: 50 allegro-shaped frames, configs[4]: 200 frames of N=262144 / K=128, both dealt over the ranks)")
     ap.add_argument("--no-other-workloads", action="store_true",
                     help="skip the extra legs of the default single-GPU run: BASELINE configs[2] (franka shape) and configs[4] (N=262144, K=128)")
     ap.add_argument("--no-rccl-world1", action="store_true", help="single process without a launcher: do not create the world-1 RCCL group")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="sequences mode: the timed region (the same --steps frames from the same state) is run this many times in all; "
-                         "`value` is the FIRST run (exactly --steps steps after --warmup), `repeats` reports median / min / max")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, parity against the oracle, the ICP-style line, cpu_baseline, the other "
+                         "single-GPU workloads, the strong-scaling legs at world > 1, the RCCL gather probe and 5 repeats of the timed region "
+                         "(each still subject to its --no-* switch).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (poses, train results, re-sampled "
+                         "clusters) as DIR/<name>.npy in float32 / float64 (rank 0; at most 64 MB in all)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="sequences mode: the timed region (the same --steps frames from the same state) is run this many times in all "
+                         "(default 5 with --full, else 1); `value` is the FIRST run (exactly --steps steps after --warmup), `repeats` reports "
+                         "median / min / max")
     ap.add_argument("--r", choices=["q", "dq", "6d", "rpy"], default="q",
                     help="pose representation (mlp_reg.py:360 --r); 'q' is the reference's default and the metric's; the others skip the roofline / cpu_baseline legs")
     ap.add_argument("--eager", action="store_true", help="eager launches instead of the captured epoch graph")
@@ -897,10 +939,22 @@ def build_parser():
     return ap
 
 
+def parse_args(ap, argv):
+    """The arguments, with what a plain run leaves out switched off: without --full only the headline's own work runs."""
+    a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
+    if not a.full:
+        a.no_cpu_baseline = a.no_icp_variant = a.no_roofline = a.no_parity = True
+        a.no_other_workloads = a.no_strong_scaling = True
+        a.force_strong_scaling = False
+    return a
+
+
 def main(argv=None):
     import sys
     ap = build_parser()
-    args = ap.parse_args(argv)
+    args = parse_args(ap, argv)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus, sys.argv[1:] if argv is None else argv))
     ctx = init_world(args)
@@ -912,13 +966,13 @@ def main(argv=None):
         out = run_c5(args, ctx, robot, n_points, k_clusters, wl_tag)
     else:
         out = run_registration(args, ctx)
-        # The default single-GPU invocation (what the driver runs) also carries the other single-GPU BASELINE configs, each a full run of
+        # The single-GPU --full invocation also carries the other single-GPU BASELINE configs, each a full run of
         # its own workload in this process AFTER the headline was measured: configs[2] (franka shape) and configs[4] (N=262144, K=128).
         headline = (args.workload == "wx200_5" and args.mode == "sequences" and args.r == "q" and ctx.world == 1 and not STUB
                     and not args.no_other_workloads and not args.eager and args.graph_branches == 0 and args.sequences == 5)
         if headline and out is not None:
             out["other_workloads"] = other_workloads(ap, ctx)
-        # world > 1 (the driver's `--gpus N` line): the north star's strong-scaling questions answered by the same command -- BASELINE
+        # world > 1 with --full: the north star's strong-scaling questions answered by the same command -- BASELINE
         # configs[3] (50 allegro-shaped frames) and configs[4] (200 frames of N=262144 / K=128) dealt over the N ranks.  EVERY rank takes part
         # (the legs hold barriers and the gather); the weak-scaling line above stays the headline.
         strong = (args.workload == "wx200_5" and args.mode == "sequences" and args.r == "q" and (ctx.world > 1 or args.force_strong_scaling) and not args.no_strong_scaling
@@ -933,13 +987,13 @@ def main(argv=None):
         ctx.dist.destroy_process_group()
 
 
-STRONG_LEGS = {"configs[3]": ["--mode", "replay", "--workload", "allegro", "--steps", "50", "--warmup", "5", "--no-cpu-baseline", "--no-icp-variant", "--no-roofline",
-                              "--repeats", "1"],
-               "configs[4]": ["--workload", "c5", "--steps", "200", "--warmup", "2"]}
+STRONG_LEGS = {"configs[3]": ["--mode", "replay", "--workload", "allegro", "--steps", "50", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-icp-variant",
+                              "--no-roofline", "--repeats", "1"],
+               "configs[4]": ["--workload", "c5", "--steps", "200", "--warmup", "2", "--full"]}
 
 
 def strong_scaling_legs(ap, ctx):
-    """`bench.py --gpus N`, N > 1: the two strong-scaling configurations of BASELINE.json after the weak-scaling headline, on every rank:
+    """`bench.py --gpus N --full`, N > 1: the two strong-scaling configurations of BASELINE.json after the weak-scaling headline, on every rank:
     `--mode replay --workload allegro --steps 50` (configs[3]: 50 frames sharded across the GPUs, RCCL gather of the poses) and
     `--workload c5 --steps 200` (configs[4]: 200 frames of N=262144 / K=128).  Total work is fixed, so value(N) / value(1 GPU of the same
     leg) is the speedup the north star asks for (>= 6x at N = 8 on configs[3]); the driver's N = 1 run carries no such leg -- run
@@ -949,7 +1003,7 @@ def strong_scaling_legs(ap, ctx):
     for name, argv in STRONG_LEGS.items():
         t0 = time.perf_counter()
         try:
-            a = ap.parse_args(["--gpus", str(ctx.world)] + argv)
+            a = parse_args(ap, ["--gpus", str(ctx.world)] + argv)
             a.brief = True
             robot, n_points, k_clusters, wl_tag = WORKLOADS[a.workload]
             if a.workload == "c5":
@@ -980,13 +1034,13 @@ def other_workloads(ap, ctx):
     """BASELINE configs[2] and configs[4] on the driver's one line: the same code paths as `--workload franka` / `--workload c5`, trimmed
     to what a reader needs (value, ms per step, checksum, the run's own roofline block).  A leg that fails reports its error instead of
     taking the headline with it."""
-    legs = {"franka": ["--workload", "franka", "--steps", "20", "--warmup", "5", "--no-cpu-baseline", "--no-icp-variant", "--repeats", "1"],
-            "c5": ["--workload", "c5", "--steps", "8", "--warmup", "2"]}
+    legs = {"franka": ["--workload", "franka", "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-icp-variant", "--repeats", "1"],
+            "c5": ["--workload", "c5", "--steps", "8", "--warmup", "2", "--full"]}
     res = {}
     for name, argv in legs.items():
         t0 = time.perf_counter()
         try:
-            a = ap.parse_args(argv)
+            a = parse_args(ap, argv)
             robot, n_points, k_clusters, wl_tag = WORKLOADS[a.workload]
             if name == "c5":
                 a.mode = "replay"
@@ -1067,6 +1121,7 @@ def run_registration(args, ctx):
         if le is not None:
             epochs_log.append(le)
 
+    last = [reg, None]                  # the registrar of the last step and what its step() returned (--dump-outputs)
     if replay:
         items = capture_items(reg, frames64, frames32, cap_rounds, clone_params=not STUB)[:total_items]
         job = items[args.warmup:]
@@ -1089,6 +1144,7 @@ def run_registration(args, ctx):
             rb = reg_for(len(batch))
             load_items(rb, batch)
             out = rb.step([it["f64"] for it in batch], [it["f32"] for it in batch])
+            last[:] = [rb, out]
             if record is not None:
                 note_epochs(rb)
                 for i, (m, _) in enumerate(out):
@@ -1131,6 +1187,7 @@ def run_registration(args, ctx):
         def run_rounds(lo, hi):
             for f in range(lo, hi):
                 out = reg.step([frames64[s][f] for s in range(S)], [frames32[s][f] for s in range(S)])
+                last[1] = out
                 note_epochs()
                 for s, (m, res) in enumerate(out):
                     poses[f * S + s].copy_(m)
@@ -1157,7 +1214,7 @@ def run_registration(args, ctx):
         run_rounds(0, warm_rounds)
         n_rep = max(1, args.repeats)
         snap = snapshot() if n_rep > 1 else None
-        if not STUB and rank == 0:      # sequence 0 entering its first timed frame (the parity summary, computed after the timing)
+        if not STUB and rank == 0 and not args.no_parity:      # sequence 0 entering its first timed frame (the parity summary, computed after the timing)
             r0 = reg.seqs[0]
             parity_state = (r0.m, r0.pts, r0.off, [q.clone() for q in r0.p_step])
         fence()
@@ -1194,9 +1251,18 @@ def run_registration(args, ctx):
         rep_elapsed = [float(v) for v in t.tolist()]
         elapsed = rep_elapsed[0]
     assert torch.isfinite(gathered).all() and gathered.shape[0] == n_counted, (gathered.shape, n_counted)
+    if args.dump_outputs and rank == 0 and last[1] is not None:
+        rl, ol = last
+        dump_outputs(args.dump_outputs, {
+            "poses": torch.stack([o[0] for o in ol]),                              # (S,K,4,4) float32: the registered poses
+            "train_result": torch.stack([o[1] for o in ol]),                       # (S,4) float32: [min_loss, epochs_run, lr, ...] of the Anchor train
+            **({"clusters_local": torch.stack([r.local64 for r in rl.seqs]),       # (S,N,3) float64: the re-sampled clusters in their local frames
+                "cluster_offsets": torch.stack([r.off for r in rl.seqs])} if not STUB else {})})
     # the job's one collective, on its own (every rank takes part)
     mine_block = poses[:max(n_mine, 1)] if replay else poses[warm_rounds * S: warm_rounds * S + args.steps]
-    rccl = rccl_gather_probe(ctx, mine_block.contiguous()) if (not replay or len({len(job[r::world]) for r in range(world)}) == 1) else None
+    rccl = None
+    if args.full and (not replay or len({len(job[r::world]) for r in range(world)}) == 1):
+        rccl = rccl_gather_probe(ctx, mine_block.contiguous())
 
     out = None
     if rank == 0:

@@ -14,7 +14,7 @@ import bench                                                             # noqa:
 L = _lib.load()
 fn = L.creg_debug_bd_stamps
 fn.argtypes = [ctypes.c_void_p]
-sys.argv = ["bench.py", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-icp-variant"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", "5", "--warmup", "1", "--no-cpu-baseline", "--no-icp-variant"] + sys.argv[1:]
 bench.main()
 torch.cuda.synchronize()
 out = (ctypes.c_double * 24)()

@@ -97,13 +97,13 @@ def test_replay_many_rounds_ragged_two_ranks():
 
 
 def test_bench_gpus_2_line_carries_the_strong_scaling_legs():
-    """`bench.py --gpus N` (N > 1) answers the north star's strong-scaling questions by itself -- after the weak-scaling
+    """`bench.py --gpus N --full` (N > 1) answers the north star's strong-scaling questions by itself -- after the weak-scaling
     headline every rank runs BASELINE configs[3] (--mode replay --workload allegro --steps 50) and configs[4] (--workload c5 --steps 200);
     the one JSON line carries both under `strong_scaling`, each with value / scaling "strong" / what every rank ran / the gather."""
     env = dict(os.environ, CREG_BENCH_STUB="1", OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "5"], env=env, cwd=ROOT,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "5", "--full"], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -124,3 +124,29 @@ def test_bench_gpus_2_line_carries_the_strong_scaling_legs():
     # a single rank's line has no such legs (the divisor is the same command at --gpus 1 with the leg's own arguments)
     one = _run(1, ["--steps", "6", "--warmup", "3"])
     assert "strong_scaling" not in one
+
+
+def test_plain_run_is_the_headline_only_and_full_keeps_the_legs():
+    """Without --full the line is the headline alone (no repeats, no strong-scaling legs); --full at world 2 carries the legs again."""
+    plain = _run(2, ["--steps", "6", "--warmup", "3"])
+    assert "strong_scaling" not in plain and "repeats" not in plain and "rccl_gather" not in plain
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 6 and plain["ms_per_step"] > 0
+
+
+@pytest.mark.parametrize("extra", [["--mode", "sequences"], ["--mode", "replay"], ["--workload", "c5"]])
+def test_dump_outputs_writes_the_last_step_and_is_reproducible(tmp_path, extra):
+    """--dump-outputs DIR: the arrays the last timed step returned, as float32 / float64 .npy, identical from run to run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        _run(1, ["--steps", "6", "--warmup", "2", "--dump-outputs", str(d)] + extra)
+        dumps.append({f.name: np.load(str(f)) for f in sorted(d.iterdir())})
+    assert "poses.npy" in dumps[0] and set(dumps[0]) == set(dumps[1])
+    for name, a in dumps[0].items():
+        assert a.dtype in (np.float32, np.float64) and a.size > 0, name
+        np.testing.assert_array_equal(a, dumps[1][name], err_msg=name)
+    poses = dumps[0]["poses.npy"]
+    assert poses.shape[-2:] == (4, 4) and np.isfinite(poses).all()

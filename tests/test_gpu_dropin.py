@@ -225,7 +225,7 @@ def test_bench_under_torchrun_world_one_runs_the_rccl_gather(mode):
         env.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "5", "--mode", mode,
-                        "--no-cpu-baseline", "--no-icp-variant", "--no-roofline", "--no-other-workloads", "--repeats", "2"],
+                        "--full", "--no-cpu-baseline", "--no-icp-variant", "--no-roofline", "--no-other-workloads", "--repeats", "2"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -249,12 +249,35 @@ def test_bench_plain_single_process_creates_its_own_world_one_rccl_group():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-icp-variant", "--no-roofline", "--no-other-workloads", "--repeats", "1"],
+                        "--full", "--no-cpu-baseline", "--no-icp-variant", "--no-roofline", "--no-other-workloads", "--repeats", "1"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["rccl_world1_gather_us"] > 0 and d["rccl_gather"]["backend"] == "nccl", d.get("rccl_gather")
     assert "created by bench.py" in d["rccl_gather"]["group"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): the headline line alone, no side legs, and the
+    last timed step's outputs -- the five sequences' poses, train results and re-sampled clusters -- written as float .npy files."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "5", "--dump-outputs", str(tmp_path)],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert d["steps"] == 5 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f32"
+    for k in ("roofline", "parity", "icp_variant", "cpu_baseline", "other_workloads", "repeats", "rccl_gather"):
+        assert k not in d, k
+    poses, res = np.load(tmp_path / "poses.npy"), np.load(tmp_path / "train_result.npy")
+    local, off = np.load(tmp_path / "clusters_local.npy"), np.load(tmp_path / "cluster_offsets.npy")
+    assert poses.shape == (5, 20, 4, 4) and poses.dtype == np.float32 and np.isfinite(poses).all()
+    assert res.shape == (5, 4) and local.shape == (5, 4096, 3) and local.dtype == np.float64 and off.shape == (5, 21)
+    assert (off[:, -1] == 4096).all()
 
 
 _TWO_PROC_CHILD = r"""

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import pytest
 
+from _robots import unpack_robots
 from _toy_urdf import write_toy_robot
 
 
@@ -43,13 +44,12 @@ def test_urdf_meshes_and_fk_vs_independent_oracle(tmp_path):
         load_mesh("x.ply")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Robot"), reason="reference assets only exist in the build container")
 @pytest.mark.parametrize("rel,dof", [("interbotix_descriptions/urdf/wx200_real.urdf", 5),
                                      ("allegro_hand_description/allegro_hand_description_left.urdf", 16)])
-def test_reference_urdfs_parse_when_present(rel, dof):
-    """The real assets the generator is for (parameters.json 'gt' entries); read-only, build container only."""
+def test_reference_urdfs_parse_when_present(tmp_path, rel, dof):
+    """The real assets the generator is for (parameters.json 'gt' entries): the reference's URDFs and meshes, from tests/golden/robots."""
     from autourdf_amd.sim_data import SimEnv
-    env = SimEnv(os.path.join("/root/reference/Robot", rel), dof=dof)
+    env = SimEnv(os.path.join(unpack_robots(tmp_path), rel), dof=dof)
     assert len(env.dof_list) == dof and len(env.robot.tri) > 1000
     T = env.robot.fk(env.set_joint_positions(np.zeros(len(env.joint_list))))
     assert np.isfinite(T).all() and np.allclose(np.linalg.det(T[:, :3, :3]), 1.0)
@@ -148,10 +148,9 @@ def test_camera_ring_vs_reference_minted_golden(tmp_path, golden):
         np.testing.assert_allclose(ring, env.cam_frames, atol=1e-15)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Robot"), reason="reference assets only exist in the build container")
-def test_reference_franka_collada_visuals_parse_when_present():
+def test_reference_franka_collada_visuals_parse_when_present(tmp_path):
     from autourdf_amd.sim_data import SimEnv
-    env = SimEnv("/root/reference/Robot/franka/franka_panda.urdf", dof=6)
+    env = SimEnv(os.path.join(unpack_robots(tmp_path), "franka", "franka_panda.urdf"), dof=6)
     assert len(env.robot.tri) > 100000 and len(env.dof_list) == 6
     T = env.robot.fk(env.set_joint_positions(np.zeros(len(env.joint_list))))
     pts = np.concatenate([env.robot.tri[env.robot.tri_link == l].reshape(-1, 3) @ T[l, :3, :3].T + T[l, :3, 3]
