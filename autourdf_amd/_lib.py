@@ -84,6 +84,8 @@ SIGNATURES = {
     "creg_coord_dist_map_workspace_bytes": (sz, [i32, i32]),
     "creg_coord_dist_map_f64": (ctypes.c_int, [vp, i32, i32, f64, i32, vp, vp, vp, sz, vp]),
     "creg_pose_coords_f64": (ctypes.c_int, [vp, i64, vp, vp]),
+    "creg_link_sweep_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "creg_coord_mst_f64": (ctypes.c_int, [vp, i32, i32, vp, vp, vp]),
     "creg_train_workspace_bytes": (sz, [ctypes.POINTER(TrainShape)]),
     "creg_train_plan_create": (ctypes.c_int, [ctypes.POINTER(TrainShape), vp, sz, ctypes.POINTER(vp)]),
     "creg_train_plan_run": (ctypes.c_int, [vp, ctypes.POINTER(TrainArgs), vp]),

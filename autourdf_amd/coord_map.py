@@ -10,7 +10,13 @@ Same constructor, attributes and method signatures as the reference class (coord
 (the reference's arrays are float64 whenever frame 0 -- saved as float64, mlp_reg.py:257-263 -- is in
 the range; an all-float32 range is promoted, which only removes the reference's own float32 rounding).
 
-The graph / URDF half of the reference file (MST, silhouette clustering, joints, GUI) is out of scope.
+The graph half of the URDF stage is here too: ``coord_clustering`` / ``silhouette_score_method``
+(coord_map.py:70-128; every candidate link count in ONE launch of ``creg_link_sweep_f64``), ``CoordMap.coord_mst``
+(:334-349, ``creg_coord_mst_f64``) and ``CoordMap.kinematics_tree`` (:351-441, host bookkeeping over <= 25 links).
+Graphs are ``Graph``, a minimal stand-in for the networkx.Graph surface the reference uses (``nodes``, ``edges``,
+``neighbors(n)``, insertion-ordered adjacency), and ``connected_components`` walks it exactly as networkx does, so
+the component sets are built in the same insertion order and iterate identically.  Link clouds, joint axes, the
+URDF writer and the GUI of the reference file are not part of this module.
 There is no CPU fallback: the methods need the HIP library and a GPU.
 """
 import glob
@@ -20,6 +26,146 @@ import torch
 
 from . import _lib, ops
 from .cluster_icp import read_point_cloud
+
+THRESHOLD_STEP = 0.0001                     # the reference's lattice decrement (coord_map.py:94)
+
+
+class Graph:
+    """The part of networkx.Graph the URDF stage touches, with networkx's insertion-ordered adjacency, so that
+    ``edges`` and ``connected_components`` iterate in networkx's order (as cluster_icp.PointCloud stands in for Open3D)."""
+
+    def __init__(self):
+        self._adj = {}
+
+    def add_nodes_from(self, nodes):
+        for n in nodes:
+            self._adj.setdefault(n, {})
+
+    def add_edge(self, u, v):
+        self._adj.setdefault(u, {})
+        self._adj.setdefault(v, {})
+        self._adj[u][v] = self._adj[v][u] = {}
+
+    def add_edges_from(self, edges):
+        for u, v in edges:
+            self.add_edge(u, v)
+
+    @property
+    def nodes(self):
+        return list(self._adj)
+
+    @property
+    def edges(self):
+        """networkx's EdgeView order: nodes in insertion order, each node's unseen neighbours in insertion order."""
+        seen, out = set(), []
+        for n, nbrs in self._adj.items():
+            out.extend((n, m) for m in nbrs if m not in seen)
+            seen.add(n)
+        return out
+
+    def neighbors(self, n):
+        return iter(self._adj[n])
+
+    def number_of_nodes(self):
+        return len(self._adj)
+
+    def number_of_edges(self):
+        return len(self.edges)
+
+    def __len__(self):
+        return len(self._adj)
+
+    def __iter__(self):
+        return iter(self._adj)
+
+    def __contains__(self, n):
+        return n in self._adj
+
+
+def connected_components(G):
+    """networkx.connected_components: sets built by the same level-order BFS (same insertion order), yielded in
+    node order."""
+    seen, n = set(), len(G)
+    for v in G:
+        if v in seen:
+            continue
+        comp, nextlevel = {v}, [v]
+        while nextlevel and len(comp) < n:
+            thislevel, nextlevel = nextlevel, []
+            for u in thislevel:
+                for w in G._adj[u]:
+                    if w not in comp:
+                        comp.add(w)
+                        nextlevel.append(w)
+                if len(comp) == n:
+                    break
+        seen.update(comp)
+        yield comp
+
+
+def _check_map(num_coords, d_map):
+    d = np.asarray(d_map.cpu().numpy() if isinstance(d_map, torch.Tensor) else d_map, dtype=np.float64)
+    if d.shape != (num_coords, num_coords):
+        raise ValueError(f"d_map must be ({num_coords},{num_coords}), got {d.shape}")
+    if not np.all(np.isfinite(d)):
+        raise ValueError("d_map contains NaN or infinity")            # sklearn's check_array
+    if num_coords > ops.LINK_SWEEP_MAX_K:
+        raise ValueError(f"link discovery supports at most {ops.LINK_SWEEP_MAX_K} clusters, got {num_coords}")
+    return d
+
+
+def _threshold_graph(num_coords, d, threshold):
+    """G1 of coord_clustering: every node, the edges (i, j), i < j, d[i, j] < threshold in the reference's loop order."""
+    G = Graph()
+    G.add_nodes_from(range(num_coords))
+    ii, jj = np.nonzero(np.triu(d < threshold, 1))
+    G.add_edges_from(zip(ii.tolist(), jj.tolist()))
+    return G
+
+
+def _sweep(num_coords, d_map, lo, hi):
+    d = _check_map(num_coords, d_map)
+    labels, n_comp, thr, scores, best = ops.link_sweep(torch.as_tensor(d, device=_lib.device(d_map)), lo, hi)
+    best, n_comp = int(best.item()), n_comp.cpu().numpy()
+    if best < 0:
+        bad = [lo + i for i, c in enumerate(n_comp) if not 1 < c < num_coords]
+        raise ValueError(f"Number of labels is invalid for link counts {bad} (component counts "
+                         f"{[int(n_comp[b - lo]) for b in bad]}); valid values are 2 to n_samples - 1 (inclusive)")
+    return d, labels.cpu().numpy(), n_comp, thr.cpu().numpy(), scores.cpu().numpy(), best
+
+
+def _clusters_at(num_coords, d, threshold, labels):
+    G1 = _threshold_graph(num_coords, d, threshold)
+    cluster_idx = list(connected_components(G1))
+    host = np.empty(num_coords, np.int64)
+    for cid, c in enumerate(cluster_idx):
+        host[list(c)] = cid
+    if not np.array_equal(host, labels):
+        raise RuntimeError("creg_link_sweep_f64 components disagree with the threshold graph")
+    return cluster_idx, G1
+
+
+def coord_clustering(num_coords, d_map, num_links):
+    """Cluster the coordinates based on the distance variance matrix (reference coord_map.py:70-111): the connected
+    components of {d < t} at the first lattice threshold with >= num_links of them, and their silhouette score."""
+    d, labels, _, thr, scores, _ = _sweep(num_coords, d_map, num_links, num_links + 1)
+    print("Threshold: ", thr[0] - THRESHOLD_STEP)
+    cluster_idx, G1 = _clusters_at(num_coords, d, thr[0], labels[0])
+    silhouette_avg = np.float64(scores[0])
+    print(f"n={num_links}, silhouette score:{silhouette_avg}")
+    return cluster_idx, G1, silhouette_avg
+
+
+def silhouette_score_method(num_coords, d_map, link_range=(3, 15)):
+    """Silhouette Score Method (reference coord_map.py:114-128): every link count of the range in one launch."""
+    nls = np.arange(link_range[0], link_range[1])
+    d, labels, _, thr, scores, best = _sweep(num_coords, d_map, int(nls[0]), int(nls[-1]) + 1)
+    s_score = [np.float64(s) for s in scores]
+    for nl, t, s in zip(nls, thr, s_score):
+        print("Threshold: ", t - THRESHOLD_STEP)
+        print(f"n={nl}, silhouette score:{s}")
+    cluster_idx, g1 = _clusters_at(num_coords, d, thr[best], labels[best])
+    return cluster_idx, g1, s_score, nls
 
 
 class CoordMap:
@@ -96,3 +242,91 @@ class CoordMap:
         s = cmap.abs().sum(dim=2)
         s = (s - s.min()) / (s.max() - s.min())
         return cmap.cpu().numpy(), s.cpu().numpy()
+
+    # ---- the graph half (coord_map.py:334-441) ------------------------------------------------------
+    def coord_mst(self):
+        """Minimum Spanning Tree of the T-summed cluster xyz (coord_map.py:334-349), as the reference's G_MST: nodes
+        0..K-1, then the tree's edges in networkx's order (Kruskal's weight order, ties row-major, re-read through
+        EdgeView).  The tree itself is one launch of creg_coord_mst_f64."""
+        K = self.num_coords
+        coords = torch.as_tensor(np.asarray(self.coords, np.float64), device=_lib.device(getattr(self, "_M", None)))
+        edges, w = ops.coord_mst(coords.contiguous())
+        e, w = edges.cpu().numpy(), w.cpu().numpy()
+        kruskal = sorted(((float(wt), min(a, b), max(a, b)) for (a, b), wt in zip(e.tolist(), w)))
+        mst = Graph()
+        mst.add_nodes_from(range(K))
+        mst.add_edges_from((a, b) for _, a, b in kruskal)
+        G_MST = Graph()
+        G_MST.add_nodes_from(range(K))
+        G_MST.add_edges_from(mst.edges)
+        return G_MST
+
+    def kinematics_tree(self, g0, g1):
+        """Build the kinematics tree based on the cluster_idx (coord_map.py:351-441): links, their neighbours in the
+        base graph g0, the root (least movement), a BFS for parent_id / tree_id, links sorted by tree_id."""
+        links = []
+        cluster_idx = list(connected_components(g1))
+        for link_id, idx in enumerate(cluster_idx):
+            link = {'id': link_id, 'tree_id': None, 'cluster_idx': idx, 'connected_links': set()}
+            for cid in idx:
+                connected_cid = list(g0.neighbors(cid))
+                for i in range(len(cluster_idx)):
+                    if i == link_id:
+                        continue
+                    for ccid in connected_cid:
+                        if ccid in cluster_idx[i] and i not in link['connected_links']:
+                            link['connected_links'].add(i)
+            links.append(link)
+
+        link_graph = Graph()
+        link_graph.add_nodes_from(range(len(links)))
+        for link in links:
+            for connected_link in link['connected_links']:
+                link_graph.add_edge(link['id'], connected_link)
+        n_cc = len(list(connected_components(link_graph)))
+        if n_cc == 1 and link_graph.number_of_edges() == len(links) - n_cc:
+            print("The graph is connected and Acyclic")
+        else:
+            print("The graph is not connected or Acyclic")
+
+        for link in links:                                        # the root: least movement of the mean coordinates
+            centers = np.mean(self.coords[:, list(link['cluster_idx']), :], axis=1)
+            centers_diff = np.diff(centers, axis=0)
+            link['movement'] = np.sum(np.linalg.norm(centers_diff, axis=1))
+
+        links = sorted(links, key=lambda x: x['movement'])
+        for link in links:
+            print(link)
+        root_link = links[0]
+        root_link['parent_id'] = None
+        root_link['tree_id'] = 0
+        tree_id_counter = 1
+        current_layer = [root_link]
+        count = 0
+        while True:
+            count += 1
+            child_link_id = set()
+            next_layer = []
+            for current_link in current_layer:
+                if current_link['parent_id'] is not None:
+                    child = current_link['connected_links'] - {current_link['parent_id']}
+                else:
+                    child = current_link['connected_links']
+                for i in child:
+                    for link in links:
+                        if link['id'] == i:
+                            link['parent_id'] = current_link['id']
+                            link['tree_id'] = tree_id_counter
+                            tree_id_counter += 1
+                            next_layer.append(link)
+                            break
+                child_link_id.update(child)
+            print(child_link_id)
+            current_layer = next_layer
+            if len(child_link_id) == 0 or count > 100:           # no child link, or the reference's dead-loop cap
+                break
+
+        links = sorted(links, key=lambda x: x['tree_id'])
+        for i, link in enumerate(links):
+            print(f'Layer{i} ---', 'Real ID: ', link['id'], 'Tree ID: ', link['tree_id'], 'Parent Link', link['parent_id'])
+        return links

@@ -384,6 +384,44 @@ def pose_coords(M: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------ N4 URDF stage: link discovery, MST
+LINK_SWEEP_MAX_K = 256
+
+
+def link_sweep(d_map: torch.Tensor, nl_lo: int, nl_hi: int):
+    """coord_clustering for every nl in [nl_lo, nl_hi) plus silhouette_score_method's choice, one launch.
+    d_map (K,K) f64 on the device.  Returns (labels (n,K) int32, n_comp (n) int32, thresholds (n) f64,
+    scores (n) f64, best (1) int32); best = -1 when a label count fell outside [2, K-1]."""
+    L = _lib.load()
+    d_map = _need(d_map, torch.float64, "d_map")
+    if d_map.dim() != 2 or d_map.shape[0] != d_map.shape[1]:
+        raise ValueError("link_sweep: d_map must be (K,K)")
+    K, n = d_map.shape[0], nl_hi - nl_lo
+    dev = d_map.device
+    labels = torch.empty(max(n, 1), K, dtype=torch.int32, device=dev)
+    n_comp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+    thr = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    scores = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+    best = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.check(L.creg_link_sweep_f64(_p(d_map), K, int(nl_lo), int(nl_hi), _p(labels), _p(n_comp), _p(thr), _p(scores),
+                                     _p(best), _stream()), "creg_link_sweep_f64")
+    return labels, n_comp, thr, scores, best
+
+
+def coord_mst(coords: torch.Tensor):
+    """CoordMap.coord_mst's tree over the T-summed xyz of coords (T,K,7) f64: (edges (K-1,2) int32, weights (K-1) f64)
+    in Prim's attachment order."""
+    L = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    if coords.dim() != 3 or coords.shape[2] != 7:
+        raise ValueError("coord_mst: coords must be (T,K,7)")
+    T, K = coords.shape[:2]
+    edges = torch.empty(max(K - 1, 1), 2, dtype=torch.int32, device=coords.device)
+    w = torch.empty(max(K - 1, 1), dtype=torch.float64, device=coords.device)
+    _lib.check(L.creg_coord_mst_f64(_p(coords), T, K, _p(edges), _p(w), _stream()), "creg_coord_mst_f64")
+    return edges[:K - 1], w[:K - 1]
+
+
 # ------------------------------------------------------------------------------ K5 row conversions
 def masked_icp(local: torch.Tensor, world: torch.Tensor, offsets: torch.Tensor, frame: torch.Tensor, M: torch.Tensor,
                scale: float = 1.2, th: float = 1.0, max_iteration: int = 10000, ori: bool = False,

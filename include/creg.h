@@ -261,6 +261,36 @@ int creg_coord_dist_map_f64(const double* M, int32_t T, int32_t K, double boundi
 int creg_pose_coords_f64(const double* M, int64_t n, double* coords, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * N4  the graph half of the URDF stage (coord_map.py:70-128, :334-349), fp64, one workgroup per call.
+ *
+ * creg_link_sweep_f64: link discovery for every candidate link count nl in [nl_lo, nl_hi) in one launch --
+ * coord_clustering(K, d_map, nl) for each nl and silhouette_score_method's choice.
+ *   d_map (K,K) fp64, the normalised sum map; only its strict upper triangle defines the graph ({i<j : d[i][j] < t}),
+ *     the full rows feed the silhouette.  2 <= K <= 256 (kept in LDS up to K = 128, read from global above);
+ *     1 <= nl_lo < nl_hi <= K + 1.  Entries must be finite (the caller checks).
+ *   thresholds (n) : the float64 lattice point t_k (t_0 = 1, t_{k+1} = fl(t_k - 1e-4) by repeated subtraction) at which
+ *     the reference's loop first sees >= nl components -- the value BEFORE its decrement / print.  n = nl_hi - nl_lo.
+ *   labels (n,K) int32 : component of every node at that threshold, components numbered by their smallest node
+ *     (networkx.connected_components order);  n_comp (n) int32 : the component count.
+ *   scores (n) : sklearn silhouette_score(d_map, labels, metric="precomputed") (row sums in index order per cluster,
+ *     intra / (n_c - 1), minimum inter-cluster mean, singletons 0, NaN 0, numpy's pairwise mean); NaN where the
+ *     label count is outside [2, K-1].  A partition always gets the same bits, whichever nl produced it.
+ *   best (1) int32 : index of the first maximum score (np.argmax), or -1 when some nl had a label count outside
+ *     [2, K-1] (sklearn raises ValueError there; the Python layer raises it).
+ * The components come from one Prim MST of the upper triangle (any MST gives the same components).
+ *
+ * creg_coord_mst_f64: CoordMap.coord_mst.  coords (T,K,7) fp64 ([xyz, quaternion], load_matrix's layout); the xyz are
+ *   summed over T and Prim runs on their Euclidean distance matrix from node 0.  edges (K-1,2) int32 = (tree node, new
+ *   node) and weights (K-1) fp64, in the order Prim attaches them.  2 <= K <= 256.
+ *   Tie rule: among equal keys the smallest node index is attached first, and a node's key is replaced only by a
+ *   strictly smaller weight.  With distinct weights the MST is unique and equals networkx's Kruskal result; the
+ *   Python layer restores networkx's edge order (weights ascending, ties row-major). */
+int creg_link_sweep_f64(const double* d_map, int32_t K, int32_t nl_lo, int32_t nl_hi, int32_t* labels,
+                        int32_t* n_comp, double* thresholds, double* scores, int32_t* best, creg_stream_t stream);
+int creg_coord_mst_f64(const double* coords, int32_t T, int32_t K, int32_t* edges, double* weights,
+                       creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The `--normal` branch (mlp_reg.py:190-203, cluster_icp.py:49-62; CLI flag mlp_reg.py:399): Open3D normal estimation +
  * orientation, then sklearn k_means over [xyz | 0.5 * normal].
  *
