@@ -537,6 +537,8 @@ def _rows(fn_name, a, out_shape, b=None, out2_shape=None):
     k = a.shape[0]
     out = torch.empty((k,) + out_shape, dtype=torch.float32, device=a.device)
     fn = getattr(L, fn_name)
+    if k == 0:                                   # an empty tensor's data pointer is null, which the C ABI rejects
+        return (out, torch.empty((0,) + out2_shape, dtype=torch.float32, device=a.device)) if out2_shape is not None else out
     if out2_shape is not None:
         out2 = torch.empty((k,) + out2_shape, dtype=torch.float32, device=a.device)
         _lib.check(fn(_p(a), k, _p(out), _p(out2), _stream()), fn_name)
