@@ -86,6 +86,11 @@ SIGNATURES = {
     "creg_pose_coords_f64": (ctypes.c_int, [vp, i64, vp, vp]),
     "creg_link_sweep_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "creg_coord_mst_f64": (ctypes.c_int, [vp, i32, i32, vp, vp, vp]),
+    "creg_joint_axes_samples": (ctypes.c_int, [i32, i32, i32]),
+    "creg_joint_axes_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                           vp, vp, vp, vp]),
+    "creg_link_clouds_f64": (ctypes.c_int, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp,
+                                            vp]),
     "creg_train_workspace_bytes": (sz, [ctypes.POINTER(TrainShape)]),
     "creg_train_plan_create": (ctypes.c_int, [ctypes.POINTER(TrainShape), vp, sz, ctypes.POINTER(vp)]),
     "creg_train_plan_run": (ctypes.c_int, [vp, ctypes.POINTER(TrainArgs), vp]),

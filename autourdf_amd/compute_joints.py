@@ -1,0 +1,214 @@
+"""Drop-in for the reference's ``PointCloud/compute_joints.py``: joint axes of the kinematic tree and the URDF writer
+(SURVEY 8(f) N4).
+
+``estimate_joint_axes_from_tree`` (:216-268) is ONE launch of ``creg_joint_axes_f64``: every joint, every sequence,
+phase and step, with the per-link mean poses (:10-39), the relative motions (:41-52, :93-102), the screw axes
+(transforms3d's ``aff2axangle`` in closed form), the principal axis and the refined joint point (:124-214).
+``get_cluster_pose_mean``, ``average_quaternions`` and ``calculate_joint_axis_relative`` go through the same launch as
+batches of one.  ``relative_transform`` and ``optimize_joint_axis`` take poses and axes the caller already holds; they
+are the kernel's closed forms restated on the host for a single joint (4x4 products and one 3x3 eigen problem).
+``create_urdf`` (:274-388) writes the same XML; its per-link transforms come from ``creg_link_clouds_f64``.
+The axis sign follows creg.h's convention: the first usable sample of a joint has a positive angle (the reference's
+sign follows np.linalg.eig, so the two agree up to one sign per joint).  ``visualize_urdf`` (pybullet GUI) is out of
+scope.  No CPU fallback.
+"""
+import os
+import xml.etree.ElementTree as ET
+
+import numpy as np
+import torch
+from scipy.spatial.transform import Rotation as R
+
+from . import _lib, ops
+
+
+def _jet(x):
+    """matplotlib's ``get_cmap("jet")(x)`` for scalar x: its 256-entry lookup table, restated."""
+    N = 256
+    segs = {"red": ((0.00, 0, 0), (0.35, 0, 0), (0.66, 1, 1), (0.89, 1, 1), (1.00, 0.5, 0.5)),
+            "green": ((0.000, 0, 0), (0.125, 0, 0), (0.375, 1, 1), (0.640, 1, 1), (0.910, 0, 0), (1.000, 0, 0)),
+            "blue": ((0.00, 0.5, 0.5), (0.11, 1, 1), (0.34, 1, 1), (0.65, 0, 0), (1.00, 0, 0))}
+    rgba = []
+    for ch in ("red", "green", "blue"):
+        a = np.array(segs[ch], dtype=float)
+        xs, y0, y1 = a[:, 0] * (N - 1), a[:, 1], a[:, 2]
+        xind = (N - 1) * np.linspace(0, 1, N)
+        ind = np.searchsorted(xs, xind)[1:-1]
+        dist = (xind[1:-1] - xs[ind - 1]) / (xs[ind] - xs[ind - 1])
+        lut = np.clip(np.concatenate([[y1[0]], dist * (y0[ind] - y1[ind - 1]) + y1[ind - 1], [y0[-1]]]), 0, 1)
+        i = int(x * N)
+        rgba.append(lut[min(max(i, 0), N - 1)])
+    return tuple(rgba) + (1.0,)
+
+
+def _coords(cm_list):
+    c = [np.asarray(cm.coords, np.float64) for cm in cm_list]
+    if len({x.shape for x in c}) != 1:
+        raise ValueError(f"every sequence needs the same (T, K): got {[x.shape for x in c]}")
+    return torch.as_tensor(np.stack(c), device=_lib.device(getattr(cm_list[0], "_M", None))).contiguous()
+
+
+def _one_joint(coords, link_clusters, start_step=0, num_steps=1, interval=1):
+    return ops.joint_axes(coords, link_clusters, [(0, 1)], start_step, num_steps, interval)
+
+
+def get_cluster_pose_mean(cm, cluster, step):
+    """Mean xyz and average quaternion of the clusters at one step (compute_joints.py:10-19)."""
+    c = torch.as_tensor(np.asarray(cm.coords, np.float64)[step][None, None], device=_lib.device()).contiguous()
+    fp = _one_joint(c, [list(cluster), list(cluster)])["first_pose"][0, 0].cpu().numpy()
+    return fp[:3].copy(), fp[3:].copy()
+
+
+def average_quaternions(quaternions):
+    """Top eigenvector of (1/n) sum q q^T (compute_joints.py:21-39); its sign is the eigen solver's."""
+    q = np.asarray(quaternions, np.float64).reshape(-1, 4)
+    c = np.concatenate([np.zeros((len(q), 3)), q], axis=1)[None, None]
+    cl = list(range(len(q)))
+    return _one_joint(torch.as_tensor(c, device=_lib.device()).contiguous(), [cl, cl])["first_pose"][0, 0, 3:].cpu().numpy()
+
+
+def _pose_matrix(pose):
+    pos, ori = pose
+    q = np.asarray(ori, np.float64)
+    w, x, y, z = q
+    s = 2.0 / (q * q).sum()
+    T = np.eye(4)
+    T[:3, :3] = [[1 - s * (y * y + z * z), s * (x * y - z * w), s * (x * z + y * w)],
+                 [s * (x * y + z * w), 1 - s * (x * x + z * z), s * (y * z - x * w)],
+                 [s * (x * z - y * w), s * (y * z + x * w), 1 - s * (x * x + y * y)]]
+    T[:3, 3] = pos
+    return T
+
+
+def relative_transform(pose_parent, pose_child):
+    """inv(T_parent) @ T_child of two (position, quaternion) poses (compute_joints.py:41-52)."""
+    return np.linalg.inv(_pose_matrix(pose_parent)) @ _pose_matrix(pose_child)
+
+
+def calculate_joint_axis_relative(poses_parent, poses_child):
+    """Per-step screw axis of the child relative to the parent (compute_joints.py:54-122): lists (axes, angles, poses),
+    one entry per consecutive pair.  Each (axis, angle) pair has angle in [0, pi]; a step below the usable angle gets
+    NaN axis and point."""
+    n = len(poses_parent)
+    if n < 2:
+        return [], [], []
+    c = np.zeros((1, n, 2, 7))
+    for i, ((pp, po), (cp, co)) in enumerate(zip(poses_parent, poses_child)):
+        c[0, i, 0] = np.concatenate([pp, po])
+        c[0, i, 1] = np.concatenate([cp, co])
+    out = _one_joint(torch.as_tensor(c, device=_lib.device()).contiguous(), [[0], [1]], 0, n, 1)
+    ax, an, pt = (out[k][0].cpu().numpy() for k in ("sample_axis", "sample_angle", "sample_point"))
+    return list(ax), list(an), list(pt)
+
+
+def optimize_joint_axis(poses_parent, poses_child, axes, poses):
+    """Principal axis, global axes, refined global point and its child-frame homogeneous point
+    (compute_joints.py:124-214), with the kernel's closed forms: the top eigenvector of sum a a^T, sign of the first axis,
+    and refine_position's minimiser t* = s_u + (s_v - s_u) r_u / (r_u + r_v) (midpoint when both distances vanish)."""
+    a = np.array([x / np.linalg.norm(x) for x in axes])
+    a0 = a[0]
+    w, V = np.linalg.eigh(a.T @ a)
+    principal_axis = V[:, -1]
+    if np.dot(principal_axis, a0) < 0:
+        principal_axis = -principal_axis
+    principal_pos = np.mean(poses, axis=0)
+    global_axes = [_pose_matrix(p)[:3, :3] @ principal_axis for p in poses_child]
+    Tc = _pose_matrix(poses_child[0]).astype(np.float32).astype(np.float64)
+    g = (Tc @ np.append(principal_pos, 1.0))[:3]
+    u, v = np.asarray(poses_parent[0][0]) - g, np.asarray(poses_child[0][0]) - g
+    su, sv = u @ principal_axis, v @ principal_axis
+    ru, rv = np.linalg.norm(u - su * principal_axis), np.linalg.norm(v - sv * principal_axis)
+    t = su + (sv - su) * (ru / (ru + rv)) if ru + rv > 0 else 0.5 * (su + sv)
+    local = np.linalg.inv(Tc) @ np.append(g + t * principal_axis, 1.0)
+    return principal_axis, global_axes, (Tc @ local)[:3], local
+
+
+def estimate_joint_axes_from_tree(links, cm_list, start_step=0, num_steps=500, interval=1):
+    """Joint axes between connected links of the kinematics tree (compute_joints.py:216-268), one launch.  Returns the
+    reference's list of dicts (parent_link, child_link, local_axis, local_pos, global_pos, global_axis) in its order.
+    A joint without a usable step (the child never turns relative to its parent) raises ValueError."""
+    by_id = {l["id"]: i for i, l in enumerate(links)}
+    pairs = [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+    out = ops.joint_axes(_coords(cm_list), [list(l["cluster_idx"]) for l in links], pairs, start_step, num_steps, interval)
+    res = {k: out[k].cpu().numpy() for k in ("local_axis", "local_pos", "global_pos", "global_axis", "count")}
+    joint_data = []
+    for j, (p, c) in enumerate(pairs):
+        pid, cid = links[p]["id"], links[c]["id"]
+        if res["count"][j] == 0:
+            raise ValueError(f"joint between parent link {pid} and child link {cid}: no step turns the child by at least "
+                             f"{ops.JOINT_THETA_MIN} rad relative to the parent, its axis is undefined")
+        print(f"Joint between parent link {pid} and child link {cid}: axis {res['local_axis'][j]}")
+        joint_data.append({"parent_link": pid, "child_link": cid, "local_axis": res["local_axis"][j],
+                           "local_pos": res["local_pos"][j], "global_pos": res["global_pos"][j],
+                           "global_axis": res["global_axis"][j]})
+    return joint_data
+
+
+def link_transforms(links, cm, time_step=0):
+    """create_urdf's per-link transform (compute_joints.py:278-287): the float32 mean of the clusters' float32 matrices
+    at time_step, from creg_link_clouds_f64 (no points)."""
+    dev = _lib.device(getattr(cm, "_M", None))
+    c = torch.as_tensor(np.asarray(cm.coords, np.float64)[time_step:time_step + 1], device=dev).contiguous()
+    K = c.shape[1]
+    M = torch.eye(4, dtype=torch.float64, device=dev).repeat(1, K, 1, 1)
+    _, mm, _, _, _ = ops.link_clouds(c, M, [list(l["cluster_idx"]) for l in links],
+                                     torch.zeros(0, 3, dtype=torch.float64, device=dev), np.zeros(K + 1, np.int64),
+                                     mean_matrices=True)
+    mm = mm[0].cpu().numpy()
+    return {l["id"]: mm[i] for i, l in enumerate(links)}
+
+
+def create_urdf(links, joint_data, cm, output_file="robot.urdf", mesh_dir="", time_step=0):
+    """Write the estimated robot as URDF (compute_joints.py:274-388): same elements, names, attributes, mesh paths,
+    layout and XML declaration."""
+    robot = ET.Element("robot", name="estimated_robot")
+    link_transforms_ = link_transforms(links, cm, time_step)
+    link_pos_local = {}
+    for joint in joint_data:
+        child_frame = link_transforms_[joint["child_link"]]
+        link_pos_local[joint["child_link"]] = child_frame[:3, 3] - joint["global_pos"][:3]
+    colors = [_jet(i / len(links)) for i in range(len(links))]
+    for link in links:
+        link_elem = ET.SubElement(robot, "link", name=f"link_{link['id']}")
+        transform = link_transforms_[link["id"]]
+        if link["parent_id"] is None:
+            link_pos_local[link["id"]] = transform[:3, 3]
+        xyz = " ".join(map(str, link_pos_local[link["id"]]))
+        rpy = " ".join(map(str, np.zeros(3)))
+        visual = ET.SubElement(link_elem, "visual")
+        ET.SubElement(visual, "origin", xyz=xyz, rpy=rpy)
+        geometry = ET.SubElement(visual, "geometry")
+        mesh_filename = os.path.join(mesh_dir, f"{link['id']:04}.stl")
+        ET.SubElement(geometry, "mesh", filename=mesh_filename, scale="1 1 1")
+        material = ET.SubElement(visual, "material", name=f"material_{link['id']}")
+        rgba = colors[link["id"]][:3] + (1,)
+        ET.SubElement(material, "color", rgba=" ".join(map(str, rgba)))
+        collision = ET.SubElement(link_elem, "collision")
+        ET.SubElement(collision, "origin", xyz=xyz, rpy=rpy)
+        geometry = ET.SubElement(collision, "geometry")
+        ET.SubElement(geometry, "mesh", filename=mesh_filename, scale="1 1 1")
+        inertial = ET.SubElement(link_elem, "inertial")
+        ET.SubElement(inertial, "origin", xyz=xyz, rpy=rpy)
+        ET.SubElement(inertial, "mass", value="1.0")
+        ET.SubElement(inertial, "inertia", ixx="0.1", ixy="0.0", ixz="0.0", iyy="0.1", iyz="0.0", izz="0.1")
+    for joint in joint_data:
+        joint_elem = ET.SubElement(robot, "joint", name=f"joint_{joint['child_link']}", type="revolute")
+        ET.SubElement(joint_elem, "parent", link=f"link_{joint['parent_link']}")
+        ET.SubElement(joint_elem, "child", link=f"link_{joint['child_link']}")
+        parent_transform = link_transforms_[joint["parent_link"]]
+        child_transform = link_transforms_[joint["child_link"]]
+        local_pos = np.linalg.inv(parent_transform) @ np.append(joint["global_pos"], 1)
+        origin_xyz = " ".join(map(str, local_pos[:3] + link_pos_local[joint["parent_link"]]))
+        local_axis = np.linalg.inv(parent_transform[:3, :3]) @ np.append(joint["global_axis"], 0)[:3]
+        local_axis = local_axis / np.linalg.norm(local_axis)
+        relative_rot = np.linalg.inv(parent_transform[:3, :3]) @ child_transform[:3, :3]
+        origin_rpy = " ".join(map(str, R.from_matrix(relative_rot).as_euler("xyz")))
+        ET.SubElement(joint_elem, "origin", xyz=origin_xyz, rpy=origin_rpy)
+        ET.SubElement(joint_elem, "axis", xyz=" ".join(map(str, local_axis)))
+        ET.SubElement(joint_elem, "limit", effort="100", velocity="100", lower="-3.14159", upper="3.14159")
+    tree = ET.ElementTree(robot)
+    ET.indent(tree, space="  ", level=0)
+    if os.path.dirname(output_file):
+        os.makedirs(os.path.dirname(output_file), exist_ok=True)
+    tree.write(output_file, encoding="utf-8", xml_declaration=True)
+    print(f"URDF file saved as {output_file}")

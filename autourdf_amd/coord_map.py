@@ -15,8 +15,10 @@ The graph half of the URDF stage is here too: ``coord_clustering`` / ``silhouett
 (:334-349, ``creg_coord_mst_f64``) and ``CoordMap.kinematics_tree`` (:351-441, host bookkeeping over <= 25 links).
 Graphs are ``Graph``, a minimal stand-in for the networkx.Graph surface the reference uses (``nodes``, ``edges``,
 ``neighbors(n)``, insertion-ordered adjacency), and ``connected_components`` walks it exactly as networkx does, so
-the component sets are built in the same insertion order and iterate identically.  Link clouds, joint axes, the
-URDF writer and the GUI of the reference file are not part of this module.
+the component sets are built in the same insertion order and iterate identically.  ``CoordMap.cluster_to_link``
+(:443-502) is one launch of ``creg_link_clouds_f64``; joint axes and the URDF writer are in compute_joints.py.  ``main``
+is the headless part of the reference's command line (:641-792).  The GUI of the reference file is not part of this
+module.
 There is no CPU fallback: the methods need the HIP library and a GPU.
 """
 import glob
@@ -330,3 +332,126 @@ class CoordMap:
         for i, link in enumerate(links):
             print(f'Layer{i} ---', 'Real ID: ', link['id'], 'Tree ID: ', link['tree_id'], 'Parent Link', link['parent_id'])
         return links
+
+    # ---- link clouds (coord_map.py:443-502) ----------------------------------------------------------
+    def cluster_to_link(self, cluster_idx):
+        """Combine the clusters to links: one dict per link with 'matrices' (T,4,4) float32, 'clusters' (T arrays (n,3),
+        link frame) and 'clusters_wf' (T arrays (n,3), world frame), every frame and link in one launch of
+        creg_link_clouds_f64."""
+        T, K = self.coords.shape[:2]
+        dev = _lib.device(getattr(self, "_M", None))
+        M = getattr(self, "_M", None)
+        if M is None:
+            M = torch.as_tensor(np.asarray(self.matrices, np.float64))
+        M = M.to(dev).contiguous()
+        idx = [list(c) for c in cluster_idx]
+        used = {int(k) for c in idx for k in c}
+        clouds, sizes = [], np.zeros(T * K, np.int64)
+        for t in range(T):
+            for k in range(K):
+                if k not in used:                                 # never read, as in the reference
+                    continue
+                c = np.asarray(self.clusters[t][str(k)], np.float64).reshape(-1, 3)    # KeyError when missing
+                clouds.append(c)
+                sizes[t * K + k] = len(c)
+        pts = torch.as_tensor(np.concatenate(clouds) if clouds else np.zeros((0, 3)), device=dev).contiguous()
+        coords = torch.as_tensor(np.asarray(self.coords, np.float64), device=dev).contiguous()
+        lm, _, wf, lf, oo = ops.link_clouds(coords, M, idx, pts, np.concatenate([[0], np.cumsum(sizes)]))
+        lm, wf, lf = lm.cpu().numpy(), wf.cpu().numpy(), lf.cpu().numpy()
+        L = len(idx)
+        return [{'matrices': lm[:, l],
+                 'clusters': [lf[oo[t * L + l]:oo[t * L + l + 1]] for t in range(T)],
+                 'clusters_wf': [wf[oo[t * L + l]:oo[t * L + l + 1]] for t in range(T)]} for l in range(L)]
+
+
+def _parser():
+    """The reference's flags (coord_map.py:738-751)."""
+    import argparse
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--robot', type=str, default='wx200_5')
+    parser.add_argument('--xyz_r', type=float, default=0.5)
+    parser.add_argument('--start_steps', type=int, default=0)
+    parser.add_argument('--end_steps', type=int, default=10)  # number of frames/steps
+    parser.add_argument('--start_video', type=int, default=0)
+    parser.add_argument('--end_video', type=int, default=1)  # number of videos, each video is a sequence of frames
+    parser.add_argument('--unknown_dof', action='store_true')
+    parser.add_argument('--vis_flow', action='store_true')
+    parser.add_argument('--num_cameras', type=int, default=20)  # number of cameras
+    parser.add_argument('--step_size', type=int, default=4)  # motor step size
+    parser.add_argument('--diff', action='store_true')
+    parser.add_argument('--legacy', action='store_true')
+    return parser
+
+
+def main(argv=None):
+    """The reference's ``python coord_map.py`` (coord_map.py:641-792) without its viewers, plots and meshing: sum maps,
+    MST, link discovery, kinematic tree, joint axes, link clouds, their ICP refinement and the URDF file.  Paths are
+    the reference's, relative to the working directory, and ``parameters.json`` is read from there."""
+    import json
+    import os
+
+    from . import prefer_device_kernargs
+    prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
+    from .compute_joints import create_urdf, estimate_joint_axes_from_tree
+    from .link import refine_links_clusters, save_links
+    args = _parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("autourdf_amd.coord_map needs an MI355X: no GPU is visible and there is no CPU path")
+    with open('parameters.json') as f:
+        robot_params = json.load(f)[args.robot]
+    ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
+    STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
+    part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
+    link_path = f'data/mesh/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
+    raw_path_list = sorted(glob.glob(f'data/raw/{ROBOT}/{STEP}_deg_{CAMS}_cams/*/'))
+    if len(raw_path_list) == 0:                                      # real data
+        raw_path_list = sorted(glob.glob(f'data/raw/{ROBOT}/*/'))
+    sub_part_path = sorted(glob.glob(part_path + '*/'))[args.start_video:args.end_video]
+    sub_raw_path = raw_path_list[args.start_video:args.end_video]
+    if not sub_part_path or len(sub_raw_path) < len(sub_part_path):
+        raise FileNotFoundError(f"need registered sequences under {part_path} and their raw frames under data/raw/{ROBOT}/")
+    print(sub_part_path)
+
+    cm_list, sum_map_list = [], []
+    for i, path in enumerate(sub_part_path):
+        cm = CoordMap(path, sub_raw_path[i], start_steps=START, end_steps=END)
+        if args.legacy:
+            _, sum_map = cm.coord_dist_map_legacy(diff=False)
+        else:
+            _, sum_map = cm.coord_dist_map(diff=args.diff)
+        cm_list.append(cm)
+        sum_map_list.append(sum_map)
+    sum_map = np.mean(sum_map_list, axis=0)
+    sum_map = (sum_map - np.min(sum_map)) / (np.max(sum_map) - np.min(sum_map))
+
+    g0 = cm_list[0].coord_mst()
+    if args.unknown_dof:
+        test_num_links = (4, min(25, cm_list[0].num_coords))
+        cluster_idx, g1, s_score_list, nls = silhouette_score_method(cm_list[0].num_coords, sum_map,
+                                                                     link_range=test_num_links)
+        if len(sub_part_path) == 1:
+            print("score folder", sub_part_path[0] + 'score/')
+            os.makedirs(sub_part_path[0] + 'score/', exist_ok=True)
+            with open(sub_part_path[0] + 'score/silhouette_score.txt', 'w') as f:
+                f.write(f"Silhouette Score: {s_score_list}\n")
+                f.write(f"Number of Links: {nls}\n")
+        dof = len(cluster_idx) - 1
+    else:
+        dof = robot_params['dof']
+        cluster_idx, g1, _ = coord_clustering(cm_list[0].num_coords, sum_map, num_links=dof + 1)
+
+    links = cm_list[0].kinematics_tree(g0, g1)
+    joint_data = estimate_joint_axes_from_tree(links, cm_list, START, END - START, 4)
+    sub_link_path = [link_path + path.split('/')[-2] + '/' for path in sub_part_path][:1]
+    save_links(cm_list, cluster_idx, sub_link_path, START, END)
+    refine_links_clusters(sub_link_path, START, END, dof)
+    print("skipped (out of scope): the cluster / link viewers and plots, visualize_links, link_mesh (meshing), "
+          "visualize_kinematic_tree and visualize_urdf")
+    os.makedirs(f'data/urdf/{ROBOT}_{NUM_SEG}_seg/', exist_ok=True)
+    urdf_path = f'data/urdf/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams.urdf'
+    create_urdf(links, joint_data, cm_list[0], urdf_path, sub_link_path[0])
+    return urdf_path
+
+
+if __name__ == "__main__":
+    main()

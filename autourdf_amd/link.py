@@ -1,5 +1,6 @@
-"""Drop-in for ``refine_links_clusters`` of the reference's ``PointCloud/link.py`` (:85-127; SURVEY 8(f)
-N3): every link cloud of every time step is registered to the same link at ``start_steps`` by
+"""Drop-in for ``save_links`` and ``refine_links_clusters`` of the reference's ``PointCloud/link.py`` (:67-127; SURVEY
+8(f) N3).  ``save_links`` writes what ``CoordMap.cluster_to_link`` computes (one launch per sequence).  In
+``refine_links_clusters`` every link cloud of every time step is registered to the same link at ``start_steps`` by
 point-to-point ICP (threshold 1, identity start, open3d's relative 1e-6 stopping rule) and written,
 moved, to ``cluster_rf/{t:04}.npz``.  The reference runs one Open3D ICP per (time step, link); here the
 links of up to 16 time steps share ONE launch of the K4 kernel in its point-to-point mode
@@ -22,6 +23,20 @@ def _pack(clouds, device):
     off = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32, device=device)
     pts = torch.as_tensor(np.concatenate([np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]), device=device)
     return pts.contiguous(), off
+
+
+def save_links(cm_list, cluster_idx, path_list, start_steps, end_steps):
+    """Save every link's matrices and clouds per time step (same signature and files as link.py:67-82):
+    matrix/{t:04}.npy (L,4,4) float32, cluster/{t:04}.npz (link frame) and cluster_wf/{t:04}.npz (world frame)."""
+    for cm, link_dir in zip(cm_list, path_list):
+        os.makedirs(link_dir + 'cluster', exist_ok=True)
+        os.makedirs(link_dir + 'matrix', exist_ok=True)
+        os.makedirs(link_dir + 'cluster_wf', exist_ok=True)
+        links_cm = cm.cluster_to_link(cluster_idx)
+        for t in range(end_steps - start_steps):
+            np.save(link_dir + f'matrix/{t:04}.npy', [link['matrices'][t] for link in links_cm])
+            save_pc_npz([link['clusters'][t] for link in links_cm], link_dir + f'cluster/{t:04}.npz')
+            save_pc_npz([link['clusters_wf'][t] for link in links_cm], link_dir + f'cluster_wf/{t:04}.npz')
 
 
 def refine_links_clusters(path_list, start_steps, end_steps, dof):

@@ -422,6 +422,155 @@ def coord_mst(coords: torch.Tensor):
     return edges[:K - 1], w[:K - 1]
 
 
+# ------------------------------------------------------------------------------ N4 URDF stage: joint axes, link clouds
+JOINT_MAX_SAMPLES = 4096
+JOINT_THETA_MIN = 2e-4             # rad: a sample below it is not usable (creg.h)
+
+
+def _link_table(link_clusters, K, what):
+    flat, off = [], [0]
+    for l, c in enumerate(link_clusters):
+        c = [int(x) for x in c]
+        if not c:
+            raise ValueError(f"{what}: link {l} has no cluster")
+        bad = [x for x in c if not 0 <= x < K]
+        if bad:
+            raise ValueError(f"{what}: link {l} names clusters {bad} outside [0, {K})")
+        flat.extend(c)
+        off.append(len(flat))
+    return flat, off
+
+
+def joint_samples(S: int, num_steps: int, interval: int) -> int:
+    """Samples per joint: S sequences x sum over phases a < interval of (len(range(a, num_steps, interval)) - 1)^+."""
+    return int(_lib.load(check_device=False).creg_joint_axes_samples(int(S), int(num_steps), int(interval)))
+
+
+def joint_axes(coords: torch.Tensor, link_clusters, joints, start_step: int = 0, num_steps: int = 500, interval: int = 1):
+    """estimate_joint_axes_from_tree's arithmetic for every joint in one launch of creg_joint_axes_f64
+    (joint_axes_prepare, then its launch).
+    coords (S,T,K,7) f64 [xyz, wxyz]; link_clusters: one cluster list per link (set order); joints: (parent, child)
+    indices into link_clusters.  Returns a dict of device tensors: sample_axis (J,NS,3), sample_angle (J,NS),
+    sample_point (J,NS,3), sample_usable (J,NS) bool, local_axis (J,3), local_pos (J,4), global_pos (J,3),
+    global_axis (J,3), count (J), first_pose (J,2,7).  Raises IndexError for a step past T (as numpy indexing would) and
+    ValueError for K > 256, an empty link or more than JOINT_MAX_SAMPLES samples per joint, before any launch."""
+    launch, out = joint_axes_prepare(coords, link_clusters, joints, start_step, num_steps, interval)
+    launch()
+    out["sample_usable"] = out["sample_usable"] != 0
+    return out
+
+
+def joint_axes_prepare(coords: torch.Tensor, link_clusters, joints, start_step: int = 0, num_steps: int = 500,
+                       interval: int = 1):
+    """Checks and device tables of joint_axes, done once: returns (launch, outputs), where launch() only enqueues
+    creg_joint_axes_f64 on the current stream (sample_usable stays int32 here)."""
+    L = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    if coords.dim() != 4 or coords.shape[3] != 7:
+        raise ValueError("joint_axes: coords must be (S,T,K,7)")
+    S, T, K = coords.shape[:3]
+    if K > LINK_SWEEP_MAX_K:
+        raise ValueError(f"joint_axes supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+    start_step, num_steps, interval = int(start_step), int(num_steps), int(interval)
+    if start_step < 0 or num_steps < 1 or interval < 1:
+        raise ValueError(f"joint_axes: need start_step >= 0, num_steps >= 1, interval >= 1 "
+                         f"(got {start_step}, {num_steps}, {interval})")
+    if start_step + num_steps > T:
+        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 0 with size {T}")
+    flat, off = _link_table(link_clusters, K, "joint_axes")
+    jt = [(int(p), int(c)) for p, c in joints]
+    for p, c in jt:
+        if not (0 <= p < len(off) - 1 and 0 <= c < len(off) - 1):
+            raise ValueError(f"joint_axes: joint ({p}, {c}) names a link outside [0, {len(off) - 1})")
+    NS = joint_samples(S, num_steps, interval)
+    if NS > JOINT_MAX_SAMPLES:
+        raise ValueError(f"joint_axes: {NS} samples per joint, at most {JOINT_MAX_SAMPLES} are supported")
+    dev, J = coords.device, len(jt)
+    i32 = dict(dtype=torch.int32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    cl = torch.tensor(flat, **i32)
+    lo = torch.tensor(off, **i32)
+    jn = torch.tensor(jt, **i32).reshape(-1, 2) if J else torch.zeros(1, 2, **i32)
+    out = {"sample_axis": torch.empty(J, NS, 3, **f64), "sample_angle": torch.empty(J, NS, **f64),
+           "sample_point": torch.empty(J, NS, 3, **f64), "sample_usable": torch.empty(J, NS, **i32),
+           "local_axis": torch.empty(J, 3, **f64), "local_pos": torch.empty(J, 4, **f64),
+           "global_pos": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
+           "count": torch.zeros(J, **i32), "first_pose": torch.empty(J, 2, 7, **f64)}
+    smp = (_p(out["sample_axis"]), _p(out["sample_angle"]), _p(out["sample_point"]),
+           _p(out["sample_usable"])) if NS else (None, None, None, None)
+    args = (_p(coords), S, T, K, _p(cl), _p(lo), len(flat), _p(jn), J, start_step, num_steps, interval, *smp,
+            _p(out["local_axis"]), _p(out["local_pos"]), _p(out["global_pos"]), _p(out["global_axis"]), _p(out["count"]),
+            _p(out["first_pose"]))
+    keep = (coords, cl, lo, jn)                                    # the tables must outlive every launch
+
+    def launch():
+        if J:
+            _lib.check(L.creg_joint_axes_f64(*args, _stream()), "creg_joint_axes_f64")
+        return keep
+    return launch, out
+
+
+def link_clouds_bytes(n_points: int, n_out: int, T: int, K: int, L: int) -> int:
+    """HBM traffic of one creg_link_clouds_f64 launch: points read, both clouds written, poses and offsets."""
+    return 24 * n_points + 48 * n_out + T * K * (7 + 16) * 8 + (T * K + T * L + 2) * 8 + T * L * 2 * 64
+
+
+def link_clouds(coords: torch.Tensor, matrices: torch.Tensor, link_clusters, points: torch.Tensor, point_offsets,
+                mean_matrices: bool = False):
+    """CoordMap.cluster_to_link's arithmetic for every frame and link in one launch of creg_link_clouds_f64
+    (link_clouds_prepare, then its launch).
+    coords (T,K,7) f64, matrices (T,K,4,4) f64, points (N,3) f64 every frame's local cluster points packed frame-major
+    with point_offsets (T*K+1) (host ints: cluster k of frame t is rows [off[t*K+k], off[t*K+k+1])).
+    Returns (link_matrices (T,L,4,4) f32, mean_matrices (T,L,4,4) f32 or None, clouds_wf (M,3) f64, clouds_lf (M,3) f64,
+    out_offsets (T*L+1) numpy int64: link l of frame t is rows [o[t*L+l], o[t*L+l+1]))."""
+    launch, out = link_clouds_prepare(coords, matrices, link_clusters, points, point_offsets, mean_matrices)
+    launch()
+    return out
+
+
+def link_clouds_prepare(coords: torch.Tensor, matrices: torch.Tensor, link_clusters, points: torch.Tensor, point_offsets,
+                        mean_matrices: bool = False):
+    """Checks, output sizing and device tables of link_clouds, done once: returns (launch, outputs), where launch() only
+    enqueues creg_link_clouds_f64 on the current stream."""
+    L_ = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    matrices = _need(matrices, torch.float64, "matrices")
+    points = _need(points, torch.float64, "points")
+    if coords.dim() != 3 or coords.shape[2] != 7 or tuple(matrices.shape) != tuple(coords.shape[:2]) + (4, 4):
+        raise ValueError("link_clouds: coords must be (T,K,7) and matrices (T,K,4,4)")
+    T, K = coords.shape[:2]
+    if K > LINK_SWEEP_MAX_K:
+        raise ValueError(f"link_clouds supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("link_clouds: points must be (N,3)")
+    flat, off = _link_table(link_clusters, K, "link_clouds")
+    L = len(off) - 1
+    po = np.asarray(point_offsets, np.int64)
+    if po.shape != (T * K + 1,) or po[0] != 0 or np.any(np.diff(po) < 0) or po[-1] != points.shape[0]:
+        raise ValueError("link_clouds: point_offsets must be (T*K+1) non-decreasing from 0 to len(points)")
+    member = np.zeros((K, L), np.int64)                            # member[k, l]: times cluster k appears in link l
+    np.add.at(member, (np.asarray(flat), np.repeat(np.arange(L), np.diff(off))), 1)
+    per = np.diff(po).reshape(T, K) @ member                       # (T, L) rows of every (frame, link)
+    oo = np.concatenate([[0], np.cumsum(per.reshape(-1))]).astype(np.int64)
+    dev = coords.device
+    n_out = int(oo[-1])
+    lm = torch.empty(T, L, 4, 4, dtype=torch.float32, device=dev)
+    mm = torch.empty(T, L, 4, 4, dtype=torch.float32, device=dev) if mean_matrices else None
+    wf = torch.empty(max(n_out, 1), 3, dtype=torch.float64, device=dev)
+    lf = torch.empty(max(n_out, 1), 3, dtype=torch.float64, device=dev)
+    cl = torch.tensor(flat, dtype=torch.int32, device=dev)          # named: they must outlive the launch call
+    lo = torch.tensor(off, dtype=torch.int32, device=dev)
+    po_d, oo_d = torch.from_numpy(po).to(dev), torch.from_numpy(oo).to(dev)
+    args = (_p(coords), _p(matrices), T, K, _p(cl), _p(lo), len(flat), L, _p(points) if points.shape[0] else None,
+            _p(po_d), int(po[-1]), _p(oo_d), n_out, int(per.max()), _p(lm), _p(mm), _p(wf), _p(lf))
+    keep = (coords, matrices, points, cl, lo, po_d, oo_d)          # the tables must outlive every launch
+
+    def launch():
+        _lib.check(L_.creg_link_clouds_f64(*args, _stream()), "creg_link_clouds_f64")
+        return keep
+    return launch, (lm, mm, wf[:n_out], lf[:n_out], oo)
+
+
 # ------------------------------------------------------------------------------ K5 row conversions
 def masked_icp(local: torch.Tensor, world: torch.Tensor, offsets: torch.Tensor, frame: torch.Tensor, M: torch.Tensor,
                scale: float = 1.2, th: float = 1.0, max_iteration: int = 10000, ori: bool = False,

@@ -291,6 +291,56 @@ int creg_coord_mst_f64(const double* coords, int32_t T, int32_t K, int32_t* edge
                        creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * N4  the geometric half of the URDF stage (compute_joints.py:10-268, coord_map.py:443-502), fp64.
+ *
+ * Links are passed as a flat cluster list link_clusters (n_link_clusters int32) plus link_offsets (L+1 int32): link l is
+ * link_clusters[link_offsets[l] .. link_offsets[l+1]), in the iteration order of the reference's cluster_idx set (the
+ * kernels never sort it; every sum runs in that order).  Every link holds >= 1 cluster, every index is in [0, K), K <= 256.
+ *
+ * creg_joint_axes_f64: estimate_joint_axes_from_tree for every joint in one launch (one workgroup per joint).
+ *   coords (S,T,K,7) fp64 = load_matrix's [xyz, wxyz] of S sequences.  joints (J,2) int32 = (parent link, child link) as
+ *   indices into link_offsets, in the order the reference visits them.  Samples of a joint: sequence-major, then phase
+ *   a in [0, interval), then step k >= 1 of range(start_step + a, start_step + num_steps, interval); sample (s, a, k)
+ *   relates coords[s, i - interval] and coords[s, i], i = start_step + a + k * interval.  start_step + num_steps <= T
+ *   (the host raises IndexError first); creg_joint_axes_samples(S, num_steps, interval) = NS <= 4096 samples per joint.
+ *   Per sample (J,NS): sample_axis (3) unit direction, sample_angle in [0, pi], sample_point (3) the canonical point of the
+ *   axis (init_position, compute_joints.py:68-77), sample_usable int32.  Each sample's angle is >= 0 (axis and angle as
+ *   one pair (d, theta); the reference may return (-d, -theta)).  A sample is usable iff theta >= 2e-4 rad and the
+ *   outputs are finite; an unusable sample has NaN axis and point.
+ *   Per joint: local_axis (J,3) = the principal axis, local_pos (J,4) = optimize_joint_axis's principal_pos (homogeneous),
+ *   global_pos (J,3), global_axis (J,3) = R_child(first pose) @ local_axis, count (J) int32 usable samples,
+ *   first_pose (J,2,7) or NULL = get_cluster_pose_mean of the parent and the child at sequence 0, step start_step
+ *   ([xyz, wxyz]; the average quaternion's sign is the eigen solver's).
+ *   SIGN CONVENTION: local_axis points so that the joint's first usable sample has a positive angle (the reference's
+ *   principal axis follows the sign np.linalg.eig gives its first axis: it equals this one up to one sign per joint).
+ *   A joint with count 0 gets NaN outputs.  The child's first-pose matrix is rounded to float32 as the reference's
+ *   xyzquant2matrix_torch rounds it, and inverted as a general 4x4 in fp64.
+ *
+ * creg_link_clouds_f64: CoordMap.cluster_to_link for T frames and L links: workgroups over (frame, link) x slices of
+ *   1024 output rows; max_link_rows (HOST) = the largest out_offsets[i+1] - out_offsets[i] sizes the slices (a smaller
+ *   value costs speed, never rows: a workgroup strides over the slices of its (frame, link)).
+ *   coords (T,K,7) fp64, matrices (T,K,4,4) fp64 the cluster poses.  points (n_points,3) fp64: every frame's local
+ *   cluster points packed frame-major, cluster k of frame t at point_offsets[t*K + k .. t*K + k + 1) (T*K + 1 int64).
+ *   out_offsets (T*L + 1 int64): link l of frame t fills rows out_offsets[t*L + l ..) of clouds_wf / clouds_lf
+ *   (n_out,3) fp64, its clusters concatenated in set order (the host sizes them; nothing is written past n_out).
+ *   link_matrices (T,L,4,4) float32 = quaternion_to_matrix of the fp64 mean cluster coords, rounded to float32.
+ *   mean_matrices (T,L,4,4) float32 or NULL = create_urdf's link transform: the float32 mean (summed in set order) of the
+ *   clusters' float32 matrices.  clouds_wf = local @ R_k^T + t_k; clouds_lf = clouds_wf moved by the fp64 inverse of the
+ *   float32 link matrix.  Traffic: 24 B read and 48 B written per point. */
+int creg_joint_axes_samples(int32_t S, int32_t num_steps, int32_t interval);
+int creg_joint_axes_f64(const double* coords, int32_t S, int32_t T, int32_t K, const int32_t* link_clusters,
+                        const int32_t* link_offsets, int32_t n_link_clusters, const int32_t* joints, int32_t J,
+                        int32_t start_step, int32_t num_steps, int32_t interval, double* sample_axis, double* sample_angle,
+                        double* sample_point, int32_t* sample_usable, double* local_axis, double* local_pos,
+                        double* global_pos, double* global_axis, int32_t* count, double* first_pose,
+                        creg_stream_t stream);
+int creg_link_clouds_f64(const double* coords, const double* matrices, int32_t T, int32_t K, const int32_t* link_clusters,
+                         const int32_t* link_offsets, int32_t n_link_clusters, int32_t L, const double* points,
+                         const int64_t* point_offsets, int64_t n_points, const int64_t* out_offsets, int64_t n_out,
+                         int64_t max_link_rows, float* link_matrices, float* mean_matrices, double* clouds_wf,
+                         double* clouds_lf, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The `--normal` branch (mlp_reg.py:190-203, cluster_icp.py:49-62; CLI flag mlp_reg.py:399): Open3D normal estimation +
  * orientation, then sklearn k_means over [xyz | 0.5 * normal].
  *

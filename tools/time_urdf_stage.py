@@ -1,7 +1,11 @@
-"""Time the graph half of the URDF stage on the GPU at K = 20 and K = 45 (S = 5 sequences, T = 10 steps):
-event-timed microseconds per launch of creg_link_sweep_f64 (link counts 4 .. min(25, K) - 1, as main()'s
---unknown_dof passes) and creg_coord_mst_f64, and the wall time of the whole Python stage (sum maps of S sequences,
-silhouette_score_method, coord_mst, kinematics_tree) around a device synchronise, after a warm-up.
+"""Time the URDF stage on the GPU at K = 20 and K = 45 (S = 5 sequences, T = 10 steps): event-timed microseconds per
+launch of creg_link_sweep_f64 (link counts 4 .. min(25, K) - 1, as main()'s --unknown_dof passes), creg_coord_mst_f64,
+creg_joint_axes_f64 (interval 4, as main() passes) and creg_link_clouds_f64 (PTS points per cluster and frame, with the
+fraction of the MI355X's 8 TB/s HBM peak its bytes reach over that time), and the wall time of the whole Python stage
+(sum maps of S sequences, silhouette_score_method, coord_mst, kinematics_tree, estimate_joint_axes_from_tree,
+cluster_to_link and create_urdf) around a device synchronise, after a warm-up.  The joint and link-cloud figures time
+back-to-back launches only: their arguments and device tables are built once before the timed region (ops.*_prepare).
+The wrapper's own per-call cost (checks, tables, host-to-device copies, output sizing) is printed beside them.
 
     python tools/time_urdf_stage.py [--reps 200]
 """
@@ -11,13 +15,14 @@ import io
 import json
 import os
 import sys
+import tempfile
 import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from autourdf_amd import coord_map, ops  # noqa: E402
+from autourdf_amd import compute_joints, coord_map, ops  # noqa: E402
 from scipy.spatial.transform import Rotation  # noqa: E402
 
 
@@ -66,8 +71,17 @@ def event_us(fn, reps):
     return a.elapsed_time(b) * 1000.0 / reps
 
 
-def stage(Ms, bbox, K):
-    cms = [coord_map.CoordMap.from_arrays(M, bbox) for M in Ms]
+PTS = 400                       # points per cluster and frame
+HBM_PEAK = 8.0e12               # bytes / s
+
+
+def clouds(T, K, seed):
+    rng = np.random.default_rng(seed)
+    return [{str(k): rng.normal(scale=0.02, size=(PTS, 3)).astype(np.float32) for k in range(K)} for _ in range(T)]
+
+
+def stage(Ms, bbox, K, clusters, out_dir):
+    cms = [coord_map.CoordMap.from_arrays(M, bbox, clusters) for M in Ms]
     sums = [cm.coord_dist_map(diff=True)[1] for cm in cms]
     sm = np.mean(sums, axis=0)
     sm = (sm - sm.min()) / (sm.max() - sm.min())
@@ -75,8 +89,11 @@ def stage(Ms, bbox, K):
         cluster_idx, g1, _, _ = coord_map.silhouette_score_method(K, sm, link_range=(4, min(25, K)))
         g0 = cms[0].coord_mst()
         links = cms[0].kinematics_tree(g0, g1)
+        joint_data = compute_joints.estimate_joint_axes_from_tree(links, cms, 0, cms[0].coords.shape[0], 4)
+        cms[0].cluster_to_link(cluster_idx)
+        compute_joints.create_urdf(links, joint_data, cms[0], os.path.join(out_dir, "robot.urdf"), out_dir)
     torch.cuda.synchronize()
-    return len(links)
+    return links
 
 
 def main():
@@ -93,14 +110,33 @@ def main():
         coords = torch.from_numpy(np.asarray(cm.coords, np.float64)).to(dev)
         sweep = event_us(lambda: ops.link_sweep(sm, 4, min(25, K)), args.reps)
         mst = event_us(lambda: ops.coord_mst(coords), args.reps)
-        stage(Ms, 0.9, K)                                         # warm-up
-        t0 = time.perf_counter()
-        n = 5
-        for _ in range(n):
-            nlinks = stage(Ms, 0.9, K)
-        wall = (time.perf_counter() - t0) / n
+        cl = clouds(10, K, K)
+        with tempfile.TemporaryDirectory() as out_dir:
+            links = stage(Ms, 0.9, K, cl, out_dir)                # warm-up
+            t0 = time.perf_counter()
+            n = 5
+            for _ in range(n):
+                links = stage(Ms, 0.9, K, cl, out_dir)
+            wall = (time.perf_counter() - t0) / n
+        lc = [list(l["cluster_idx"]) for l in links]
+        by_id = {l["id"]: i for i, l in enumerate(links)}
+        pairs = [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+        all_coords = torch.from_numpy(np.stack([ops.pose_coords(m).cpu().numpy() for m in Ms])).to(dev)
+        launch_j, _ = ops.joint_axes_prepare(all_coords, lc, pairs, 0, 10, 4)
+        joints = event_us(launch_j, args.reps)
+        joints_call = event_us(lambda: ops.joint_axes(all_coords, lc, pairs, 0, 10, 4), args.reps)
+        pts = torch.from_numpy(np.concatenate([c[str(k)] for c in cl for k in range(K)]).astype(np.float64)).to(dev)
+        po = np.arange(10 * K + 1, dtype=np.int64) * PTS
+        launch_c, _ = ops.link_clouds_prepare(coords, Ms[0], lc, pts, po)
+        lcl = event_us(launch_c, args.reps)
+        lcl_call = event_us(lambda: ops.link_clouds(coords, Ms[0], lc, pts, po), args.reps)
+        nbytes = ops.link_clouds_bytes(len(pts), len(pts), 10, K, len(lc))
         print(json.dumps({"K": K, "S": 5, "T": 10, "link_sweep_us": round(sweep, 2), "coord_mst_us": round(mst, 2),
-                          "stage_wall_ms": round(wall * 1e3, 3), "links": nlinks}), flush=True)
+                          "joints": len(pairs), "joint_axes_us": round(joints, 2),
+                          "joint_axes_wrapper_call_us": round(joints_call, 2), "points": len(pts),
+                          "link_clouds_us": round(lcl, 2), "link_clouds_wrapper_call_us": round(lcl_call, 2),
+                          "link_clouds_bytes": nbytes, "link_clouds_hbm_fraction": round(nbytes / (lcl * 1e-6) / HBM_PEAK, 4),
+                          "stage_wall_ms": round(wall * 1e3, 3), "links": len(links)}), flush=True)
 
 
 if __name__ == "__main__":
