@@ -88,9 +88,11 @@ __device__ void smallest_eigvec(const double Cin[6], double* nrm) {
             eigvec_deflated(A, v2, e1, v1);
             cross3(v1, v2, nrm);
         } else eigvec_by_rows(A, e0, nrm);
-    } else {                                            // diagonal matrix: the axis of the smallest entry (z on ties, as the branch order gives)
+    } else {                                            // diagonal matrix: the axis of the smallest entry; z whenever z is among the
+        // smallest, y when only x and y tie (`<=` below: z there would be the LARGEST eigenvalue's axis, e.g. for an exact line
+        // along z, C = diag(0, 0, c))
         nrm[0] = (A[0] < A[3] && A[0] < A[5]) ? 1.0 : 0.0;
-        nrm[1] = (nrm[0] == 0.0 && A[3] < A[0] && A[3] < A[5]) ? 1.0 : 0.0;
+        nrm[1] = (nrm[0] == 0.0 && A[3] <= A[0] && A[3] < A[5]) ? 1.0 : 0.0;
         nrm[2] = (nrm[0] == 0.0 && nrm[1] == 0.0) ? 1.0 : 0.0;
     }
 }
@@ -154,8 +156,9 @@ using namespace creg;
 
 extern "C" int creg_knn_normals_f64(const double* X, int64_t n, double radius, int32_t max_nn, int32_t* idx_out, int32_t* cnt_out,
                                     double* normals, creg_stream_t stream) {
+    CREG_REQUIRE(n >= 1 && n < (1ll << 31) && max_nn >= 1 && max_nn <= KNN_MAX,
+                 "creg_knn_normals_f64: needs 1 <= n < 2^31 and 1 <= max_nn <= %d (n = %lld, max_nn = %d)", KNN_MAX, (long long)n, (int)max_nn);
     CREG_REQUIRE(X && (idx_out || cnt_out || normals), "creg_knn_normals_f64: null pointer");
-    CREG_REQUIRE(n >= 1 && n < (1ll << 31) && max_nn >= 1 && max_nn <= KNN_MAX, "creg_knn_normals_f64: needs 1 <= max_nn <= %d", KNN_MAX);
     const int smem = (int)(sizeof(double) * 3 * KNN_TILE + (sizeof(double) + sizeof(int)) * KNN_MAX * KNN_Q);
     hipLaunchKernelGGL(k_knn_normals, dim3(cdiv(n, KNN_Q)), dim3(KNN_Q), smem, (hipStream_t)stream, X, (int)n,
                        radius > 0 ? radius * radius : -1.0, (int)max_nn, idx_out, cnt_out, normals);

@@ -349,7 +349,10 @@ int creg_link_clouds_f64(const double* coords, const double* matrices, int32_t T
  * <= 0 none (SearchKNN).  idx_out (n, max_nn) int32 (-1 past the count), cnt_out (n) int32, normals (n,3) fp64 -- any may be
  * NULL.  normals = PointCloud::EstimateNormals of those neighbourhoods: unit eigenvector of the smallest eigenvalue of their
  * covariance (raw-moment form), (0,0,1) for fewer than three neighbours; signs are NOT oriented (the host does that:
- * autourdf_amd/normals.py, orient_normals_consistent_tangent_plane). */
+ * autourdf_amd/normals.py, orient_normals_consistent_tangent_plane).  An exactly diagonal covariance gives the axis of its
+ * smallest entry: z whenever z is among the smallest, y when only x and y tie.  A covariance that is exactly 0 gives (0,0,1).
+ * n < 1 (an empty cloud), max_nn < 1 or max_nn > 32 return CREG_EINVAL with creg_last_error() set and launch nothing; the
+ * Python wrapper (ops.knn_normals) raises RuntimeError with that text. */
 int creg_knn_normals_f64(const double* X, int64_t n, double radius, int32_t max_nn, int32_t* idx_out, int32_t* cnt_out,
                          double* normals, creg_stream_t stream);
 /* sklearn.cluster.k_means(X, init=<array>, n_clusters=k, n_init=1) over DIM-dimensional features (dim = 6: the --normal
