@@ -324,6 +324,9 @@ int creg_coord_mst_f64(const double* coords, int32_t T, int32_t K, int32_t* edge
  *   out_offsets (T*L + 1 int64): link l of frame t fills rows out_offsets[t*L + l ..) of clouds_wf / clouds_lf
  *   (n_out,3) fp64, its clusters concatenated in set order (the host sizes them; nothing is written past n_out).
  *   link_matrices (T,L,4,4) float32 = quaternion_to_matrix of the fp64 mean cluster coords, rounded to float32.
+ *   A link whose cluster quaternions sum to exactly zero (q and -q) divides by |q|^2 = 0 as the reference does: the
+ *   rotation block of its link_matrices is NaN (translation and last row stay finite) and its clouds_lf rows are NaN;
+ *   its clouds_wf and mean_matrices, and every other (frame, link) of the launch, are unaffected.
  *   mean_matrices (T,L,4,4) float32 or NULL = create_urdf's link transform: the float32 mean (summed in set order) of the
  *   clusters' float32 matrices.  clouds_wf = local @ R_k^T + t_k; clouds_lf = clouds_wf moved by the fp64 inverse of the
  *   float32 link matrix.  Traffic: 24 B read and 48 B written per point. */
