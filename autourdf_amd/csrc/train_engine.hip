@@ -1,21 +1,22 @@
 // train_engine.hip -- A1: the whole `train` loop of the reference (PointCloud/mlp_reg.py:17-152)
-// as a device-resident plan.  One epoch = FIVE small launches, no host round trip (round 3: the forward of the
-// hidden layers no longer has a launch of its own -- every parameter row is read once per epoch, by the kernel
-// that updates it, which also computes the NEXT epoch's activation of that row from the registers it holds):
+// as a device-resident plan.  One epoch = FIVE small launches (enqueue_epoch), no host round trip; every parameter
+// row is read once per epoch, by the role that updates it:
 //
 //   k_head    output layer(s) + residual + pose assembly + calculate_pc (mlp_reg.py:62-94,155-170),
 //             one workgroup per pose row / cluster
-//   k_nn_l1   L1 nearest neighbour both ways (chamfer_distance, mlp_reg.py:96); its epilogue emits
-//             the loss partials and the sign scatter of the y->x term (integer atomics: exact)
+//   NN        L1 nearest neighbour both ways (chamfer_distance, mlp_reg.py:96): k_nn_rows, k_nn_plan or k_nn_l1 by
+//             problem size (launch_nn); its epilogue emits the loss partials and the sign scatter of the y->x term
+//             (integer atomics: exact)
 //   k_gradc   loss, best tracking (mlp_reg.py:102-111), ReduceLROnPlateau, Adam scalars, early stop;
 //             per-cluster reduction to dL/dR, dL/dt, backward through the pose head and the output
 //             layer(s): its pose row of dL/d(hidden pre-activation)
-//   k_bwd2    backward through the hidden layer(s) to the encoder activation, COMPLETE per column block
-//             (a workgroup owns 16 hidden units of the encoder and all H2 rows of their W2 columns), then
-//             those encoder rows' weight gradients + Adam and the NEXT epoch's encoder activation
-//   k_dw      hidden / output rows: weight gradients fused with the Adam update (no gradient buffer), and
-//             -- for the hidden rows -- the NEXT epoch's hidden activation from the just-updated weights
-//   (k_l1, k_l2: the first epoch's activations, once per train)
+//   k_bd      two independent roles side by side, told apart by block index:
+//             B (bwd2_role)  backward through the hidden layer(s) to the encoder activation, COMPLETE per column block
+//                            (a workgroup owns 16 hidden units of the encoder and all H2 rows of their W2 columns), then
+//                            those encoder rows' weight gradients + Adam and the NEXT epoch's encoder activation
+//             D (dw_role)    hidden / output rows: weight gradients merged with the Adam update (no gradient buffer)
+//   k_l2      the NEXT epoch's hidden activation, from B's encoder activation and D's updated hidden rows
+//   (k_l1, and k_l2 once more: the first epoch's activations, once per train)
 //
 // Everything is fp32 like the reference; every reduction has a fixed order (bit-reproducible
 // run to run).  State that the reference keeps in Python (min_loss, count, scheduler, lr) lives in
@@ -29,10 +30,6 @@
 #include <vector>
 #include "creg_common.h"
 #include "nn_l1.h"
-
-#ifndef CREG_L2_IN_BD_DEFAULT
-#define CREG_L2_IN_BD_DEFAULT false        // (until measured faster)
-#endif
 
 namespace creg {
 
@@ -85,8 +82,6 @@ struct Ws {         // device pointers into the caller's workspace
     int* off;
     Hyper* hyper;
     unsigned long long* ysum;   // [4] per chunk of the target frame: fingerprint of the points its k-d leaves were built from (k_sort_y)
-    int* sync;          // fused backward launch (k_gbd): [0] arrivals of the gradient role's blocks (k_head zeroes it every epoch),
-                        //   [32 .. 35] (its own 128-byte line) the record the consumers need of the advanced state: stopped, step_size, bc2_sqrt
 };
 
 // Problem b of a batch lives in its own copy of the workspace layout, `bytes` = b * stride further on:
@@ -180,7 +175,6 @@ __global__ __launch_bounds__(256) void k_prep(Dims D, Ws W0, size_t bstride, Pre
             s.bc2_sqrt = 1.f; s.last_loss = NAN;
             s.next_bc1 = 1.0 - 0.9; s.next_bc2s = (float)sqrt(1.0 - 0.999);         // step 1 (the tables are filled by this launch)
             W.state[0] = s; W.state[1] = s;
-            for (int i = 0; i < 64; ++i) W.sync[i] = 0;          // [1]: arrivals of the backward launch's B role since the train began (k_bd with the next hidden activation inside)
         }
     }
 }
@@ -214,7 +208,6 @@ __global__ __launch_bounds__(256) void k_l1(Dims D, Ws W0, int par, size_t bstri
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int L2_THREADS = 512;
 constexpr int L2_RB = 32;             // pose rows per pass (two M-tiles)
-constexpr int L2_SMEM = (L2_THREADS / 64) * L2_RB * 16 * 4;
 template <int NC>
 __device__ __forceinline__ void l2_body(const Dims& D, const Ws& W, int par, int blk) {
     constexpr int KW = 8 * NC, NS = KW / 4;
@@ -296,11 +289,10 @@ template <int NC, bool X = false>
 __global__ __launch_bounds__(512) void k_head(Dims D, Ws W0, int par, size_t bstride) {
     // every kernel argument in the entry block, one wait (see k_bd)
     asm volatile("" :: "s"(W0.P), "s"(W0.P1), "s"(W0.h2[0]), "s"(W0.h2[1]), "s"(W0.pose_in), "s"(W0.head_save), "s"(W0.m2), "s"(W0.pts4), "s"(W0.pred4),
-                 "s"(W0.psl4), "s"(W0.ps4), "s"(W0.pbox), "s"(W0.sb), "s"(W0.cnt4), "s"(W0.state), "s"(W0.off), "s"(W0.sync), "s"(D.rot), "s"(D.K), "s"(D.H2), "s"(D.HA),
+                 "s"(W0.psl4), "s"(W0.ps4), "s"(W0.pbox), "s"(W0.sb), "s"(W0.cnt4), "s"(W0.state), "s"(W0.off), "s"(D.rot), "s"(D.K), "s"(D.H2), "s"(D.HA),
                  "s"(D.HB), "s"(D.OA), "s"(D.OB), "s"(D.NP), "s"(D.npb), "s"(D.ppl), "s"(D.nbp), "s"(D.oW3A), "s"(D.ob3A), "s"(D.oW3B), "s"(D.ob3B), "s"(par),
                  "s"(bstride));
     const Ws W = ws_shift(W0, blockIdx.z * bstride);
-    if (blockIdx.x == 0 && threadIdx.x == 0) W.sync[0] = 0;      // the fused backward launch of this epoch (k_gbd) counts its gradient blocks from zero
     const float* h2cur = par ? W.h2[1] : W.h2[0];
     const float* Pc = par ? W.P1 : W.P;
     __shared__ float outs[12];
@@ -804,27 +796,16 @@ __device__ __forceinline__ TrainState advance_state(const TrainState& S, float l
 }
 
 constexpr int GC_QMAX = 3;             // hidden units per thread of k_gradc's last phase: H2 <= 768 = 3 x 256
-// FUSED (the gradient role of k_gbd, 256 live threads of a 512-thread workgroup): what the other roles of the SAME launch consume --
-// g_out, g_h2, the three scalars of the advanced state -- goes out as 16-byte write-through (sc1) stores, and every block, also one
-// that leaves early (a stopped train), drains its stores and counts itself in W.sync[0] on its way out.
-__device__ __forceinline__ void gradc_arrive(const Ws& W) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this thread's write-through stores have been acknowledged ...
-    __syncthreads();                                       // ... every thread's
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(W.sync, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <bool FUSED>
 __device__ __forceinline__ void gradc_role(const Dims& D, const Ws& W, int epoch, int nbx, int nby, int k) {
     __shared__ float red[4][14];
     __shared__ float s_loss;
     __shared__ float s_go[16];
-    __shared__ __attribute__((aligned(16))) float s_gh[FUSED ? 256 * GC_QMAX : 4];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // ONE round trip for everything that does not depend on another load: the state (with the bias corrections of the
     // coming step), the cluster bounds, the hyper-parameters, the NN launch's loss partials, the pose row, and the
     // operands of the last phase (this thread's hidden units of pose row k and their output-layer weights) -- round 2
     // waited for the state first (the early exit of a stopped train) and then for the table entries it indexes
     const TrainState S = W.state[epoch & 1];
-    const int handoff_err = W.sync[3];                  // an in-launch hand-off of an earlier epoch timed out (the opt-in fused launches only): see below
     const int b0 = W.off[k], e0 = W.off[k + 1];
     const Hyper hy = *W.hyper;
     float a = tid < nbx ? W.lossp_x[tid] : 0.f, b = tid < nby ? W.lossp_y[tid] : 0.f;
@@ -853,14 +834,11 @@ __device__ __forceinline__ void gradc_role(const Dims& D, const Ws& W, int epoch
     for (int q = 0; q < GC_QMAX; ++q)
         asm volatile("" :: "v"(h2v[q]), "v"(w3v[q][0]), "v"(w3v[q][1]), "v"(w3v[q][2]), "v"(w3v[q][3]), "v"(w3v[q][4]), "v"(w3v[q][5]), "v"(w3v[q][6]),
                      "v"(w3v[q][7]));
-    if (S.stopped || handoff_err) {                     // (a failed hand-off stops the train and poisons what it returns: loud, not silently inconsistent)
+    if (S.stopped) {
         if (k == 0 && tid == 0) {
             TrainState E = S; E.stopped = 1;
-            if (handoff_err) { E.min_loss = NAN; W.result[0] = NAN; }
             W.state[(epoch + 1) & 1] = E;
-            if constexpr (FUSED) st4_wt((float*)W.sync, 32, make_float4(__int_as_float(1), 0.f, 0.f, 0.f));
         }
-        if constexpr (FUSED) gradc_arrive(W);
         return;
     }
     // second round trip: this thread's first point of the cluster (the loss reduction runs in its shadow)
@@ -898,12 +876,8 @@ __device__ __forceinline__ void gradc_role(const Dims& D, const Ws& W, int epoch
         W.loss_hist[S.epochs_run] = loss;
         W.lr_hist[S.epochs_run] = (float)S.lr;
         W.result[0] = N.min_loss; W.result[1] = (float)N.epochs_run; W.result[2] = (float)N.lr; W.result[3] = (float)N.best_epoch;
-        if constexpr (FUSED) st4_wt((float*)W.sync, 32, make_float4(__int_as_float(N.stopped), N.step_size, N.bc2_sqrt, 0.f));
     }
-    if (N.stopped) {                                    // the reference breaks before backward()
-        if constexpr (FUSED) gradc_arrive(W);
-        return;
-    }
+    if (N.stopped) return;                              // the reference breaks before backward()
     // ---- per-cluster reduction of the point gradients
     const float gx = 1.0f / (float)D.NP, gy = 1.0f / (float)D.NT;
     float acc[12];
@@ -960,16 +934,11 @@ __device__ __forceinline__ void gradc_role(const Dims& D, const Ws& W, int epoch
             dq_to_se3_vjp(sv, G, gt, gdq);
             for (int i = 0; i < 8; ++i) go[4 + i] = gdq[i];
         }
-        if constexpr (FUSED) {
-            for (int i = 0; i < 12; ++i) s_go[i] = go[i];
-            for (int i = 0; i < 3; ++i) st4_wt(W.g_out, 16 * k + 4 * i, make_float4(go[4 * i], go[4 * i + 1], go[4 * i + 2], go[4 * i + 3]));
-        } else {
-            for (int i = 0; i < 12; ++i) { W.g_out[16 * k + i] = go[i]; s_go[i] = go[i]; }
-        }
+        for (int i = 0; i < 12; ++i) { W.g_out[16 * k + i] = go[i]; s_go[i] = go[i]; }
     }
     __syncthreads();
     // ---- pose row k of dL/d(hidden pre-activation): g_h2[k][o] = act'(h2[k][o]) * sum_j g_out[k][j] W3[j][o]
-    // (a row needs only its own g_out, so it is final here: k_bwd2 and k_dw read the finished matrix)
+    // (a row needs only its own g_out, so it is final here: both roles of k_bd read the finished matrix)
 #pragma unroll
     for (int q = 0; q < GC_QMAX; ++q) {
         const int o = q * 256 + tid;
@@ -979,15 +948,8 @@ __device__ __forceinline__ void gradc_role(const Dims& D, const Ws& W, int epoch
             float sum = 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) if (j < nj) sum = fmaf(s_go[gofs + j], w3v[q][j], sum);
-            const float gh = sum * act_grad(h2v[q], D.slope);
-            if constexpr (FUSED) s_gh[o] = gh;           // the row leaves as 16-byte write-through stores below
-            else W.g_h2[(size_t)k * D.H2 + o] = gh;
+            W.g_h2[(size_t)k * D.H2 + o] = sum * act_grad(h2v[q], D.slope);
         }
-    }
-    if constexpr (FUSED) {
-        __syncthreads();
-        if (4 * tid < D.H2) st4_wt(W.g_h2, k * D.H2 + 4 * tid, *(const float4*)(s_gh + 4 * tid));
-        gradc_arrive(W);
     }
 }
 
@@ -995,13 +957,12 @@ __global__ __launch_bounds__(256) void k_gradc(Dims D, Ws W0, int epoch, int nbx
     // every kernel argument in the entry block, one wait (see k_bd)
     asm volatile("" :: "s"(W0.P), "s"(W0.P1), "s"(W0.h2[0]), "s"(W0.h2[1]), "s"(W0.head_save), "s"(W0.m2), "s"(W0.gm2), "s"(W0.pts4), "s"(W0.pred4),
                  "s"(W0.sgn_x), "s"(W0.cnt4), "s"(W0.lossp_x), "s"(W0.lossp_y), "s"(W0.g_out), "s"(W0.g_h2), "s"(W0.state), "s"(W0.bc1), "s"(W0.bc2s),
-                 "s"(W0.best_m), "s"(W0.best_pred), "s"(W0.loss_hist), "s"(W0.lr_hist), "s"(W0.result), "s"(W0.off), "s"(W0.hyper), "s"(W0.sync),
+                 "s"(W0.best_m), "s"(W0.best_pred), "s"(W0.loss_hist), "s"(W0.lr_hist), "s"(W0.result), "s"(W0.off), "s"(W0.hyper),
                  "s"(D.rot), "s"(D.K), "s"(D.H2), "s"(D.HA), "s"(D.HB), "s"(D.OA), "s"(D.OB), "s"(D.NP), "s"(D.NT), "s"(D.epochs), "s"(D.slope),
                  "s"(D.oW3A), "s"(D.oW3B), "s"(epoch), "s"(nbx), "s"(nby), "s"(bstride));
     const Ws W = ws_shift(W0, blockIdx.z * bstride);
-    gradc_role<false>(D, W, epoch, nbx, nby, blockIdx.x);
+    gradc_role(D, W, epoch, nbx, nby, blockIdx.x);
 }
-
 
 // ------------------------------------------------------------------------------------------ Adam
 __device__ __forceinline__ float adam_value(float p, float& mm, float& vv, float g, float step_size, float bc2_sqrt) {
@@ -1087,37 +1048,7 @@ __device__ __forceinline__ float row_sum16(float v) {
 // first FMA): every load is in flight at once and the MFMAs start on the first operands that land.  The per-wave partial tiles are
 // summed over the waves in wave order through LDS as before.  Then, unchanged: activation gradient, the 16 encoder rows' weight
 // gradients + Adam, and the NEXT epoch's encoder activation of the block's 16 units from the registers that hold the updated rows.
-// ---- fused backward launch (k_gbd): the consumers' side of the hand-off ----------------------------------------------------------
-// A consumer role first requests everything that does NOT depend on this epoch's gradients -- its parameter rows and Adam moments,
-// its slab of W2, the activations: 96-110 KB per workgroup, the part of k_bd that a CU's ~11 B/cycle intake makes slow -- then waits
-// here until the K blocks of the gradient role have counted themselves in, and only then asks for the gradients and the three
-// scalars of the advanced state (sc1 loads: the producers wrote them through with sc1 stores and nothing of this launch has touched
-// those lines before, MI355X_MICROARCH.md "valid forms").  One polling lane per workgroup; the poll is bounded (a few hundred
-// milliseconds): a launch whose producers never arrive -- which cannot happen while workgroups are dispatched in index order, the
-// gradient role owning the lowest indices -- ends as a stopped train instead of hanging the queue.
-struct GbdRecord { int stopped; float step_size, bc2_sqrt; int step; };
-__device__ __forceinline__ bool gbd_wait(const Ws& W, int K) {
-    __shared__ int s_ok;
-    if (threadIdx.x == 0) {
-        int it = 0, seen = __hip_atomic_load(W.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (seen < K && ++it < (1 << 19)) { __builtin_amdgcn_s_sleep(16); seen = __hip_atomic_load(W.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-        s_ok = seen >= K;
-        if (!s_ok) __hip_atomic_store(W.sync + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      //  a hand-off that timed out is an ERROR of the train:
-    }                                                                                                     //   k_gradc of the next epoch / k_params_home stop it and return NaN as its min_loss
-    __syncthreads();
-    return s_ok != 0;
-}
-__device__ __forceinline__ GbdRecord gbd_record(const Ws& W, bool ok) {
-    const u32x4v v = __builtin_amdgcn_raw_buffer_load_b128(buf_rsrc(W.sync, 64 * 4), 32 * 4, 0, 16);      // sc1
-    GbdRecord r;
-    r.stopped = ok ? (int)v[0] : 1; r.step_size = __uint_as_float(v[1]); r.bc2_sqrt = __uint_as_float(v[2]);
-    return r;
-}
-
-// L2IN (round 6): the D role of the SAME launch goes on to the next hidden activation (what k_l2 computed a launch later) and needs the next
-// encoder activation this role produces: the tile leaves as 16-byte write-through stores, the wave drains them, and the workgroup counts
-// itself in W.sync[1] -- a monotonic count of B-role arrivals since the train began (nB per optimizer step; k_prep / k_set_state set it).
-template <int KW, bool X, bool FUSED = false, bool L2IN = false>              // W2 rows per wave: H2 = 8 KW; X: more than 64 input features ('6d': 72) -- lanes i4 < 2 of a row take a second float4
+template <int KW, bool X>              // W2 rows per wave: H2 = 8 KW; X: more than 64 input features ('6d': 72) -- lanes i4 < 2 of a row take a second float4
 __device__ __forceinline__ void bwd2_role(const Dims& D, const Ws& W, int epoch, int blk, float* sh, unsigned long long bd_entry) {
     constexpr int NS = KW / 4;                 // k-steps of a wave
     constexpr bool V4 = KW % 16 == 0;          // A operand as 16-byte loads
@@ -1151,32 +1082,18 @@ __device__ __forceinline__ void bwd2_role(const Dims& D, const Ws& W, int epoch,
                                                  (__attribute__((address_space(3))) void*)(dst + i * B2_CB), 16, 0, 0);
     }
     const float* gbase = W.g_h2 + wv * KW + (V4 ? 4 * kk : kk);        // + row * H2 (+ 16 g | 4 s)
-    const __amdgpu_buffer_rsrc_t rGH = buf_rsrc(W.g_h2, D.KP * D.H2 * 4);
     auto load_a = [&](int row, float* dst) {                           // one tile's A operands of this lane: pose row `row` (clamped)
-        if constexpr (FUSED) {                                         // written by the gradient role of THIS launch: sc1 loads
-            const int off = (min(row, D.K - 1) * D.H2 + wv * KW + (V4 ? 4 * kk : kk)) * 4;
+        const float* g = gbase + (size_t)min(row, D.K - 1) * D.H2;
 #pragma unroll
-            for (int q = 0; q < NA; ++q) {
-                if constexpr (V4) {
-                    const u32x4v v = __builtin_amdgcn_raw_buffer_load_b128(rGH, off + 64 * q, 0, 16);
-                    dst[4 * q] = __uint_as_float(v[0]); dst[4 * q + 1] = __uint_as_float(v[1]); dst[4 * q + 2] = __uint_as_float(v[2]); dst[4 * q + 3] = __uint_as_float(v[3]);
-                } else dst[q] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rGH, off + 16 * q, 0, 16));
-            }
-        } else {
-            const float* g = gbase + (size_t)min(row, D.K - 1) * D.H2;
-#pragma unroll
-            for (int q = 0; q < NA; ++q) {
-                if constexpr (V4) { const float4 v = *(const float4*)(g + 16 * q); dst[4 * q] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w; }
-                else dst[q] = g[4 * q];
-            }
+        for (int q = 0; q < NA; ++q) {
+            if constexpr (V4) { const float4 v = *(const float4*)(g + 16 * q); dst[4 * q] = v.x; dst[4 * q + 1] = v.y; dst[4 * q + 2] = v.z; dst[4 * q + 3] = v.w; }
+            else dst[q] = g[4 * q];
         }
     };
     float a0[NS], a1[NS];
     const bool two0 = D.K > 16;                        // workgroup-uniform
-    if constexpr (!FUSED) {
-        load_a(lj, a0);
-        if (two0) load_a(16 + lj, a1);
-    }
+    load_a(lj, a0);
+    if (two0) load_a(16 + lj, a1);
     // encoder rows: thread = (half, row of the block, float4 of its IN inputs); both halves hold the row (same operands,
     // same Adam result) and share the pose rows of the next-activation loop
     const int half = tid >> 8, t2 = tid & 255, row = t2 >> 4, i4 = t2 & 15, hu = c0 + row;
@@ -1206,17 +1123,7 @@ __device__ __forceinline__ void bwd2_role(const Dims& D, const Ws& W, int epoch,
     __builtin_amdgcn_sched_barrier(0);                 // the loads above stay above
     // the state is requested LAST: hipcc makes `stopped` wave-uniform (v_readfirstlane) the moment it can, i.e. it waits for this load
     // right where it is issued -- at the top of the role that put a whole memory round trip in front of every other request
-    GbdRecord S;
-    if constexpr (FUSED) {
-        const bool ok = gbd_wait(W, D.K);              // everything above is in flight or has landed; now the gradients exist
-        load_a(lj, a0);
-        if (two0) load_a(16 + lj, a1);
-        __builtin_amdgcn_sched_barrier(0);
-        S = gbd_record(W, ok);
-    } else {
-        const TrainState St = W.state[(epoch + 1) & 1];
-        S.stopped = St.stopped; S.step_size = St.step_size; S.bc2_sqrt = St.bc2_sqrt;
-    }
+    const TrainState S = W.state[(epoch + 1) & 1];
     const bool live = !S.stopped;
     __builtin_amdgcn_sched_barrier(0);
     BD_T                                               // B1: everything requested
@@ -1309,17 +1216,7 @@ __device__ __forceinline__ void bwd2_role(const Dims& D, const Ws& W, int epoch,
         if (i4 == 0) xt[r * B2_CB + row] = act_f(v, D.slope);
     }
     __syncthreads();
-    if constexpr (L2IN) {
-        if (live) {                             // 64-byte row segments as four 16-byte write-through stores: the D role reads them in this launch
-            for (int t = tid; t < D.K * (B2_CB / 4); t += B2_THREADS) {
-                const int r = t >> 2, c4 = 4 * (t & 3);
-                st4_wt(x1next, r * D.H + c0 + c4, *(const float4*)(xt + r * B2_CB + c4));
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this thread's write-through stores have been acknowledged ...
-            __syncthreads();                                       // ... every thread's
-            if (tid == 0) __hip_atomic_fetch_add(W.sync + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    } else if (live)                            // the tile goes out as 64-byte row segments, 8 bytes per lane
+    if (live)                                   // the tile goes out as 64-byte row segments, 8 bytes per lane
         for (int t = tid; t < D.K * (B2_CB / 2); t += B2_THREADS) {
             const int r = t >> 3, c2 = 2 * (t & 7);
             *(nn_f2*)(x1next + (size_t)r * D.H + c0 + c2) = nn_f2{xt[r * B2_CB + c2], xt[r * B2_CB + c2 + 1]};
@@ -1346,8 +1243,7 @@ constexpr int DW_TILES = 4;           // 16-input tiles per wave: 8 waves x 64 i
 constexpr int DW_KC = 5;              // k-steps (4 pose rows each) per chunk of operand loads: K = 20 is one chunk
 __host__ __device__ inline int dw_blocks(const Dims& D) { return D.H2 / DW_UNITS + 2; }
 
-template <bool FUSED = false, bool L2IN = false>
-__device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, int blk, unsigned long long bd_entry, float* sh = nullptr) {
+__device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, int blk, unsigned long long bd_entry) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, lj = lane & 15, q = lane >> 4;
     __builtin_amdgcn_s_waitcnt(0x0F70);             // vmcnt(0): see bwd2_role
     const int par = epoch & 1;
@@ -1366,10 +1262,7 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
     else if (blk == nb2) { u0 = 0; nu = D.OA; n_in = D.HA; oW = D.oW3A; ob = D.ob3A; amat = h2cur; astride = D.H2; gmat = W.g_out; gstride = 16; }
     else { u0 = 0; nu = D.OB; n_in = D.HB; oW = D.oW3B; ob = D.ob3B; amat = h2cur + D.HA; astride = D.H2; gmat = W.g_out + 4; gstride = 16; }
     if (nu == 0) return;                            // no decoder_1 ('dq'): block-uniform
-    if (64 * wv >= n_in) {                          // a wave past the row's width (wave-uniform)
-        if constexpr (FUSED) (void)gbd_wait(W, D.K);        // (it still owes the workgroup's barrier inside the wait)
-        return;
-    }
+    if (64 * wv >= n_in) return;                    // a wave past the row's width (wave-uniform)
     BD_T0
     const int unit = min(lj, nu - 1);               // lanes past the live units mirror the last one and store nothing
     const bool ulive = lj < nu;
@@ -1403,21 +1296,12 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
     const int aoff = (q * astride + i0 + 16 * (lj & 3) + 4 * (lj >> 2)) * 4, goff = (q * gstride + unit) * 4;
     float bop[DW_KC];
     float4 aop[DW_KC];
-    auto load_b = [&](int s0) {                     // the gradients (FUSED: written by the gradient role of THIS launch -- sc1 loads)
-#pragma unroll
-        for (int s = 0; s < DW_KC; ++s)
-            bop[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rG, goff, 4 * (s0 + s) * gstride * 4, FUSED ? 16 : 0));
-    };
-    auto load_a = [&](int s0) {                     // the activations
-#pragma unroll
-        for (int s = 0; s < DW_KC; ++s) aop[s] = ld_buf4(rA, aoff, 4 * (s0 + s) * astride * 4);   // (inputs past the row's width read the next row or 0: their gradients are not used)
-    };
     auto load_ops = [&](int s0) {
 #pragma unroll
         for (int s = 0; s < DW_KC; ++s) {
             const int r4 = 4 * (s0 + s);             // scalar: rows r4 + q
-            bop[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rG, goff, r4 * gstride * 4, FUSED ? 16 : 0));
-            aop[s] = ld_buf4(rA, aoff, r4 * astride * 4);
+            bop[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rG, goff, r4 * gstride * 4, 0));
+            aop[s] = ld_buf4(rA, aoff, r4 * astride * 4);   // (inputs past the row's width read the next row or 0: their gradients are not used)
         }
     };
     auto mfma_ops = [&]() {
@@ -1431,13 +1315,9 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
 #pragma unroll
         for (int s = 0; s < DW_KC; ++s) gb += bop[s];
     };
-    GbdRecord S;
-    if constexpr (FUSED) load_a(0); else load_ops(0);
+    load_ops(0);
     __builtin_amdgcn_sched_barrier(0);              // (the scheduler otherwise interleaves requests with the MFMAs and their waits)
-    if constexpr (!FUSED) {
-        const TrainState St = W.state[(epoch + 1) & 1];
-        S.stopped = St.stopped; S.step_size = St.step_size; S.bc2_sqrt = St.bc2_sqrt; S.step = St.step;
-    }
+    const TrainState S = W.state[(epoch + 1) & 1];
     float pb = Pc[ob + unit], mb = W.AM[ob + unit], vb = W.AV[ob + unit];
     __builtin_amdgcn_sched_barrier(0);
     float4 pw[DW_TILES], pm[DW_TILES], pv[DW_TILES];
@@ -1446,13 +1326,6 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
     for (int v = 0; v < DW_TILES; ++v) {
         vl[v] = ulive && i0 + 16 * v + 4 * q < n_in;                 // (HA = 32 at hidden 64: half a wave's inputs exist)
         pw[v] = ld_buf4(rP, po + 64 * v, 0); pm[v] = ld_buf4(rM, po + 64 * v, 0); pv[v] = ld_buf4(rV, po + 64 * v, 0);      // (past the arrays: 0)
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (FUSED) {
-        const bool ok = gbd_wait(W, D.K);           // the parameter rows and the activations are here; now the gradients exist
-        load_b(0);
-        __builtin_amdgcn_sched_barrier(0);
-        S = gbd_record(W, ok);
         __builtin_amdgcn_sched_barrier(0);
     }
     BD_T                                            // D1: everything requested
@@ -1472,7 +1345,6 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
         nw.z = adam_value(pw[v].z, pm[v].z, pv[v].z, acc[2][v], S.step_size, S.bc2_sqrt);
         nw.w = adam_value(pw[v].w, pm[v].w, pv[v].w, acc[3][v], S.step_size, S.bc2_sqrt);
         if (vl[v]) { const int e = po / 4 + 16 * v; st4_wt(Pn, e, nw); st4_wt(W.AM, e, pm[v]); st4_wt(W.AV, e, pv[v]); }
-        if constexpr (L2IN) pw[v] = nw;             // the updated rows stay in registers: the B operands of the next hidden activation below
     }
     if (wv == 0) {                                  // the units' biases: gradient = sum over the pose rows of g[r][u], the four lane groups q in order
         float sum = gb;
@@ -1480,64 +1352,6 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
         sum += __shfl_xor(sum, 32, 64);             // ((0,1), (2,3))
         pb = adam_value(pb, mb, vb, sum, S.step_size, S.bc2_sqrt);
         if (q == 0 && ulive) { Pn[ob + unit] = pb; W.AM[ob + unit] = mb; W.AV[ob + unit] = vb; }
-    }
-    if constexpr (L2IN) {
-        // ---- the NEXT hidden activation of this block's 16 units, h2' = act(x1' . W2'^T + b2'), inside the backward launch (round 6): what k_l2
-        // computed a launch later -- from the updated rows this wave still holds (the very B operands k_l2 loaded back: lane (q, unit) holds
-        // inputs i0 + 16 v + 4 q + t as component t of float4 v, k_l2's k order) and the next encoder activation x1' of the B role of THIS launch
-        // (write-through stores there, sc1 loads here, one counter in between).  Same tiles, same k order, same cross-wave sum in wave order:
-        // bit for bit k_l2's result.  Only the hidden blocks take part (the output rows' blocks have left), all eight waves of them (H = 512).
-        if (blk < nb2) {                            // block-uniform
-            float* red = sh;                        // [8 waves][32 rows][16 units] partial tiles, then the 16 new biases
-            float* sbias = red + (BD_THREADS / 64) * L2_RB * 16;
-            if (wv == 0 && q == 0) sbias[lj] = pb;
-            const int nB = D.H / B2_CB;
-            if (threadIdx.x == 0) {                 // the B role's workgroups of this problem have counted themselves in: nB per optimizer step
-                int it = 0;
-                const int want = nB * S.step;
-                while (__hip_atomic_load(W.sync + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want && ++it < (1 << 20)) __builtin_amdgcn_s_sleep(2);
-                if (it >= (1 << 20)) __hip_atomic_store(W.sync + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (cannot happen while workgroups are dispatched in index order: see gbd_wait)
-            }
-            __syncthreads();
-            const float* x1n = par ? W.x1[0] : W.x1[1];
-            float* h2n = par ? W.h2[0] : W.h2[1];
-            const __amdgpu_buffer_rsrc_t rX = buf_rsrc(x1n, D.KP * D.H * 4);
-            const int tid = threadIdx.x;
-            for (int r0 = 0; r0 < D.K; r0 += L2_RB) {
-                const int nr = min(L2_RB, D.K - r0);
-                const bool two = nr > 16;           // block-uniform
-                u32x4v xa[DW_TILES], xb[DW_TILES];
-                const int o0 = (min(r0 + lj, D.K - 1) * D.H + i0 + 4 * q) * 4, o1 = (min(r0 + 16 + lj, D.K - 1) * D.H + i0 + 4 * q) * 4;
-#pragma unroll
-                for (int v = 0; v < DW_TILES; ++v) {
-                    xa[v] = __builtin_amdgcn_raw_buffer_load_b128(rX, o0 + 64 * v, 0, 16);      // sc1: written through by the B role of this launch
-                    if (two) xb[v] = __builtin_amdgcn_raw_buffer_load_b128(rX, o1 + 64 * v, 0, 16);
-                }
-                f32x4 c0v = {0.f, 0.f, 0.f, 0.f}, c1v = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int v = 0; v < DW_TILES; ++v) {
-                    const float bq[4] = {pw[v].x, pw[v].y, pw[v].z, pw[v].w};
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        c0v = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xa[v][t]), bq[t], c0v, 0, 0, 0);
-                        if (two) c1v = __builtin_amdgcn_mfma_f32_16x16x4f32(__uint_as_float(xb[v][t]), bq[t], c1v, 0, 0, 0);
-                    }
-                }
-                if (r0) __syncthreads();            // the previous pass has read red
-                {
-                    float* o = red + (wv * L2_RB + 4 * q) * 16 + lj;
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) { o[v * 16] = c0v[v]; if (two) o[(16 + v) * 16] = c1v[v]; }
-                }
-                __syncthreads();
-                if (tid < nr * 16) {
-                    float sum = red[tid];
-#pragma unroll
-                    for (int w2 = 1; w2 < BD_THREADS / 64; ++w2) sum += red[w2 * L2_RB * 16 + tid];
-                    h2n[(size_t)(r0 + (tid >> 4)) * D.H2 + u0 + (tid & 15)] = act_f(sum + sbias[tid & 15], D.slope);
-                }
-            }
-        }
     }
     BD_TEND(1, epoch);                              // D3: Adam, the write-through stores acknowledged
 }
@@ -1551,7 +1365,7 @@ __device__ __forceinline__ void dw_role(const Dims& D, const Ws& W, int epoch, i
 // side the launch takes what the longer role takes, and the next hidden activation, the one thing that needs BOTH results (the
 // next encoder activation from B, the updated hidden rows from D), is k_l2 again, a launch boundary later.
 // grid.x = (H / 16 + H2 / 8 + 1) * problems: the B blocks of ALL problems first (the longer chain of dependent phases).
-template <int NC, int KW, bool X = false, bool L2IN = false>
+template <int NC, int KW, bool X = false>
 __global__ __launch_bounds__(BD_THREADS, 4) void k_bd(Dims D, Ws W0, int epoch, size_t bstride, int nz) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
 #ifdef CREG_BD_STAMPS
@@ -1577,43 +1391,8 @@ __global__ __launch_bounds__(BD_THREADS, 4) void k_bd(Dims D, Ws W0, int epoch, 
 #ifdef CREG_BD_ONLY                                   // measurement build: one role alone (1: backward to the encoder, 2: dW + Adam)
     if ((CREG_BD_ONLY == 1) != roleB) return;
 #endif
-    if (roleB) bwd2_role<KW, X, false, L2IN>(D, W, epoch, blk, (float*)smem, bd_entry);
-    else dw_role<false, L2IN>(D, W, epoch, blk, bd_entry, (float*)smem);
-}
-
-// ------------------------------------------------------------------------------------------ the fused backward launch: k_gbd (round 5)
-// k_gradc and k_bd as ONE launch: grid.x = (K + H / 16 + H2 / 16 + 2) * problems, the gradient role's blocks first.  What the
-// boundary between the two launches serialised is not the arithmetic but the INTAKE: a B block pulls 110 KB and a D block 96 KB
-// through a CU that takes ~11 bytes per cycle, and all but the few KB of gradients of it -- parameter rows, Adam moments, W2 slab,
-// activations -- is known before k_gradc has started.  Here the consumers request all of that at once, then wait for the K gradient
-// blocks (gbd_wait), then fetch the gradients.  One hand-off (gradient role -> {B, D} side by side), write-through stores on one side,
-// sc1 loads on the other, no fence; bit-identical to the two launches (same arithmetic in the same order).
-template <int NC, int KW, bool X = false>
-__global__ __launch_bounds__(BD_THREADS, 4) void k_gbd(Dims D, Ws W0, int epoch, int nbx, int nby, size_t bstride, int nz) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    asm volatile("" :: "s"(W0.P), "s"(W0.P1), "s"(W0.AM), "s"(W0.AV), "s"(W0.enc), "s"(W0.x1[0]), "s"(W0.x1[1]), "s"(W0.h2[0]), "s"(W0.h2[1]),
-                 "s"(W0.g_out), "s"(W0.g_h2), "s"(W0.state), "s"(W0.sync), "s"(D.K), "s"(D.KP), "s"(D.IN), "s"(D.H), "s"(D.H2), "s"(D.HA), "s"(D.HB), "s"(D.OA),
-                 "s"(D.OB), "s"(D.oW1), "s"(D.ob1), "s"(D.oW2), "s"(D.ob2), "s"(D.oW3A), "s"(D.ob3A), "s"(D.oW3B), "s"(D.ob3B), "s"(D.NPAR),
-                 "s"(D.slope), "s"(epoch), "s"(bstride), "s"(nz));
-    asm volatile("" :: "s"(W0.head_save), "s"(W0.m2), "s"(W0.gm2), "s"(W0.pts4), "s"(W0.pred4), "s"(W0.sgn_x), "s"(W0.cnt4), "s"(W0.lossp_x), "s"(W0.lossp_y),
-                 "s"(W0.bc1), "s"(W0.bc2s), "s"(W0.best_m), "s"(W0.best_pred), "s"(W0.loss_hist), "s"(W0.lr_hist), "s"(W0.result), "s"(W0.off), "s"(W0.hyper),
-                 "s"(D.rot), "s"(D.NP), "s"(D.NT), "s"(D.epochs), "s"(nbx), "s"(nby));
-    const int nG = D.K, nB = D.H / B2_CB, nD = dw_blocks(D);
-    int i = blockIdx.x;
-    if (i < nG * nz) {
-        if (threadIdx.x >= 256) return;             // the gradient role is a 256-thread role
-        const int z = i / nG;
-        const Ws W = ws_shift(W0, (size_t)z * bstride);
-        gradc_role<true>(D, W, epoch, nbx, nby, i - z * nG);
-        return;
-    }
-    i -= nG * nz;
-    const bool roleB = i < nB * nz;
-    if (!roleB) i -= nB * nz;
-    const int n = roleB ? nB : nD, z = i / n, blk = i - z * n;
-    const Ws W = ws_shift(W0, (size_t)z * bstride);
-    if (roleB) bwd2_role<KW, X, true>(D, W, epoch, blk, (float*)smem, 0ull);
-    else dw_role<true>(D, W, epoch, blk, 0ull);
+    if (roleB) bwd2_role<KW, X>(D, W, epoch, blk, (float*)smem, bd_entry);
+    else dw_role(D, W, epoch, blk, bd_entry);
 }
 
 // after the last epoch: the parameters of an odd number of optimizer steps sit in the second buffer; the copy-out reads the first
@@ -1635,7 +1414,6 @@ __global__ void k_set_state(Dims D, Ws W, ResumeState rs) {
     s.min_loss = rs.min_loss; s.epochs_run = rs.epochs_run; s.best_epoch = rs.best_epoch;
     s.next_bc1 = W.bc1[min(rs.step + 1, D.epochs)]; s.next_bc2s = W.bc2s[min(rs.step + 1, D.epochs)];       // (k_prep, the launch before, filled the tables)
     W.state[0] = s; W.state[1] = s;
-    W.sync[1] = (D.H / B2_CB) * rs.step;          // (k_bd with the next hidden activation inside: B-role arrivals so far = nB per optimizer step)
     W.result[0] = s.min_loss; W.result[1] = (float)s.epochs_run; W.result[2] = (float)s.lr; W.result[3] = (float)s.best_epoch;
 }
 __global__ void k_get_state(Ws W, int sidx, double* out) {
@@ -1659,8 +1437,6 @@ struct Plan {
     int nz;                   // problems per launch right now (grid.z): B for run, 1 for probe / profile
     size_t bstride;           // bytes between consecutive problems' workspaces
     int smem_bd;
-    bool fused;               // gradient reduction + backward as ONE launch (k_gbd)
-    bool l2in;                // the next hidden activation inside the backward launch (k_bd<.., true>): no k_l2 launch per epoch
     int branches;             // parallel chains in the captured graph (groups of problems)
     // chain-stream mode (creg_train_shape.graph_branches < 0): every chain is its OWN linear graph on its OWN stream, forked from /
     // joined to the caller's stream once per train by events -- the chains' hardware queues are then the streams', not what the
@@ -1751,7 +1527,6 @@ static size_t carve(const Dims& D, char* base, Ws* W) {
     w.best_m = (float*)take(f * 16 * D.K); w.best_pred = (float*)take(f * 3 * D.NP);
     w.loss_hist = (float*)take(f * D.epochs); w.lr_hist = (float*)take(f * D.epochs); w.result = (float*)take(f * 4);
     w.off = (int*)take(sizeof(int) * (D.K + 1)); w.hyper = (Hyper*)take(sizeof(Hyper));
-    w.sync = (int*)take(sizeof(int) * 64);
     w.ysum = (unsigned long long*)take(sizeof(unsigned long long) * 4);
     if (W) *W = w;
     return o;
@@ -1791,26 +1566,7 @@ static void by_bd(const Dims& D, F f) {
 static void launch_bd(Plan* P, int epoch, hipStream_t s) {
     const Dims& D = P->D; const Ws& W = P->W;
     const int per = D.H / B2_CB + dw_blocks(D);
-    if (P->l2in) {                                   // (hidden 512, 'q' / 'rpy' / 'dq' widths: see creg_train_plan_create)
-        if (D.HA) hipLaunchKernelGGL((k_bd<8, 96, false, true>), dim3(per * P->nz), dim3(BD_THREADS), P->smem_bd, s, D, W, epoch, P->bstride, P->nz);
-        else hipLaunchKernelGGL((k_bd<8, 64, false, true>), dim3(per * P->nz), dim3(BD_THREADS), P->smem_bd, s, D, W, epoch, P->bstride, P->nz);
-        return;
-    }
     by_bd(D, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(per * P->nz), dim3(BD_THREADS), P->smem_bd, s, D, W, epoch, P->bstride, P->nz); });
-}
-template <typename F>
-static void by_gbd(const Dims& D, F f) {
-    by_nc(D.H, [&](auto nc) {
-        constexpr int NC = decltype(nc)::value;
-        if (D.IN > 64) f(k_gbd<NC, 12 * NC, true>);
-        else if (D.HA) f(k_gbd<NC, 12 * NC>);
-        else f(k_gbd<NC, 8 * NC>);
-    });
-}
-static void launch_gbd(Plan* P, int epoch, hipStream_t s) {
-    const Dims& D = P->D; const Ws& W = P->W;
-    const int per = D.K + D.H / B2_CB + dw_blocks(D);
-    by_gbd(D, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(per * P->nz), dim3(BD_THREADS), P->smem_bd, s, D, W, epoch, D.nbx, D.nby, P->bstride, P->nz); });
 }
 static void launch_nn(const Dims& D, const Ws& W, size_t bstride, int nz, hipStream_t s, int par = 0) {
     const EngineEpi epi{W.sgn_x, W.cnt4, W.lossp_x, W.lossp_y, bstride, &W.state[par].stopped};
@@ -1874,7 +1630,7 @@ static void launch_nn(const Dims& D, const Ws& W, size_t bstride, int nz, hipStr
 constexpr int NKERN = 5;
 // `ev` (optional): NKERN + 1 events recorded before kernel 0 and after each kernel.
 // Entering epoch e, x1[e & 1] and h2[e & 1] hold the activations of the current parameters (k_l1 / k_l2 for epoch 0,
-// k_bwd2 / k_dw of the previous epoch afterwards).
+// k_bd's B role / k_l2 of the previous epoch afterwards).
 static void enqueue_epoch(Plan* P, int epoch, hipStream_t s, hipEvent_t* ev = nullptr) {
     const Dims& D = P->D; const Ws& W = P->W;
     const int par = epoch & 1;
@@ -1882,13 +1638,9 @@ static void enqueue_epoch(Plan* P, int epoch, hipStream_t s, hipEvent_t* ev = nu
     mark(0);
     launch_head(P, par, s); mark(1);
     launch_nn(D, W, P->bstride, P->nz, s, par); mark(2);
-    if (P->fused) { launch_gbd(P, epoch, s); mark(3); mark(4); }
-    else {
-        hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, P->nz), dim3(256), 0, s, D, W, epoch, D.nbx, D.nby, P->bstride); mark(3);
-        launch_bd(P, epoch, s); mark(4);
-    }
-    if (!P->l2in) launch_l2(P, par ^ 1, s);   // the next epoch's hidden activation: next encoder activation (B) x updated hidden rows (D)
-    mark(5);                                  //   (l2in: computed at the end of k_bd's D role)
+    hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, P->nz), dim3(256), 0, s, D, W, epoch, D.nbx, D.nby, P->bstride); mark(3);
+    launch_bd(P, epoch, s); mark(4);
+    launch_l2(P, par ^ 1, s); mark(5);        // the next epoch's hidden activation: next encoder activation (B) x updated hidden rows (D)
 }
 
 // One launch copies up to 16 (source, destination, dword count) ranges: a problem's 10 parameter tensors + offsets in,
@@ -1966,7 +1718,7 @@ static int stage_inputs(Plan* P, const creg_train_args* args, int n, hipStream_t
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(k_prep, dim3(blocks, 1, n), dim3(256), 0, s, D, P->W, P->bstride, pb);
     hipLaunchKernelGGL(k_l1, dim3(cdiv(D.H, 4), 1, n), dim3(256), 0, s, D, P->W, 0, P->bstride);
-    {   // the first epoch's hidden activation (later ones come out of k_dw)
+    {   // the first epoch's hidden activation (later ones: the k_l2 launch that ends every epoch)
         const int nz_keep = P->nz;
         P->nz = n;
         launch_l2(P, 0, s);
@@ -2204,26 +1956,6 @@ extern "C" int creg_train_plan_create(const creg_train_shape* shape, void* works
         hipError_t e2 = hipSuccess;
         by_bd(D, [&](auto kern) { e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
         CREG_REQUIRE(e2 == hipSuccess, "creg_train_plan_create: cannot raise the dynamic LDS limit of k_bd");
-        // the fused launch carries the gradient role's static LDS (4 KB) beside the B role's dynamic block
-        const char* fe = getenv("CREG_FUSED_GBD");
-        // Measured (profiles/r05_fused_gbd_ab.log): bit-identical, and SLOWER -- 174 against 181.5 frames/s at five sequences, 48.5
-        // against 48.8 at one, franka 77.2 against 80.9: what the consumers do AFTER the gradients exist (B: a 61 KB read of g_h2, the
-        // MFMAs, the cross-wave sum, dW1, Adam, the next activation: ~7 us of dependent phases) is the critical path, not the intake
-        // the prefetch hides, and the hand-off costs what the boundary did.  Off unless CREG_FUSED_GBD=1 (kept as a tested experiment).
-        P->fused = (fe ? fe[0] == '1' : false) && P->smem_bd + 4608 <= 160 * 1024;
-        // Round 6: the next hidden activation inside the backward launch (no k_l2 launch per epoch).  Hidden 512 without the '6d' input width;
-        // CREG_L2_IN_BD=0 / 1 overrides (A/B).  Not together with the fused gradient launch.
-        const char* le = getenv("CREG_L2_IN_BD");
-        P->l2in = !P->fused && D.H == 512 && D.IN <= 64 && (le ? le[0] == '1' : CREG_L2_IN_BD_DEFAULT);
-        if (P->l2in) {
-            if (D.HA) e2 = hipFuncSetAttribute((const void*)k_bd<8, 96, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            else e2 = hipFuncSetAttribute((const void*)k_bd<8, 64, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e2 != hipSuccess) { (void)hipGetLastError(); P->l2in = false; }
-        }
-        if (P->fused) {
-            by_gbd(D, [&](auto kern) { e2 = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4608); });
-            if (e2 != hipSuccess) { (void)hipGetLastError(); P->fused = false; }
-        }
     }
     // the limit is per kernel, not per plan: always raise it to the largest any plan can ask for (16384 keys + boxes),
     // so that a small plan created later does not lower it under a large one
@@ -2549,275 +2281,6 @@ extern "C" long long creg_debug_nn_waves(unsigned long long* out, long long cap,
 }
 #endif
 
-#ifdef CREG_XCD_PROBE
-// ---- Stage 1 of the XCD-resident train: a MEASUREMENT build (python -m autourdf_amd.build --variant xcd with
-// CREG_EXTRA_FLAGS=-DCREG_XCD_PROBE; tests/measure/xcd_stage1.py).  Two questions, two kernels:
-//   (a) what does a barrier among the workgroups of ONE XCD cost, a 4 KB hand-off included (every member writes its share with plain
-//       stores, everybody reads all of it)?  Members find each other at run time: a workgroup reads HW_REG_XCC_ID and takes a ticket
-//       from its XCD's counter -- nothing assumes blockIdx % 8.
-//   (b) what does the plan's nearest-neighbour launch cost when ONE problem's blocks are confined to ONE XCD's 32 CUs (problem =
-//       XCC_ID, the blocks handed out by a per-XCD queue)?
-namespace creg {
-__device__ __forceinline__ int xcc_id() { return (int)(__builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20) & 7u); }      // HW_REG_XCC_ID[3:0]
-__device__ __forceinline__ int ld_sc1(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// ctl: 128-byte lines of ints.  line x (0..7): XCD x's arrival counter; line 8 + x: its member count; line 16: all members counted.
-// MODE 0 "XCD-local": plain payload stores, vmcnt(0), an atomic that STAYS in the XCD's L2 (workgroup scope: no sc1), sc1 polls and
-//   sc1 payload loads (L2-served: the vector L1 of the reading CU is bypassed) -- sound only because every member IS on this XCD.
-// MODE 1 the placement-independent recipe: plain stores, agent release, agent counter; relaxed poll, agent acquire, plain loads.
-// MODE 2 write-through: sc1 payload stores, vmcnt(0), agent counter; sc1 polls and loads.
-template <int MODE>
-__global__ __launch_bounds__(256) void k_xcd_barrier(int* ctl, float* payload, int rounds, int skew, unsigned long long* ticks, int* errs) {
-    __shared__ int s_t, s_n;
-    const int tid = threadIdx.x;
-    const int x = xcc_id();
-    if (tid == 0) {
-        s_t = __hip_atomic_fetch_add(ctl + 32 * (8 + x), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(ctl + 32 * 16, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int it = 0;
-        while (ld_sc1(ctl + 32 * 16) < (int)gridDim.x && ++it < (1 << 22)) __builtin_amdgcn_s_sleep(8);
-        s_n = it < (1 << 22) ? ld_sc1(ctl + 32 * (8 + x)) : 0;
-    }
-    __syncthreads();
-    const int t = s_t, n = s_n;
-    if (n == 0) { if (tid == 0) { ticks[blockIdx.x] = ~0ull; atomicAdd(errs, 1 << 20); } return; }      // not co-resident: no barrier possible
-    const int per = 1024 / n, lo = t * per, hi = t == n - 1 ? 1024 : lo + per;      // this member's floats of the 4 KB
-    int bad = 0;
-    const unsigned long long t0 = wall_clock64();
-    for (int r = 0; r < rounds; ++r) {
-        float* buf = payload + (size_t)(2 * x + (r & 1)) * 1024;
-        if (skew && (t & 3) == 1) for (int i = 0; i < skew; ++i) __builtin_amdgcn_s_sleep(32);      // uneven arrival
-        for (int i = lo + tid; i < hi; i += 256) {
-            const float v = (float)(r * 4096 + i + 1);
-            if (MODE == 2) __hip_atomic_store(buf + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            else buf[i] = v;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            if (MODE == 1) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-            if (MODE == 0) __hip_atomic_fetch_add(ctl + 32 * x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            else __hip_atomic_fetch_add(ctl + 32 * x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int it = 0;
-            while (ld_sc1(ctl + 32 * x) < n * (r + 1) && ++it < (1 << 22)) __builtin_amdgcn_s_sleep(1);
-            if (it >= (1 << 22)) atomicAdd(errs, 1 << 20);
-            if (MODE == 1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        __syncthreads();
-        float4 v;
-        if (MODE == 1) v = ((const float4*)buf)[tid];
-        else { const u32x4v w = __builtin_amdgcn_raw_buffer_load_b128(buf_rsrc(buf, 4096), 16 * tid, 0, 16); v = make_float4(__uint_as_float(w[0]), __uint_as_float(w[1]), __uint_as_float(w[2]), __uint_as_float(w[3])); }
-        const float e = (float)(r * 4096 + 4 * tid + 1);
-        bad += (v.x != e) + (v.y != e + 1.f) + (v.z != e + 2.f) + (v.w != e + 3.f);
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned long long t1 = wall_clock64();
-    if (tid == 0) ticks[blockIdx.x] = ((t1 - t0) << 8) | (unsigned)(x << 5) | (unsigned)min(n - 1, 31);
-    if (bad) atomicAdd(errs, bad);
-}
-
-// (b) ctl: line x of half `par`: XCD x's block queue head; line 8 + x: members seen (statistics).  The other half is zeroed for the
-// next launch.  WSCOPE: the queue atomics stay in the XCD's L2.
-template <bool ROWS, int NBT, int NBP, bool WSCOPE>
-__global__ __launch_bounds__(NN_BLOCK) void k_nn_xcd(const float* A, int na, const float* B, int nb, int blocksA, int blocksB, EngineEpi epi, NnBlocks yb,
-                                                     NnBlocks pb, size_t zstride, int nz, int* ctl, int par) {
-    __shared__ int s_bx;
-    const int x = xcc_id();
-    int* mine = ctl + 32 * (16 * par + x);
-    if (threadIdx.x == 0) {
-        ctl[32 * (16 * (par ^ 1) + x)] = 0;
-        ctl[32 * (16 * (par ^ 1) + 8 + x)] = 0;
-        __hip_atomic_fetch_add(mine + 32 * 8, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    if (x >= nz) return;
-    const size_t zb = x * zstride;
-    A = (const float*)((const char*)A + zb);
-    B = (const float*)((const char*)B + zb);
-    yb.ts4 = (const float4*)((const char*)yb.ts4 + zb);
-    yb.tbox = (const float*)((const char*)yb.tbox + zb);
-    pb.ts4 = (const float4*)((const char*)pb.ts4 + zb);
-    pb.tbox = (const float*)((const char*)pb.tbox + zb);
-    pb.nblk_dev = (const int*)((const char*)pb.nblk_dev + zb);
-    epi.shift(x);
-    for (;;) {
-        __syncthreads();                                   // the previous block's LDS partials have been read
-        if (threadIdx.x == 0)
-            s_bx = WSCOPE ? __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-                          : __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int bx = s_bx;
-        if (bx >= blocksA + blocksB) return;
-        if constexpr (ROWS) {
-            if (bx < blocksA) nn_l1_rows<NBT, EngineEpi, false, true>(pb.ts4, 0, pb.nblk_dev, pb.nblk, yb, 0, epi, bx, epi.stopped, B, epi.lossp_x);
-            else nn_l1_rows<NBP, EngineEpi, true, false>(yb.ts4, yb.nblk, nullptr, yb.nblk, pb, 1, epi, bx - blocksA, epi.stopped, A, epi.lossp_y);
-        } else {
-            if (bx < blocksA) nn_l1_block_pruned<NBT, 1, EngineEpi, true, false>(A, na, 4, yb, 0, epi, bx, epi.stopped, B, 4);
-            else nn_l1_block_pruned<NBP, 1, EngineEpi, true, true>(B, nb, 4, pb, 1, epi, bx - blocksA, epi.stopped, A, 4);
-        }
-    }
-}
-// Stage 2 pre-check: the hidden-layer launch (k_l2) with one problem's H2 / 16 workgroups confined to ONE XCD (problem = XCC_ID, blocks from the
-// per-XCD queue) -- what the W2 slabs (1.5 MB per problem, written through by k_bd a launch earlier) cost through one XCD's fabric port.
-template <int NC>
-__global__ __launch_bounds__(L2_THREADS) void k_l2_xcd(Dims D, Ws W0, int par, size_t bstride, int nz, int* ctl, int cpar) {
-    __shared__ int s_bx;
-    const int x = xcc_id();
-    int* mine = ctl + 32 * (16 * cpar + x);
-    if (threadIdx.x == 0) ctl[32 * (16 * (cpar ^ 1) + x)] = 0;
-    if (x >= nz) return;
-    const Ws W = ws_shift(W0, x * bstride);
-    for (;;) {
-        __syncthreads();
-        if (threadIdx.x == 0) s_bx = __hip_atomic_fetch_add(mine, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __syncthreads();
-        const int bx = s_bx;
-        if (bx >= D.H2 / 16) return;
-        l2_body<NC>(D, W, par, bx);
-    }
-}
-}  // namespace creg
-
-// out (HOST, 64 doubles):
-//  [0..2]  barrier + 4 KB hand-off per round (us, slowest member), 256 workgroups on an idle chip: MODE 0 / 1 / 2;   [3..5] the same with uneven arrival
-//  [6..8]  payload words that arrived wrong, per MODE (both runs);   [9] members of the smallest XCD group, [10] of the largest
-//  [16] the plan's NN launch, one problem on the whole chip (us, 200 back to back)   [17] the same with `nz` problems in grid.z
-//  [18] XCD-confined, nz problems, agent-scope queue   [19] workgroup-scope queue   [20] 1 problem confined   [21] outputs identical to the plan's launch (1 / 0)
-//  [22] workgroups per XCD used   [24..31] workgroups that landed on XCD 0..7 in the last confined launch
-//  [32] k_l2 chip-wide, nz problems (us, 200 back to back)   [33] k_l2 confined, problem = XCC_ID   [34] h2 identical (1 / 0)   [35] k_l2 chip-wide, 1 problem   [36] confined, 1 problem
-extern "C" int creg_debug_xcd_stage1(creg_train_plan* plan, const creg_train_args* a, int32_t nz, int32_t wg_per_cu, double* out, creg_stream_t stream) {
-    Plan* P = (Plan*)plan;
-    CREG_REQUIRE(P && a && out && nz >= 1 && nz <= 8 && nz <= P->B && wg_per_cu >= 1 && wg_per_cu <= 8, "creg_debug_xcd_stage1: bad argument");
-    const Dims& D = P->D; const Ws& W = P->W;
-    CREG_REQUIRE(D.nyb && D.npb && D.ppl == 1 && D.nbt == 1 && D.nbp == 2, "creg_debug_xcd_stage1: built for the configs[1] instance (64-point blocks, 1 + 2 boxes per lane)");
-    hipStream_t s = (hipStream_t)stream;
-    for (int i = 0; i < 64; ++i) out[i] = 0.0;
-    int* ctl = nullptr; float* payload = nullptr; unsigned long long* ticks = nullptr; int* errs = nullptr;
-    CREG_HIP(hipMalloc(&ctl, 4 * 32 * 32)); CREG_HIP(hipMalloc(&payload, 16 * 4096)); CREG_HIP(hipMalloc(&ticks, 8 * 1024)); CREG_HIP(hipMalloc(&errs, 4));
-    hipEvent_t e0, e1;
-    CREG_HIP(hipEventCreate(&e0)); CREG_HIP(hipEventCreate(&e1));
-    // ---- (a)
-    const int rounds = 200;
-    for (int skew = 0; skew < 2; ++skew)
-        for (int mode = 0; mode < 3; ++mode) {
-            CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s)); CREG_HIP(hipMemsetAsync(errs, 0, 4, s)); CREG_HIP(hipMemsetAsync(payload, 0, 16 * 4096, s));
-            if (mode == 0) hipLaunchKernelGGL(k_xcd_barrier<0>, dim3(256), dim3(256), 0, s, ctl, payload, rounds, skew ? 8 : 0, ticks, errs);
-            else if (mode == 1) hipLaunchKernelGGL(k_xcd_barrier<1>, dim3(256), dim3(256), 0, s, ctl, payload, rounds, skew ? 8 : 0, ticks, errs);
-            else hipLaunchKernelGGL(k_xcd_barrier<2>, dim3(256), dim3(256), 0, s, ctl, payload, rounds, skew ? 8 : 0, ticks, errs);
-            CREG_LAUNCH_CHECK();
-            CREG_HIP(hipStreamSynchronize(s));
-            unsigned long long th[256]; int eh = 0;
-            CREG_HIP(hipMemcpy(th, ticks, sizeof(th), hipMemcpyDeviceToHost)); CREG_HIP(hipMemcpy(&eh, errs, 4, hipMemcpyDeviceToHost));
-            unsigned long long mx = 0; int nmin = 99, nmax = 0;
-            for (int i = 0; i < 256; ++i) { if (th[i] == ~0ull) continue; if ((th[i] >> 8) > mx) mx = th[i] >> 8; const int n = (int)(th[i] & 31) + 1; if (n < nmin) nmin = n; if (n > nmax) nmax = n; }
-            out[3 * skew + mode] = (double)mx / 100.0 / rounds;
-            out[6 + mode] += eh;
-            out[9] = nmin; out[10] = nmax;
-        }
-    // ---- (b)
-    std::vector<creg_train_args> all((size_t)nz, *a);
-    int rc = stage_inputs(P, all.data(), nz, s);
-    if (rc) return rc;
-    P->target_blocks_valid = false;
-    launch_sorts(P, s, nz);
-    const int nz_keep = P->nz;
-    P->nz = nz;
-    for (int e = 0; e < 20; ++e) enqueue_epoch(P, e, s);          // a few epochs in: the clouds as a train sees them
-    launch_head(P, 0, s);
-    CREG_LAUNCH_CHECK();
-    const int REP = 200;
-    float ms = 0.f;
-    auto timed = [&](auto launch, double* o) -> int {
-        launch(0);
-        CREG_HIP(hipEventRecord(e0, s));
-        for (int i = 0; i < REP; ++i) launch(i + 1);
-        CREG_HIP(hipEventRecord(e1, s));
-        CREG_HIP(hipStreamSynchronize(s));
-        CREG_HIP(hipEventElapsedTime(&ms, e0, e1));
-        *o = ms * 1000.0 / REP;
-        return CREG_OK;
-    };
-    if (int r2 = timed([&](int) { launch_nn(D, W, P->bstride, 1, s); }, out + 16)) return r2;
-    if (int r2 = timed([&](int) { launch_nn(D, W, P->bstride, nz, s); }, out + 17)) return r2;
-    const EngineEpi epi{W.sgn_x, W.cnt4, W.lossp_x, W.lossp_y, P->bstride, &W.state[0].stopped};
-    const NnBlocks yb{W.ys4, W.ybox, D.nyb, nullptr}, pb{W.ps4, W.pbox, D.rows ? D.npb : 0, W.sb + D.K};
-    int blocksA, blocksB;
-    if (D.rows) { blocksA = cdiv(64 * D.npb, NN_ROW_SLOTS); blocksB = cdiv(64 * D.nyb, NN_ROW_SLOTS); }
-    else { const NnGrid g = nn_grid(D.NP, D.NT, true, true, 4); blocksA = g.blocksA; blocksB = g.blocksB; }
-    const int grid = 8 * 32 * wg_per_cu;
-    auto xl = [&](int i, int nzz, bool wscope) {
-        const int par = i & 1;
-#define CREG_XCD_GO(R, WS) hipLaunchKernelGGL((k_nn_xcd<R, 1, 2, WS>), dim3(grid), dim3(R ? NN_ROWS_BLOCK : NN_BLOCK), 0, s, (const float*)W.pred4, D.NP, (const float*)W.y4, D.NT, \
-                                              blocksA, blocksB, epi, yb, pb, P->bstride, nzz, ctl, par)
-        if (D.rows) { if (wscope) CREG_XCD_GO(true, true); else CREG_XCD_GO(true, false); }
-        else { if (wscope) CREG_XCD_GO(false, true); else CREG_XCD_GO(false, false); }
-#undef CREG_XCD_GO
-    };
-    CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-    if (int r2 = timed([&](int i) { xl(i, nz, false); }, out + 18)) return r2;
-    CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-    if (int r2 = timed([&](int i) { xl(i, nz, true); }, out + 19)) return r2;
-    CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-    if (int r2 = timed([&](int i) { xl(i, 1, true); }, out + 20)) return r2;
-    {   // identical outputs: loss partials, sign bits and scatter counters of every problem after ONE launch of either kind
-        const size_t nl = (size_t)D.nbx + D.nby;
-        std::vector<float> l0(nl * nz), l1(nl * nz); std::vector<int> s0((size_t)D.NP * nz), s1((size_t)D.NP * nz), c0((size_t)4 * D.NP * nz), c1((size_t)4 * D.NP * nz);
-        auto grab = [&](std::vector<float>& l, std::vector<int>& sg, std::vector<int>& c) -> int {
-            CREG_HIP(hipStreamSynchronize(s));
-            for (int z = 0; z < nz; ++z) {
-                const Ws Wz = ws_shift(W, (size_t)z * P->bstride);
-                CREG_HIP(hipMemcpy(l.data() + nl * z, Wz.lossp_x, 4 * (size_t)D.nbx, hipMemcpyDeviceToHost));
-                CREG_HIP(hipMemcpy(l.data() + nl * z + D.nbx, Wz.lossp_y, 4 * (size_t)D.nby, hipMemcpyDeviceToHost));
-                CREG_HIP(hipMemcpy(sg.data() + (size_t)D.NP * z, Wz.sgn_x, 4 * (size_t)D.NP, hipMemcpyDeviceToHost));
-                CREG_HIP(hipMemcpy(c.data() + (size_t)4 * D.NP * z, Wz.cnt4, 16 * (size_t)D.NP, hipMemcpyDeviceToHost));
-            }
-            return CREG_OK;
-        };
-        launch_head(P, 0, s); launch_nn(D, W, P->bstride, nz, s);
-        if (int r2 = grab(l0, s0, c0)) return r2;
-        launch_head(P, 0, s);
-        CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-        xl(0, nz, true);
-        if (int r2 = grab(l1, s1, c1)) return r2;
-        out[21] = (memcmp(l0.data(), l1.data(), 4 * l0.size()) == 0 && s0 == s1 && c0 == c1) ? 1.0 : 0.0;
-        int ch[32 * 32];
-        CREG_HIP(hipMemcpy(ch, ctl, sizeof(ch), hipMemcpyDeviceToHost));
-        for (int x = 0; x < 8; ++x) out[24 + x] = ch[32 * (8 + x)];
-    }
-    out[22] = 32 * wg_per_cu;
-    CREG_LAUNCH_CHECK();
-    if (D.H == 512) {   // ---- Stage 2 pre-check: k_l2
-        const int l2grid = 8 * (D.H2 / 16);
-        auto l2x = [&](int i, int nzz) { hipLaunchKernelGGL((k_l2_xcd<8>), dim3(l2grid), dim3(L2_THREADS), 0, s, D, W, 0, P->bstride, nzz, ctl, i & 1); };
-        P->nz = nz;
-        if (int r2 = timed([&](int) { launch_l2(P, 0, s); }, out + 32)) return r2;
-        CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-        if (int r2 = timed([&](int i) { l2x(i, nz); }, out + 33)) return r2;
-        P->nz = 1;
-        if (int r2 = timed([&](int) { launch_l2(P, 0, s); }, out + 35)) return r2;
-        CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-        if (int r2 = timed([&](int i) { l2x(i, 1); }, out + 36)) return r2;
-        P->nz = nz;
-        const size_t nh = (size_t)D.KP * D.H2;
-        std::vector<float> h0(nh * nz), h1(nh * nz);
-        launch_l2(P, 0, s);
-        CREG_HIP(hipStreamSynchronize(s));
-        for (int z = 0; z < nz; ++z) CREG_HIP(hipMemcpy(h0.data() + nh * z, ws_shift(W, (size_t)z * P->bstride).h2[0], 4 * nh, hipMemcpyDeviceToHost));
-        for (int z = 0; z < nz; ++z) CREG_HIP(hipMemsetAsync(ws_shift(W, (size_t)z * P->bstride).h2[0], 0xff, 4 * (size_t)D.K * D.H2, s));
-        CREG_HIP(hipMemsetAsync(ctl, 0, 4 * 32 * 32, s));
-        l2x(0, nz);
-        CREG_HIP(hipStreamSynchronize(s));
-        for (int z = 0; z < nz; ++z) CREG_HIP(hipMemcpy(h1.data() + nh * z, ws_shift(W, (size_t)z * P->bstride).h2[0], 4 * nh, hipMemcpyDeviceToHost));
-        bool same = true;
-        for (int z = 0; z < nz && same; ++z) same = memcmp(h0.data() + nh * z, h1.data() + nh * z, 4 * (size_t)D.K * D.H2) == 0;
-        out[34] = same ? 1.0 : 0.0;
-        CREG_LAUNCH_CHECK();
-    }
-    P->nz = nz_keep;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(ctl); (void)hipFree(payload); (void)hipFree(ticks); (void)hipFree(errs);
-    return CREG_OK;
-}
-#endif
 
 extern "C" int creg_train_plan_info(const creg_train_plan* plan, creg_train_plan_info_t* info) {
     CREG_REQUIRE(plan && info, "creg_train_plan_info: null pointer");

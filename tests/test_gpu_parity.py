@@ -1230,11 +1230,10 @@ def test_train_is_bit_reproducible_and_graph_equals_eager(dev, golden, rot, hidd
 
 
 @pytest.mark.parametrize("rot,hidden,lr,stop", [("q", 512, 2e-4, 200), ("dq", 64, 2e-4, 200), ("6d", 128, 2e-4, 200), ("q", 64, 0.2, 3)])
-def test_train_fused_backward_launch_is_bit_identical(dev, golden, rot, hidden, lr, stop, monkeypatch):
-    """CREG_FUSED_GBD=1 (round 5 experiment, off by default because it measured slower: profiles/r05_fused_gbd_ab.log): the gradient
-    reduction and the backward as ONE launch -- the consumers prefetch their parameter rows, wait for the gradient role's blocks inside
-    the launch, then read the gradients with sc1 loads.  Same arithmetic in the same order: every output bit equals the two-launch
-    plan's, eager and captured, also when the train stops early (the gradient blocks of a stopped train still count themselves in)."""
+def test_train_graph_equals_eager_at_hidden_512_64_128_and_early_stop(dev, golden, rot, hidden, lr, stop):
+    """A captured train, an eager one and a second captured one of the five-launch epoch give the same bits -- best poses, loss and lr
+    histories, result record, trained parameters -- at hidden 512 ('q'), 64 ('dq'), 128 ('6d'), and when the train stops early (lr 0.2,
+    stop 3: the remaining epochs of a captured graph run as stopped launches, the eager loop runs them too)."""
     from autourdf_amd import ops
     g, _, _ = _train_case(golden, "q")
     torch.manual_seed(5)
@@ -1247,8 +1246,7 @@ def test_train_fused_backward_launch_is_bit_identical(dev, golden, rot, hidden, 
     clusters = [torch.from_numpy(c) for c in _split(g["q_local"], g["q_offsets"])]
     pts, off = ops.pack_clusters(clusters, dev)
     outs = []
-    for fused, graph in (("0", True), ("1", False), ("1", True)):
-        monkeypatch.setenv("CREG_FUSED_GBD", fused)
+    for graph in (True, False, True):
         params = [model.state_dict()[k].clone().to(dev) for k in order]
         plan = ops.TrainPlan(rot, len(clusters), hidden, pts.shape[0], y.shape[0], epochs=40, use_graph=graph, device=dev)
         bm, bp, res, lh, lrh = plan.run(m, y, pts, off, params, lr=lr, patience=1 if lr > 0.1 else 5, stop=stop)
@@ -1260,12 +1258,10 @@ def test_train_fused_backward_launch_is_bit_identical(dev, golden, rot, hidden, 
 
 
 @pytest.mark.parametrize("rot,k,lr,stop,batch", [("q", None, 2e-4, 200, 1), ("dq", None, 2e-4, 200, 3), ("q", 40, 2e-4, 200, 2), ("q", None, 0.2, 3, 1)])
-def test_train_next_hidden_activation_inside_the_backward_launch_is_bit_identical(dev, golden, rot, k, lr, stop, batch, monkeypatch):
-    """CREG_L2_IN_BD (round 6): the D role of k_bd goes on to the next hidden activation from the updated rows it still holds and the next
-    encoder activation the B role of the same launch hands over (write-through stores, one arrival counter, sc1 loads) -- the k_l2 launch
-    of every epoch disappears.  Same tiles, same k order, same cross-wave sums: every output bit equals the five-launch plan's, eager and
-    captured, single and batched, more than 32 pose rows (two passes of the row loop), also when the train stops early and when a train is
-    resumed from a state (the arrival count follows the step count)."""
+def test_train_graph_equals_eager_at_hidden_512_batched_many_rows_early_stop_and_resumed(dev, golden, rot, k, lr, stop, batch):
+    """Hidden 512: a captured train, an eager one and a second captured one give the same bits, single and in a batch of 3, with more
+    than 32 pose rows (two passes of the row loops of k_bd and k_l2), and when the train stops early; and a train resumed from a state
+    continues it (40 epochs == 15 + 25: control exact, numbers to rounding -- see test_train_resume_continues_a_run)."""
     from autourdf_amd import ops
     g, _, _ = _train_case(golden, "q")
     torch.manual_seed(5)
@@ -1288,8 +1284,7 @@ def test_train_next_hidden_activation_inside_the_backward_launch_is_bit_identica
         assert len(clusters) > 32
     pts, off = ops.pack_clusters(clusters, dev)
     outs = []
-    for l2in, graph in (("0", True), ("1", False), ("1", True)):
-        monkeypatch.setenv("CREG_L2_IN_BD", l2in)
+    for graph in (True, False, True):
         params = [[mdl.state_dict()[kk].clone().to(dev) for kk in order] for mdl in models]
         plan = ops.TrainPlan(rot, len(clusters), hidden, pts.shape[0], y.shape[0], epochs=40, use_graph=graph, device=dev, batch=batch)
         res = plan.run_batch([(m, y, pts, off, pr) for pr in params], lr=lr, patience=1 if lr > 0.1 else 5, stop=stop)
@@ -1299,8 +1294,7 @@ def test_train_next_hidden_activation_inside_the_backward_launch_is_bit_identica
     same = lambda a, b: torch.equal(a, b) or ((torch.isnan(a) == torch.isnan(b)).all() and torch.equal(torch.nan_to_num(a), torch.nan_to_num(b)))
     for o in outs[1:]:
         assert all(same(a, b) for a, b in zip(o, outs[0]))
-    if batch == 1 and lr < 0.1 and k is None:               # resumed: 40 epochs == 15 + 25 in this mode too (control exact, numbers to rounding -- see test_train_resume_continues_a_run)
-        monkeypatch.setenv("CREG_L2_IN_BD", "1")
+    if batch == 1 and lr < 0.1 and k is None:               # resumed: 40 epochs == 15 + 25 at hidden 512 too (control exact, numbers to rounding -- see test_train_resume_continues_a_run)
         lr0 = float(np.float32(lr))
         plan = ops.TrainPlan(rot, len(clusters), hidden, pts.shape[0], y.shape[0], epochs=40, use_graph=False, device=dev)
         pa = [models[0].state_dict()[kk].clone().to(dev) for kk in order]

@@ -25,6 +25,23 @@ def test_build_produces_library_and_every_declared_symbol_resolves():
     assert lib.creg_version() >= 100
 
 
+def test_every_environment_variable_the_library_reads_is_documented():
+    """Every getenv("CREG_...") of the library's sources has a row of its own in the "Environment" table of INTEGRATION.md."""
+    csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
+    read = set()
+    for fn in os.listdir(csrc):
+        if fn.endswith((".hip", ".h")):
+            read |= set(re.findall(r'getenv\("(CREG_\w+)"\)', open(os.path.join(csrc, fn)).read()))
+    assert "CREG_NN_ROWS" in read and "CREG_KM_SPIN_LIMIT" in read           # (the scan does find them)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    table = doc[doc.index("## Environment"):doc.index("## Build / test")]
+    rows = set()
+    for line in table.splitlines():
+        if line.startswith("| `"):
+            rows |= set(re.findall(r"`(\w+)`", line.split("|")[1]))
+    assert read <= rows, sorted(read - rows)
+
+
 def test_product_path_has_no_cpu_fallback_and_never_imports_the_oracle():
     import torch
     from autourdf_amd import dq_func, ops
