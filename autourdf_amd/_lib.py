@@ -91,6 +91,15 @@ SIGNATURES = {
                                            vp, vp, vp, vp]),
     "creg_link_clouds_f64": (ctypes.c_int, [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp,
                                             vp]),
+    "creg_statistical_outlier_f64": (ctypes.c_int, [vp, i64, vp, i32, i32, f64, vp, vp, vp, vp]),
+    "creg_voxel_bounds_f64": (ctypes.c_int, [vp, i64, vp, i32, vp, f64, vp, vp, vp, vp]),
+    "creg_voxel_layout": (ctypes.c_int, [vp, vp, i32, vp]),
+    "creg_voxel_fill_f64": (ctypes.c_int, [vp, i64, vp, i32, vp, f64, vp, vp, vp, i64, vp, vp]),
+    "creg_mc_workspace_bytes": (sz, [i64]),
+    "creg_mc_count_u8": (ctypes.c_int, [vp, vp, vp, i32, i64, vp, vp, vp, sz, vp]),
+    "creg_mc_emit_i32": (ctypes.c_int, [vp, vp, i32, i64, vp, i64, i64, vp, vp, vp, sz, vp]),
+    "creg_mesh_finish_workspace_bytes": (sz, [i64]),
+    "creg_mesh_finish_f64": (ctypes.c_int, [vp, i64, vp, i64, vp, vp, i32, vp, f64, i32, vp, vp, vp, sz, vp]),
     "creg_train_workspace_bytes": (sz, [ctypes.POINTER(TrainShape)]),
     "creg_train_plan_create": (ctypes.c_int, [ctypes.POINTER(TrainShape), vp, sz, ctypes.POINTER(vp)]),
     "creg_train_plan_run": (ctypes.c_int, [vp, ctypes.POINTER(TrainArgs), vp]),

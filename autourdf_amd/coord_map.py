@@ -383,18 +383,27 @@ def _parser():
     return parser
 
 
+def _cli_parser():
+    """The reference's flags plus this project's own: --voxel_size meshes the links (it overrides parameters.json's key)."""
+    parser = _parser()
+    parser.add_argument('--voxel_size', type=float, default=None)
+    return parser
+
+
 def main(argv=None):
-    """The reference's ``python coord_map.py`` (coord_map.py:641-792) without its viewers, plots and meshing: sum maps,
-    MST, link discovery, kinematic tree, joint axes, link clouds, their ICP refinement and the URDF file.  Paths are
-    the reference's, relative to the working directory, and ``parameters.json`` is read from there."""
+    """The reference's ``python coord_map.py`` (coord_map.py:641-792) without its viewers and plots: sum maps, MST, link
+    discovery, kinematic tree, joint axes, link clouds, their ICP refinement, the link meshes and the URDF file.  Paths
+    are the reference's, relative to the working directory, and ``parameters.json`` is read from there.  The links are
+    meshed (``{i:04}.ply`` and ``{i:04}.stl`` in the link directory, the files the URDF names) when the robot's entry has a
+    ``voxel_size`` or ``--voxel_size`` is given; the option wins."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
     from .compute_joints import create_urdf, estimate_joint_axes_from_tree
-    from .link import refine_links_clusters, save_links
-    args = _parser().parse_args(argv)
+    from .link import link_mesh, refine_links_clusters, save_links, visualize_links
+    args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("autourdf_amd.coord_map needs an MI355X: no GPU is visible and there is no CPU path")
     with open('parameters.json') as f:
@@ -445,8 +454,14 @@ def main(argv=None):
     sub_link_path = [link_path + path.split('/')[-2] + '/' for path in sub_part_path][:1]
     save_links(cm_list, cluster_idx, sub_link_path, START, END)
     refine_links_clusters(sub_link_path, START, END, dof)
-    print("skipped (out of scope): the cluster / link viewers and plots, visualize_links, link_mesh (meshing), "
-          "visualize_kinematic_tree and visualize_urdf")
+    voxel_size = args.voxel_size if args.voxel_size is not None else robot_params.get('voxel_size')
+    if voxel_size is None:
+        print("skipped (out of scope): the cluster / link viewers and plots, visualize_links, link_mesh (meshing), "
+              "visualize_kinematic_tree and visualize_urdf")
+    else:
+        visualize_links(sub_link_path, START, END, dof, False)
+        link_mesh(sub_link_path, dof, voxel_size, False)
+        print("skipped (out of scope): the cluster / link viewers and plots, visualize_kinematic_tree and visualize_urdf")
     os.makedirs(f'data/urdf/{ROBOT}_{NUM_SEG}_seg/', exist_ok=True)
     urdf_path = f'data/urdf/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams.urdf'
     create_urdf(links, joint_data, cm_list[0], urdf_path, sub_link_path[0])

@@ -1,12 +1,18 @@
-"""Drop-in for ``save_links`` and ``refine_links_clusters`` of the reference's ``PointCloud/link.py`` (:67-127; SURVEY
-8(f) N3).  ``save_links`` writes what ``CoordMap.cluster_to_link`` computes (one launch per sequence).  In
+"""Drop-in for ``save_links``, ``refine_links_clusters``, ``visualize_links`` (its headless half) and ``link_mesh`` of the
+reference's ``PointCloud/link.py`` (:67-314; SURVEY 8(f) N3, DESIGN N4).  ``save_links`` writes what ``CoordMap.cluster_to_link`` computes (one launch per sequence).  In
 ``refine_links_clusters`` every link cloud of every time step is registered to the same link at ``start_steps`` by
 point-to-point ICP (threshold 1, identity start, open3d's relative 1e-6 stopping rule) and written,
 moved, to ``cluster_rf/{t:04}.npz``.  The reference runs one Open3D ICP per (time step, link); here the
 links of up to 16 time steps share ONE launch of the K4 kernel in its point-to-point mode
 (``creg_masked_icp_batch_f64`` with ``tgt_offsets``; a workgroup per link per time step).
 
-Meshing, SDF and GUI functions of the reference file are out of scope.  No CPU fallback.
+``visualize_links`` writes every link's concatenated clouds as ``{i:04}.ply`` (refined) and ``{i:04}_og.ply``; ``link_mesh``
+reads them back and writes ``{i:04}.stl``: outlier removal, voxel grid, marching cubes, one smoothing pass and the STL
+records all run on the GPU, every link of a directory in one set of launches (``ops.statistical_outlier``,
+``ops.voxel_mesh``).  The meshes follow this project's own contract (DESIGN N4), not the reference's Open3D / PyMCubes /
+pymeshfix chain: closed and consistently oriented by construction, so there is no repair step.
+
+The viewers and the SDF functions of the reference file are out of scope.  No CPU fallback.
 """
 import glob
 import os
@@ -16,6 +22,8 @@ import torch
 
 from . import _lib, ops
 from .helper_functions import load_pc_npz, save_pc_npz
+
+NB_NEIGHBORS, STD_RATIO = 20, 2.0                  # the reference's remove_statistical_outlier arguments (link.py:218)
 
 
 def _pack(clouds, device):
@@ -69,3 +77,71 @@ def refine_links_clusters(path_list, start_steps, end_steps, dof):
                 flush()
             pending.append((t, k, src, soff))
         flush()
+
+
+def write_ply(path, points):
+    """Binary little-endian PLY with double x y z, the layout sim_data.save_step_data writes."""
+    pts = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3), "<f8")
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty double x\nproperty double y\n"
+                 "property double z\nend_header\n" % len(pts)).encode("ascii"))
+        f.write(pts.tobytes())
+
+
+STL_RECORD = np.dtype([("data", "<f4", (4, 3)), ("attr", "<u2")])     # 50 bytes: normal, three vertices, attribute count
+
+
+def write_stl(path, records):
+    """Binary STL: 80-byte header, uint32 facet count, 50-byte records.  records (F,4,3) float32 as the kernel emits them."""
+    rec = np.asarray(records, np.float32).reshape(-1, 4, 3)
+    out = np.zeros(len(rec), STL_RECORD)
+    out["data"] = rec
+    with open(path, "wb") as f:
+        f.write(b"autourdf_amd link mesh".ljust(80, b" "))
+        f.write(np.uint32(len(rec)).tobytes())
+        f.write(out.tobytes())
+
+
+def read_stl(path):
+    """(F,4,3) float32 records of a binary STL; IOError unless the size matches the facet count."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 84:
+        raise IOError(f"{path}: shorter than a binary STL header")
+    count = int(np.frombuffer(raw, "<u4", 1, 80)[0])
+    if len(raw) != 84 + 50 * count:
+        raise IOError(f"{path}: {len(raw)} bytes do not hold {count} facets")
+    return np.frombuffer(raw, STL_RECORD, count, 84)["data"].copy()
+
+
+def visualize_links(path_list, start_steps, end_steps, dof, vis_flow):
+    """The headless half of link.py:131-201 (same signature): every link's clouds of steps start_steps..end_steps
+    concatenated, in the link frame -- cluster_rf as {i:04}.ply, cluster as {i:04}_og.ply."""
+    if vis_flow:
+        raise NotImplementedError("visualize_links: there is no viewer here; call it with vis_flow=False")
+    for link_dir in path_list:
+        link_c_files = sorted(glob.glob(link_dir + 'cluster/*.npz'))
+        link_crf_files = sorted(glob.glob(link_dir + 'cluster_rf/*.npz'))
+        c = [load_pc_npz(link_c_files[t]) for t in range(start_steps, end_steps)]
+        crf = [load_pc_npz(link_crf_files[t]) for t in range(start_steps, end_steps)]
+        for i in range(dof + 1):
+            write_ply(link_dir + f'{i:04}.ply', np.concatenate([np.asarray(f[i], np.float64).reshape(-1, 3) for f in crf]))
+            write_ply(link_dir + f'{i:04}_og.ply', np.concatenate([np.asarray(f[i], np.float64).reshape(-1, 3) for f in c]))
+
+
+def link_mesh(path_list, dof, vsize, vis_flow):
+    """link.py:204-314 (same signature): {i:04}.ply -> outlier removal, voxel grid of size vsize, marching cubes, one
+    smoothing pass -> binary {i:04}.stl, all dof + 1 links of a directory through one set of launches."""
+    from .cluster_icp import read_point_cloud
+    if vis_flow:
+        raise NotImplementedError("link_mesh: there is no viewer here; call it with vis_flow=False")
+    dev = _lib.device()
+    for link_dir in path_list:
+        clouds = [np.asarray(read_point_cloud(link_dir + f'{i:04}.ply').points, np.float64).reshape(-1, 3)
+                  for i in range(dof + 1)]
+        off = torch.as_tensor(np.concatenate([[0], np.cumsum([len(c) for c in clouds])]).astype(np.int64), device=dev)
+        pts = torch.as_tensor(np.concatenate(clouds), device=dev).contiguous()
+        keep, _, _ = ops.statistical_outlier(pts, off, NB_NEIGHBORS, STD_RATIO)
+        meshes = ops.voxel_mesh(pts, off, vsize, smooth=True, keep=keep)
+        for i, m in enumerate(meshes):
+            write_stl(link_dir + f'{i:04}.stl', m["stl_records"].cpu().numpy())

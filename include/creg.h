@@ -344,6 +344,51 @@ int creg_link_clouds_f64(const double* coords, const double* matrices, int32_t T
                          double* clouds_lf, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Link meshing (PointCloud/link.py:204-314, link_mesh; DESIGN N4).  The contract is this project's own, NOT pinned to
+ * Open3D / PyMCubes / pymeshfix.  Every call takes all L links of one directory: points (n,3) fp64 concatenated with
+ * offsets (L+1) int64, per-link outputs concatenated the same way.
+ *
+ * creg_statistical_outlier_f64: avg (n) = mean distance to the k' = min(nb_neighbors, n_link) nearest points of the own
+ *   link (self included, exact search); per link over avg > 0: thr (L) = mean + std_ratio * sample deviation (NaN with
+ *   fewer than two such points); keep (n) uint8 = avg > 0 && avg < thr.  nb_neighbors outside [1, 32]: CREG_EINVAL.
+ * creg_voxel_bounds_f64: over the kept points (keep may be NULL = all): origin (L,3) = min - voxel_size / 2, dims (L,3)
+ *   int32 = largest floor((p - origin) / voxel_size) + 1, n_kept (L) int64.
+ * creg_voxel_layout: HOST arrays in, HOST node_offsets (L+1) out, launches nothing.  The volume of link l has dims + 2
+ *   nodes per axis (one empty layer on every side), node (x,y,z) at (x * Y + y) * Z + z.  CREG_EINVAL for a link without
+ *   kept points, a padded axis above 1024 nodes, or more than 2^28 nodes in total.
+ * creg_voxel_fill_f64: occ (total_nodes) bytes, zeroed and filled here.
+ * creg_mc_count_u8: marching cubes at level 0.5, phase 1: classifies every cell, leaves the case masks and the scanned
+ *   per-node vertex / triangle prefixes in the workspace (creg_mc_workspace_bytes) and writes vert_offsets (L+1) and
+ *   tri_offsets (L+1) int64 (device), which the host reads to size phase 2's outputs.
+ * creg_mc_emit_i32: phase 2 on the same workspace: verts_h (V,3) int32 in half-voxel units of the unpadded grid (numbered
+ *   per link by owning node in linear order, then axis), tris (F,3) int32 local to the link (cell linear order, then
+ *   table order; normals point from occupied to empty).
+ * creg_mesh_finish_f64: vertices (V,3) fp64 = origin + (voxel_size / 2) * v', v' = (v + sum of neighbours) / (1 + deg)
+ *   with integer sums when smooth != 0 (workspace: creg_mesh_finish_workspace_bytes), v' = v otherwise; stl_records
+ *   (F,4,3) float32: unit normal of the float32-rounded vertices ((0,0,0) for zero area), then the three vertices.
+ * voxel_size <= 0 or non-finite: CREG_EINVAL.  A refused call launches nothing. */
+int creg_statistical_outlier_f64(const double* points, int64_t n, const int64_t* offsets, int32_t L, int32_t nb_neighbors,
+                                 double std_ratio, double* avg, double* thr, uint8_t* keep, creg_stream_t stream);
+int creg_voxel_bounds_f64(const double* points, int64_t n, const int64_t* offsets, int32_t L, const uint8_t* keep,
+                          double voxel_size, double* origin, int32_t* dims, int64_t* n_kept, creg_stream_t stream);
+int creg_voxel_layout(const int32_t* dims, const int64_t* n_kept, int32_t L, int64_t* node_offsets);
+int creg_voxel_fill_f64(const double* points, int64_t n, const int64_t* offsets, int32_t L, const uint8_t* keep,
+                        double voxel_size, const double* origin, const int32_t* dims, const int64_t* node_offsets,
+                        int64_t total_nodes, uint8_t* occ, creg_stream_t stream);
+size_t creg_mc_workspace_bytes(int64_t total_nodes);
+int creg_mc_count_u8(const uint8_t* occ, const int32_t* dims, const int64_t* node_offsets, int32_t L, int64_t total_nodes,
+                     int64_t* vert_offsets, int64_t* tri_offsets, void* workspace, size_t workspace_bytes,
+                     creg_stream_t stream);
+int creg_mc_emit_i32(const int32_t* dims, const int64_t* node_offsets, int32_t L, int64_t total_nodes,
+                     const int64_t* vert_offsets, int64_t V, int64_t F, int32_t* verts_h, int32_t* tris, void* workspace,
+                     size_t workspace_bytes, creg_stream_t stream);
+size_t creg_mesh_finish_workspace_bytes(int64_t V);
+int creg_mesh_finish_f64(const int32_t* verts_h, int64_t V, const int32_t* tris, int64_t F, const int64_t* vert_offsets,
+                         const int64_t* tri_offsets, int32_t L, const double* origin, double voxel_size, int32_t smooth,
+                         double* vertices, float* stl_records, void* workspace, size_t workspace_bytes,
+                         creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The `--normal` branch (mlp_reg.py:190-203, cluster_icp.py:49-62; CLI flag mlp_reg.py:399): Open3D normal estimation +
  * orientation, then sklearn k_means over [xyz | 0.5 * normal].
  *
