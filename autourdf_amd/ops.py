@@ -355,6 +355,30 @@ def visibility(tri, tri_link, link_T, cams, pts, fov_deg=60.0, aspect=1.0, near=
     return (vis.bool(), ws.reshape(C, height, width)) if return_depth else vis.bool()
 
 
+def urdf_fk(table, q, base, want_lines: bool = False):
+    """Batched forward kinematics (creg_urdf_fk_f64): ``table`` from ``UrdfRobot.fk_table()``, q (P,J) joint values in the
+    table's order and base (4,4), host arrays or f64 device tensors -> link_T (P,L,4,4) f64 on the device, and
+    joint_lines (P,J,6) = world position of the joint frame | unit world axis when ``want_lines``.  One launch for all P."""
+    L = _lib.load()
+    dev = _lib.device(q, base)
+    tdev = table.get("_dev")
+    if tdev is None or tdev[0].device != dev:                     # the table goes up once per robot and device
+        tdev = tuple(torch.as_tensor(np.ascontiguousarray(table[k]), device=dev) for k in ("parent", "child", "type", "origin", "axis"))
+        table["_dev"] = tdev
+    parent, child, kind, origin, axis = tdev
+    q = _need(torch.as_tensor(q, dtype=torch.float64, device=dev), torch.float64, "q")
+    base = _need(torch.as_tensor(base, dtype=torch.float64, device=dev), torch.float64, "base")
+    J, n_links = parent.shape[0], int(table["n_links"])
+    if q.dim() != 2 or q.shape[1] != J or tuple(base.shape) != (4, 4):
+        raise ValueError(f"urdf_fk: q must be (P,{J}) and base (4,4), got {tuple(q.shape)} and {tuple(base.shape)}")
+    P = q.shape[0]
+    link_T = torch.empty(P, n_links, 4, 4, dtype=torch.float64, device=dev)
+    lines = torch.empty(P, J, 6, dtype=torch.float64, device=dev) if want_lines else None
+    _lib.check(L.creg_urdf_fk_f64(_p(parent), _p(child), _p(kind), _p(origin), _p(axis), J, n_links, int(table["root"]), _p(q), P,
+                                  _p(base), _p(link_T), _p(lines), _stream()), "creg_urdf_fk_f64")
+    return (link_T, lines) if want_lines else link_T
+
+
 # ------------------------------------------------------------------------------ N2 pose distance maps
 def coord_dist_map(M: torch.Tensor, bounding_box: float, diff: bool = True):
     """CoordMap.coord_dist_map (coord_map.py:230-307) for poses M (T,K,4,4) f64 on the device:

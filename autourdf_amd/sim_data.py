@@ -362,6 +362,42 @@ class UrdfRobot:
             pending = rest
         return T
 
+    def fk_table(self):
+        """The joint table ``ops.urdf_fk`` (creg_urdf_fk_f64) walks, built once per robot: joints in the topological order
+        ``fk`` resolves them in, with ``parent`` / ``child`` link indices, ``type`` (0 fixed, 1 revolute or continuous,
+        2 prismatic), ``origin`` (J,4,4) already scaled by ``global_scale``, ``axis`` (J,3) normalised as ``_axis_angle`` does,
+        ``names`` (table row -> joint name), ``root`` and ``n_links``."""
+        if getattr(self, "_fk_table", None) is None:
+            done, order, pending = {self.root}, [], list(self.joints)
+            while pending:
+                rest = []
+                for j in pending:
+                    if j["parent"] in done:
+                        order.append(j)
+                        done.add(j["child"])
+                    else:
+                        rest.append(j)
+                if len(rest) == len(pending):
+                    raise ValueError(f"{self.path}: joints {[j['name'] for j in rest]} hang off unknown links")
+                pending = rest
+            kind = {"revolute": 1, "continuous": 1, "prismatic": 2}
+            unit = lambda a: a / np.linalg.norm(a) if np.linalg.norm(a) > 0 else np.array([1.0, 0.0, 0.0])   # a fixed joint may carry "0 0 0"
+            axis = np.array([unit(np.asarray(j["axis"], np.float64)) for j in order]).reshape(-1, 3)
+            names = [j["name"] for j in order]
+            self._fk_table = {
+                "parent": np.array([self.link_index[j["parent"]] for j in order], np.int32),
+                "child": np.array([self.link_index[j["child"]] for j in order], np.int32),
+                "type": np.array([kind.get(j["type"], 0) for j in order], np.int32),
+                "origin": np.array([j["origin"] for j in order], np.float64).reshape(-1, 4, 4),
+                "axis": axis, "names": names,
+                "root": self.link_index[self.root], "n_links": len(self.links)}
+        return self._fk_table
+
+    def q_rows(self, q_by_joint_list):
+        """(P,J) joint values in ``fk_table()``'s order from P dicts {name: value} (missing joints at 0, as in ``fk``)."""
+        names = self.fk_table()["names"]
+        return np.array([[float(q.get(n, 0.0)) for n in names] for q in q_by_joint_list], np.float64).reshape(-1, len(names))
+
 
 class SimEnv:
     """The part of the reference's SimEnv (sim_data.py:15-64) that describes the robot: revolute joints in URDF
@@ -407,10 +443,11 @@ class SimEnv:
             frames.append(np.concatenate([e, f, s_, np.cross(s_, f)]))
         self.cam_frames = np.asarray(frames)
 
-    def visible(self, joint_positions, pts, width=800, height=800, eps=0.004):
-        """Which of `pts` (n,3 world points, device tensor) some camera of the ring sees (creg_visibility_f64)."""
+    def visible(self, joint_positions, pts, width=800, height=800, eps=0.004, link_T=None):
+        """Which of `pts` (n,3 world points, device tensor) some camera of the ring sees (creg_visibility_f64).
+        `link_T` (L,4,4) device poses (a row of ops.urdf_fk) replace the host forward kinematics and its upload."""
         tri, _, own = self._device_mesh()
-        T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=tri.device)
+        T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=tri.device) if link_T is None else link_T
         cams = torch.as_tensor(self.cam_frames, device=tri.device)
         c = self.cameras[0]
         return ops.visibility(tri, own, T, cams, pts, c['fov'], c['aspect'], c['near_val'], c['far_val'], width, height, eps)
@@ -432,10 +469,11 @@ class SimEnv:
             q[name] = float(commands[j_id]) if name in self.dof_list else (hi + lo) / 2 + manual_positions * (hi - lo) / 2
         return q
 
-    def sample_surface(self, joint_positions, n, rng):
-        """n area-weighted surface points of the posed robot, on the GPU (creg_sample_mesh_f64)."""
+    def sample_surface(self, joint_positions, n, rng, link_T=None):
+        """n area-weighted surface points of the posed robot, on the GPU (creg_sample_mesh_f64).
+        `link_T` (L,4,4) device poses (a row of ops.urdf_fk) replace the host forward kinematics and its upload."""
         tri, cum, own = self._device_mesh()
-        T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=tri.device)
+        T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=tri.device) if link_T is None else link_T
         u = torch.as_tensor(rng.random((n, 3)), device=tri.device)
         return ops.sample_mesh(tri, cum, own, T, u)
 
@@ -460,12 +498,14 @@ def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list)
 
 
 def data_collection(env, data_path=None, width=800, height=800, visualize=False, angle_list=None, ground_flag=False,
-                    noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True):
+                    noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None):
     """One sequence: for every row of ``angle_list`` pose the robot, sample surface points, keep those that at least one
     camera of the ring sees (``occlusion``: depth buffers of ``width`` x ``height`` like the reference's rendered images,
     sim_data.py:286-306; more samples are drawn until ``oversample * num_points`` visible ones exist), add the
     reference's noise (translation N(0, 0.01) per frame and N(0, 0.0005) per point, not on the first frame;
     sim_data.py:333-343), farthest-point down-sample to ``num_points`` (:346,349) and save.
+    ``link_T`` (P,L,4,4), optional: device link poses of all rows at once (ops.urdf_fk); row ``jp_id`` poses step ``jp_id``
+    in place of the host forward kinematics.
     Returns (collision=False, list of PointCloud) like the reference (self-collision checking is PyBullet's)."""
     if visualize:
         raise NotImplementedError("visualize=True needs Open3D's viewer (out of scope)")
@@ -474,13 +514,14 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     for jp_id, cmd in enumerate(np.asarray(angle_list)):
         q = env.set_joint_positions(cmd)
         want = oversample * num_points
-        pts = env.sample_surface(q, want, rng)
+        pose = {} if link_T is None else {"link_T": link_T[jp_id]}
+        pts = env.sample_surface(q, want, rng, **pose)
         if occlusion:
-            kept = pts[env.visible(q, pts, width, height)]
+            kept = pts[env.visible(q, pts, width, height, **pose)]
             draws = 1
             while kept.shape[0] < want and draws < 16:            # interior / hidden surfaces: draw until enough are visible
-                more = env.sample_surface(q, want, rng)
-                kept = torch.cat([kept, more[env.visible(q, more, width, height)]])
+                more = env.sample_surface(q, want, rng, **pose)
+                kept = torch.cat([kept, more[env.visible(q, more, width, height, **pose)]])
                 draws += 1
             if kept.shape[0] < num_points:
                 raise RuntimeError(f"only {kept.shape[0]} of the sampled surface points are visible from the camera ring")

@@ -434,6 +434,23 @@ int creg_visibility_f64(const double* tri, const int32_t* tri_link, int32_t n_tr
                         int32_t width, int32_t height, const double* pts, int64_t n, double eps, uint8_t* visible,
                         void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
+/* Batched forward kinematics of a URDF joint table: every link pose of n_poses joint states in one launch (the evaluation
+ * stage, Sim/evaluation.py:84-224 and :228-310, where PyBullet poses the robots one state at a time).
+ * The table is in TOPOLOGICAL order -- a joint's parent link is `root` or the child of an earlier joint -- and holds, per
+ * joint: parent / child (n_joints) link indices in [0, n_links), type (n_joints) 0 fixed, 1 revolute or continuous,
+ * 2 prismatic, origin (n_joints,4,4) the joint frame in the parent link (translation already scaled), axis (n_joints,3)
+ * UNIT axis in the joint frame.  q (n_poses,n_joints) joint values in the table's order, base (4,4) the root link's pose.
+ * Poses are affine: bottom rows are taken as 0 0 0 1.
+ *   link_T (n_poses,n_links,4,4):  T_child = T_parent * origin * motion(q), motion = I + sin q K + (1 - cos q) K K for
+ *                                  type 1 (K = [axis]x), a translation by axis * q for type 2, I for type 0; the root is
+ *                                  `base`, a link no joint reaches is the identity.
+ *   joint_lines (n_poses,n_joints,6), may be NULL: (T_parent * origin)[:3,3] | (T_parent * origin)[:3,:3] axis -- the
+ *                                  joint frame's origin and the unit joint axis in the world.
+ * A joint whose parent or child index is outside [0, n_links) is skipped (its line is 0).  n_joints, n_links, n_poses >= 1. */
+int creg_urdf_fk_f64(const int32_t* parent, const int32_t* child, const int32_t* type, const double* origin,
+                     const double* axis, int32_t n_joints, int32_t n_links, int32_t root, const double* q,
+                     int32_t n_poses, const double* base, double* link_T, double* joint_lines, creg_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * A1  the whole `train` loop (mlp_reg.py:17-152) as one device-resident plan: per epoch
  * pose -> sin/cos features -> MLP -> pose -> calculate_pc -> L1 Chamfer -> backward -> Adam ->

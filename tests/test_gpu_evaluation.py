@@ -1,0 +1,414 @@
+"""The evaluation stage on the GPU (autourdf_amd/evaluation.py; reference Sim/evaluation.py): batched forward kinematics
+(creg_urdf_fk_f64) against the host FK and the independent oracle FK, the optional device-pose keyword of the frame
+generator, compare_joints on a rewritten robot with known differences, evaluation() end to end against the oracle's ICP
+filter + Chamfer on the clouds it wrote, and main() in a directory laid out like the reference's data/.
+
+Tolerances (derived, not measured).
+* FK, atol 1e-12: entries are at most about 2, every joint costs two 4x4 products, the deepest chain of these robots has
+  9 joints, device sin / cos are good to a few ulp: at most about 1e-13, one decade of margin.
+* Joint positions 1e-12 m (the same chain).  Directions: arccos near +-1 turns an error eps of the dot product into
+  sqrt(2 eps), a few ulps give up to about 3e-6 degrees: 1e-5 degrees where the expected angle is within a degree of 0
+  or 180; elsewhere the sensitivity is 1 / sin(theta) <= 58, and 1e-13 in the axes stays below 1e-9 degrees.
+* Losses: relative 1e-6 of max(1, |want|), what test_evaluation_icp_filter_and_chamfer_vs_oracle applies to this pair of
+  kernels.
+
+Every test runs under its own time limit (a watchdog that ends the process: a hung kernel must not be waited on)."""
+import faulthandler
+import json
+import os
+import xml.etree.ElementTree as ET
+
+import numpy as np
+import pytest
+import torch
+from scipy.spatial.transform import Rotation
+
+from _robots import unpack_robots
+from _toy_urdf import write_toy_robot
+
+pytestmark = pytest.mark.gpu
+
+FK_TOL = 1e-12
+POS_TOL = 1e-12
+DIR_TOL_FLAT = 1e-5
+DIR_TOL = 1e-9
+LIMITS = {"test_evaluation_end_to_end_on_the_toy_robot": 600, "test_main_writes_the_result_files": 420,
+          "test_fk_parity_on_the_fixture_robots": 300}
+
+
+@pytest.fixture(autouse=True)
+def _time_limit(request):
+    faulthandler.dump_traceback_later(LIMITS.get(request.node.originalname, 180), exit=True)
+    yield
+    faulthandler.cancel_dump_traceback_later()
+
+
+def _dir_tol(expected_deg):
+    return DIR_TOL_FLAT if min(expected_deg, 180.0 - expected_deg) < 1.0 else DIR_TOL
+
+
+# ------------------------------------------------------------------------------------------ independent restatements
+def _oracle_joints(urdf_path, global_scale=1.0):
+    """links, root and joints of a URDF as oracle.sim_data.fk takes them (its own parse: xyz / rpy / axis, not matrices)."""
+    root = ET.parse(urdf_path).getroot()
+    links = [l.get("name") for l in root.findall("link")]
+    joints = []
+    for j in root.findall("joint"):
+        o, ax = j.find("origin"), j.find("axis")
+        f = lambda e, k, d: [float(v) for v in (e.get(k, d) if e is not None else d).split()]
+        joints.append(dict(name=j.get("name"), type=j.get("type"), parent=j.find("parent").get("link"), child=j.find("child").get("link"),
+                           xyz=list(global_scale * np.array(f(o, "xyz", "0 0 0"))), rpy=f(o, "rpy", "0 0 0"), axis=f(ax, "xyz", "1 0 0")))
+    children = {j["child"] for j in joints}
+    return links, [l for l in links if l not in children][0], joints
+
+
+def _base(ori, pos=(0, 0, 0)):
+    B = np.eye(4)
+    B[:3, :3] = Rotation.from_euler("xyz", ori).as_matrix()
+    B[:3, 3] = pos
+    return B
+
+
+def _oracle_lines(links, root, joints, q, base):
+    """{joint name: (position, unit axis)} in the world: (T_parent origin)[:3,3] and (T_parent origin)[:3,:3] axis, with
+    T_parent from oracle.sim_data.fk and the origin rebuilt from xyz / rpy by scipy."""
+    from oracle import sim_data as osim
+    T = osim.fk(links, joints, q, root, base)
+    out = {}
+    for j in joints:
+        O = np.eye(4)
+        O[:3, :3] = Rotation.from_euler("xyz", j["rpy"]).as_matrix()
+        O[:3, 3] = j["xyz"]
+        A = T[links.index(j["parent"])] @ O
+        a = np.asarray(j["axis"], np.float64)
+        out[j["name"]] = (A[:3, 3], A[:3, :3] @ (a / np.linalg.norm(a)))
+    return out
+
+
+def _random_q(robot, P, rng):
+    """P joint states inside the limits (a continuous joint in [-pi, pi]; fixed joints get values too: they must be ignored),
+    the first row all zero."""
+    rows = []
+    for p in range(P):
+        q = {}
+        for j in robot.joints:
+            lo, hi = sorted(j["limit"])
+            if j["type"] != "revolute" and j["type"] != "prismatic":
+                lo, hi = -np.pi, np.pi
+            q[j["name"]] = 0.0 if p == 0 else float(rng.uniform(lo, hi))
+        rows.append(q)
+    return rows
+
+
+def _check_fk(urdf_path, P, seed, want_lines=True):
+    from autourdf_amd import ops
+    from autourdf_amd.sim_data import UrdfRobot
+    from oracle import sim_data as osim
+    robot = UrdfRobot(urdf_path)
+    table = robot.fk_table()
+    rng = np.random.default_rng(seed)
+    base = _base([0.3, -0.2, 0.9], [0.05, -0.02, 0.1])
+    rows = _random_q(robot, P, rng)
+    out = ops.urdf_fk(table, robot.q_rows(rows), base, want_lines=want_lines)
+    link_T, lines = out if want_lines else (out, None)
+    assert link_T.is_cuda and link_T.dtype == torch.float64 and tuple(link_T.shape) == (P, len(robot.links), 4, 4)
+    link_T = link_T.cpu().numpy()
+    links, root, joints = _oracle_joints(urdf_path)
+    check = range(P) if P <= 65 else list(range(0, P, 17)) + [P - 1]         # the host loops are slow: rows across every block, and the last
+    for p in check:
+        np.testing.assert_allclose(link_T[p], robot.fk(rows[p], base), rtol=0, atol=FK_TOL)
+        np.testing.assert_allclose(link_T[p], osim.fk(links, joints, rows[p], root, base), rtol=0, atol=FK_TOL)
+    assert (link_T[:, :, 3] == [0, 0, 0, 1]).all()
+    if want_lines:
+        assert tuple(lines.shape) == (P, len(robot.joints), 6)
+        lines = lines.cpu().numpy()
+        np.testing.assert_allclose(np.linalg.norm(lines[:, :, 3:], axis=2), 1.0, rtol=0, atol=1e-14)
+        for p in check:
+            want = _oracle_lines(links, root, joints, rows[p], base)
+            for i, name in enumerate(table["names"]):
+                np.testing.assert_allclose(lines[p, i, :3], want[name][0], rtol=0, atol=FK_TOL)
+                np.testing.assert_allclose(lines[p, i, 3:], want[name][1], rtol=0, atol=FK_TOL)
+    return link_T
+
+
+# ------------------------------------------------------------------------------------------ FK parity
+def test_fk_parity_on_the_toy_robot(tmp_path):
+    path, links, joints = write_toy_robot(str(tmp_path))
+    _check_fk(path, 65, seed=0)                                      # 64 random rows and the all-zero one
+
+
+def test_fk_parity_on_the_fixture_robots(tmp_path):
+    """wx200 (a continuous joint, six fixed ones, depth 9), franka (COLLADA visuals, depth 7), allegro (four fingers, depth 5)."""
+    robots = unpack_robots(tmp_path)
+    for k, rel in enumerate(["interbotix_descriptions/urdf/wx200_real.urdf", "franka/franka_panda.urdf",
+                             "allegro_hand_description/allegro_hand_description_left.urdf"]):
+        _check_fk(os.path.join(robots, rel), 65, seed=10 + k)
+
+
+@pytest.mark.parametrize("P", [1, 257])
+def test_fk_one_pose_and_a_count_no_block_size_divides(tmp_path, P):
+    path, _, _ = write_toy_robot(str(tmp_path))
+    _check_fk(path, P, seed=3)
+
+
+def test_fk_without_joint_lines_gives_the_same_poses(tmp_path):
+    path, _, _ = write_toy_robot(str(tmp_path))
+    with_lines = _check_fk(path, 65, seed=5, want_lines=True)
+    without = _check_fk(path, 65, seed=5, want_lines=False)            # joint_lines = NULL
+    np.testing.assert_array_equal(with_lines, without)
+
+
+def test_fk_refuses_bad_shapes(tmp_path):
+    from autourdf_amd import ops
+    from autourdf_amd.sim_data import UrdfRobot
+    path, _, _ = write_toy_robot(str(tmp_path))
+    robot = UrdfRobot(path)
+    with pytest.raises(ValueError):
+        ops.urdf_fk(robot.fk_table(), np.zeros((2, 3)), np.eye(4))      # the toy has four joints
+    with pytest.raises(ValueError):
+        ops.urdf_fk(robot.fk_table(), np.zeros((2, 4)), np.eye(3))
+
+
+# ------------------------------------------------------------------------------------------ the optional keyword
+def test_sample_surface_and_visible_take_device_poses(tmp_path):
+    from autourdf_amd import ops
+    from autourdf_amd.sim_data import SimEnv
+    path, _, _ = write_toy_robot(str(tmp_path))
+    env = SimEnv(path, base_position=[0.05, -0.02, 0.0], base_orientation=[0.0, 0.1, 0.7], dof=3, radius=1.2, num_cameras=4)
+    cmds = [[0.4, -0.6, 0.9], [-1.0, 0.3, 0.2], [0.0, 0.0, 0.0]]
+    qs = [env.set_joint_positions(c) for c in cmds]
+    link_T = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
+    for p, q in enumerate(qs):
+        host = env.sample_surface(q, 5000, np.random.default_rng(7))
+        again = env.sample_surface(q, 5000, np.random.default_rng(7))
+        assert torch.equal(host, again)                                  # without the keyword: bit-identical, as before
+        dev = env.sample_surface(q, 5000, np.random.default_rng(7), link_T=link_T[p])
+        assert float((host - dev).abs().max()) <= 1e-12
+        vis_host = env.visible(q, host, 200, 200)
+        assert torch.equal(vis_host, env.visible(q, host, 200, 200))
+        vis_dev = env.visible(q, host, 200, 200, link_T=link_T[p])
+        # a pose that differs by 1e-13 may flip a point that sits exactly on the eps margin of a depth buffer, or a pixel centre
+        # that sits exactly on a facet's edge: 2 in 1000 of the points at the very most
+        assert int((vis_host != vis_dev).sum()) <= 10 and 0.3 < float(vis_dev.float().mean()) < 1.0
+
+
+def test_data_collection_with_device_poses_matches_the_host_path(tmp_path):
+    from autourdf_amd import ops
+    from autourdf_amd.sim_data import SimEnv, angle_list, data_collection
+    path, _, _ = write_toy_robot(str(tmp_path / "robot"))
+    env = SimEnv(path, dof=3, radius=1.2, num_cameras=4)
+    a = angle_list(3, 4, 3, env.joint_limits, np.array([0.9] * 3), seed_i=0)
+    _, host = data_collection(env, angle_list=a, num_points=500, seed=1, occlusion=False)
+    _, host2 = data_collection(env, angle_list=a, num_points=500, seed=1, occlusion=False)
+    link_T = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows([env.set_joint_positions(c) for c in a]), env.base)
+    raw = str(tmp_path / "raw") + "/"
+    _, dev = data_collection(env, data_path=raw, angle_list=a, num_points=500, seed=1, occlusion=False, link_T=link_T)
+    for h, h2, d in zip(host, host2, dev):
+        np.testing.assert_array_equal(h.points, h2.points)
+        # farthest-point sampling picks by comparing distances: with poses 1e-13 apart it picks the same points unless two
+        # candidates tie to that precision, so compare as sets through the nearest neighbour
+        dist = np.linalg.norm(h.points[:, None] - d.points[None], axis=-1).min(1)
+        assert np.median(dist) <= 1e-12 and (dist <= 1e-12).mean() > 0.9
+    assert sorted(os.listdir(raw)) == ["0000", "0001", "0002"]
+
+
+# ------------------------------------------------------------------------------------------ compare_joints
+SHOULDER_SHIFT = np.array([0.01, -0.02, 0.005])
+SHOULDER_TURN = 0.1                                                      # radians about the joint frame's x
+
+
+def _write_variant(d, order=("wrist", "slide", "waist", "shoulder"), negate_wrist=True, move_shoulder=True, turn_shoulder=True,
+                   name="variant.urdf", finger=False):
+    """The toy rewritten next to its meshes: joints in another file order, the wrist axis negated, the shoulder origin moved by
+    SHOULDER_SHIFT, the shoulder axis turned by SHOULDER_TURN about x.  `finger`: a box on the tip link, off the wrist axis.
+    Returns (path, oracle-style joint dicts in the new order)."""
+    path, links, joints = write_toy_robot(str(d))
+    text = open(path).read()
+    joints = {j["name"]: dict(j) for j in joints}
+    if negate_wrist:
+        assert '<axis xyz="1 1 0"/>' in text
+        text = text.replace('<axis xyz="1 1 0"/>', '<axis xyz="-1 -1 0"/>')
+        joints["wrist"]["axis"] = [-1, -1, 0]
+    if move_shoulder:
+        xyz = np.array([0, 0, 0.2]) + SHOULDER_SHIFT
+        assert '<origin xyz="0 0 0.2" rpy="0.2 -0.1 0.4"/>' in text
+        text = text.replace('<origin xyz="0 0 0.2" rpy="0.2 -0.1 0.4"/>', '<origin xyz="%r %r %r" rpy="0.2 -0.1 0.4"/>' % tuple(float(v) for v in xyz))
+        joints["shoulder"]["xyz"] = list(xyz)
+    if turn_shoulder:
+        ax = [0.0, float(np.cos(SHOULDER_TURN)), float(np.sin(SHOULDER_TURN))]
+        assert '<axis xyz="0 1 0"/>' in text
+        text = text.replace('<axis xyz="0 1 0"/>', '<axis xyz="%r %r %r"/>' % tuple(ax))
+        joints["shoulder"]["axis"] = ax
+    if finger:
+        text = _add_finger(text)
+    head, tail = text.index("  <joint"), text.index("</robot>")
+    blocks = {b.split('"')[1]: "  <joint" + b for b in text[head:tail].split("  <joint")[1:]}
+    out = os.path.join(str(d), name)
+    with open(out, "w") as f:
+        f.write(text[:head] + "".join(blocks[n] for n in order) + text[tail:])
+    return out, links, [joints[n] for n in order]
+
+
+def _add_finger(text):
+    tip = '<link name="tip"><visual><geometry><sphere radius="0.015"/></geometry></visual>'
+    assert tip in text
+    return text.replace(tip, tip + '<visual><origin xyz="0.03 -0.03 0.02" rpy="0 0 0"/><geometry><box size="0.02 0.02 0.08"/></geometry></visual>')
+
+
+def test_compare_joints_toy_against_itself(tmp_path):
+    from autourdf_amd.evaluation import compare_joints
+    path, _, _ = write_toy_robot(str(tmp_path))
+    pos, ang, dmap = compare_joints(joint_map=np.arange(3), pred_urdf_path=path, gt_urdf_path=path, offset=np.zeros(3),
+                                    sim_ori=[0, 0, 0.3], pred_ori=[0, 0, 0.3], dof=3)
+    assert len(pos) == len(ang) == len(dmap) == 3 and dmap == [1, 1, 1]
+    assert np.abs(pos).max() <= POS_TOL and np.abs(ang).max() <= DIR_TOL_FLAT
+
+
+def test_compare_joints_on_a_rewritten_copy_with_known_differences(tmp_path):
+    from autourdf_amd.evaluation import compare_joints, joint_error
+    gt_path, links, gt_joints = write_toy_robot(str(tmp_path))
+    pred_path, _, pred_joints = _write_variant(tmp_path)
+    joint_map = np.array([1, 2, 0])                 # revolute joints: ground truth waist, shoulder, wrist; copy wrist, waist, shoulder
+    offset = np.array([0.3, -0.4, 0.5])
+    sim_ori, pred_ori = [0.0, 0.0, 0.3], [0.05, -0.03, 0.25]
+    pos, ang, dmap = compare_joints(joint_map=joint_map, pred_urdf_path=pred_path, gt_urdf_path=gt_path, offset=offset, sim_ori=sim_ori,
+                                    pred_ori=pred_ori, dof=3)
+    gt_lines = _oracle_lines(links, "base", gt_joints, dict(zip(["waist", "shoulder", "wrist"], offset)), _base(sim_ori))
+    pred_lines = _oracle_lines(links, "base", pred_joints, {}, _base(pred_ori))
+    assert dmap == [1, 1, -1]
+    for i, name in enumerate(["waist", "shoulder", "wrist"]):
+        want_pos, want_ang = joint_error(*pred_lines[name], *gt_lines[name])
+        if name == "wrist":
+            assert want_ang > 90
+            want_ang = 180 - want_ang
+        else:
+            assert want_ang < 90
+        print(name, "pos", pos[i], want_pos, "dir", ang[i], want_ang)
+        assert abs(pos[i] - want_pos) <= POS_TOL
+        assert abs(ang[i] - want_ang) <= _dir_tol(want_ang)
+    assert pos[1] > 1e-3 and ang[1] > 1.0             # the moved and turned shoulder is seen
+
+
+def test_compare_joints_refuses_a_dof_beyond_the_revolute_joints(tmp_path):
+    from autourdf_amd.evaluation import compare_joints
+    gt_path, _, _ = write_toy_robot(str(tmp_path))
+    pred_path, _, _ = _write_variant(tmp_path)
+    with pytest.raises(ValueError) as e:
+        compare_joints(joint_map=np.arange(4), pred_urdf_path=pred_path, gt_urdf_path=gt_path, offset=np.zeros(4), sim_ori=[0, 0, 0],
+                       pred_ori=[0, 0, 0], dof=4)
+    assert "4" in str(e.value) and "3" in str(e.value)
+
+
+# ------------------------------------------------------------------------------------------ evaluation end to end
+def _read_ply(path):
+    with open(path, "rb") as f:
+        raw = f.read()
+    head, body = raw.split(b"end_header\n", 1)
+    n = int([ln for ln in head.decode("ascii").splitlines() if ln.startswith("element vertex")][0].split()[-1])
+    return np.frombuffer(body, "<f8", count=3 * n).reshape(n, 3).copy()
+
+
+def _run_evaluation(save, pred, gt, direction_map, seed=11, num_points=2000):
+    from autourdf_amd.evaluation import evaluation
+    np.random.seed(seed)
+    return evaluation(pred_urdf_path=pred, gt_urdf_path=gt, dof=3, radius=1.2, num_cameras=8, gui=False, visualize=False,
+                      visualize_result=False, save_path=save, offset=np.zeros(3), sim_ori=[0, 0, 0.3], pred_ori=[0, 0, 0.3],
+                      joint_map=np.array([1, 2, 0]), direction_map=direction_map, num_points=num_points)
+
+
+def test_evaluation_end_to_end_on_the_toy_robot(tmp_path):
+    """Files, commands, clouds and losses of one evaluation() of the rewritten copy (other file order, axes restored apart from
+    the negated wrist, the shoulder origin still moved, so the losses are not trivially 0) against the toy; every loss against
+    the oracle's ICP filter + float32 Chamfer on the clouds the call wrote.
+
+    Discrimination.  The toy's tip link is a sphere centred on the wrist axis, so turning the wrist the wrong way leaves the
+    toy's surface where it was and no loss can see it.  The two discrimination runs therefore use the same two robots with
+    one box added to the tip link, off the wrist axis (same file order, same negated wrist, same commands and rings; the
+    shoulder origin restored as well, so the wrist is the only thing that can differ):
+    with `direction_map` all +1 -- wrong at the wrist -- the mean loss must be strictly larger.  No threshold."""
+    from oracle import chamfer as ochamfer, link as olink
+    gt, _, _ = write_toy_robot(str(tmp_path / "robot"))
+    pred, _, _ = _write_variant(tmp_path / "robot", move_shoulder=True, turn_shoulder=False)
+    save = str(tmp_path / "eval") + "/"
+    losses = _run_evaluation(save, pred, gt, [1, 1, -1])
+    for name in ("command_rad.txt", "command_deg.txt", "loss.txt", "loss_mean_std.txt"):
+        assert os.path.exists(save + name), name
+    rad, deg = np.loadtxt(save + "command_rad.txt"), np.loadtxt(save + "command_deg.txt")
+    np.random.seed(11)
+    np.testing.assert_allclose(rad, np.random.rand(3, 3) * 2 - 1, rtol=0, atol=1e-15)       # the first draw, (num_poses, dof), in [-1, 1)
+    np.testing.assert_allclose(deg, np.degrees(rad), rtol=1e-15, atol=0)
+    assert sorted(os.listdir(save + "pred")) == sorted(os.listdir(save + "gt")) == ["0000", "0001", "0002"]
+    on_disk = np.loadtxt(save + "loss.txt")
+    assert on_disk.shape == (3,) and len(losses) == 3
+    np.testing.assert_array_equal(on_disk, np.asarray(losses))            # savetxt's %.18e round-trips a double
+    for i in range(3):
+        p, g = _read_ply(save + f"pred/{i:04}/robot.ply"), _read_ply(save + f"gt/{i:04}/robot.ply")
+        assert p.shape == g.shape == (2000, 3)
+        _, moved = olink.icp_filter(p, g)
+        want = ochamfer.chamfer_distance(torch.tensor(moved, dtype=torch.float32)[None], torch.tensor(g, dtype=torch.float32)[None], norm=1)[0].item()
+        print("pose", i, "loss", on_disk[i], "oracle", want)
+        assert abs(on_disk[i] - want) <= 1e-6 * max(1.0, abs(want))
+    ms = np.loadtxt(save + "loss_mean_std.txt")
+    np.testing.assert_allclose(ms, [np.mean(on_disk), np.std(on_disk)], rtol=1e-15, atol=0)
+    # the ground truth was driven at the commands (offset 0), the copy at the mapped ones: the step files say so
+    cfg = [float(ln.split(":")[1]) for ln in open(save + "gt/0001/joint_cfg.txt")]
+    np.testing.assert_allclose(cfg, rad[1], atol=5e-7)                                       # waist, shoulder, wrist
+    cfg = [float(ln.split(":")[1]) for ln in open(save + "pred/0001/joint_cfg.txt")]
+    np.testing.assert_allclose(cfg, [-rad[1, 2], rad[1, 0], rad[1, 1]], atol=5e-7)           # wrist (negated), waist, shoulder
+
+    # discrimination, on the pair with a finger on the tip
+    fdir = tmp_path / "fingered"
+    gt_f = str(fdir / "toy_finger.urdf")
+    write_toy_robot(str(fdir))
+    with open(gt_f, "w") as f:
+        f.write(_add_finger(open(str(fdir / "toy.urdf")).read()))
+    pred_f, _, _ = _write_variant(fdir, move_shoulder=False, turn_shoulder=False, finger=True)
+    right = _run_evaluation(str(tmp_path / "eval_right") + "/", pred_f, gt_f, [1, 1, -1])
+    wrong = _run_evaluation(str(tmp_path / "eval_wrong") + "/", pred_f, gt_f, [1, 1, 1])
+    np.testing.assert_array_equal(np.loadtxt(str(tmp_path / "eval_right") + "/command_rad.txt"), np.loadtxt(str(tmp_path / "eval_wrong") + "/command_rad.txt"))
+    print("mean loss, right directions", np.mean(right), "wrong at the wrist", np.mean(wrong))
+    assert np.mean(wrong) > np.mean(right)
+
+
+# ------------------------------------------------------------------------------------------ main
+def test_main_writes_the_result_files(tmp_path, monkeypatch, capsys):
+    """main() in a directory laid out like the reference's: parameters.json, data/raw/... from sim_data.collect, the
+    ground truth under Robot/, the predicted URDF under data/urdf/.  The raw frames start at the mid-range pose, not at
+    zero, and a predicted URDF's zero pose IS the first frame: the predicted URDF here is the toy with the recorded
+    offset folded into its joint origins (origin * rotation(axis, offset)) -- the toy as a perfect pipeline would write it --
+    so the mean joint errors must be 0 within the tolerances."""
+    from autourdf_amd import evaluation as ev
+    from autourdf_amd.sim_data import collect
+    write_toy_robot(str(tmp_path / "Robot" / "toy"))
+    params = {"toy": {"num_seg": 4, "dof": 3, "gt": "Robot/toy/toy.urdf", "ori": [0, 0, 0.3], "sim_ori": [0, 0, 0.3], "cam_dist": 1.2}}
+    with open(tmp_path / "parameters.json", "w") as f:
+        json.dump(params, f)
+    collect("toy", params["toy"], num_step=2, step_size=4, epochs=1, num_points=600, root=str(tmp_path))
+    offset = ev.load_offset(str(tmp_path / "data/raw/toy/4_deg_20_cams") + "/")
+    assert offset.shape == (3,) and np.abs(offset[1:]).min() > 0.05          # shoulder and wrist do not start at zero
+    udir = tmp_path / "data" / "urdf" / "toy_4_seg"
+    path, _, joints = write_toy_robot(str(udir))
+    text = open(path).read()
+    for j, off in zip([j for j in joints if j["type"] == "revolute"], offset):
+        a = np.asarray(j["axis"], np.float64) / np.linalg.norm(j["axis"])
+        R = Rotation.from_euler("xyz", j["rpy"]) * Rotation.from_rotvec(a * off)
+        old = '<origin xyz="%s" rpy="%s"/>\n    <axis xyz="%s"/>' % tuple(" ".join("%g" % v for v in j[k]) for k in ("xyz", "rpy", "axis"))
+        assert text.count(old) == 1, old
+        text = text.replace(old, old.replace('rpy="%s"' % " ".join("%g" % v for v in j["rpy"]), 'rpy="%r %r %r"' % tuple(float(v) for v in R.as_euler("xyz"))))
+    with open(udir / "4_deg_20_cams.urdf", "w") as f:
+        f.write(text)
+    os.remove(path)
+    monkeypatch.chdir(tmp_path)
+    ev.main(["--robot", "toy", "--num_poses", "2", "--num_points", "1500", "--num_cameras_eval", "8"])
+    out = capsys.readouterr().out
+    assert "identity" in out and "Position error" in out and "Direction error" in out      # no Sim/joint_map/toy.txt here
+    res = tmp_path / "data/evaluation2/toy_4_seg/4_deg_20_cams"
+    for name in ("command_rad.txt", "command_deg.txt", "loss.txt", "loss_mean_std.txt", "pos_mean_std.txt", "dir_mean_std.txt"):
+        assert (res / name).exists(), name
+    np.random.seed(2024)
+    np.testing.assert_allclose(np.loadtxt(res / "command_rad.txt"), np.random.rand(2, 3) * 2 - 1, rtol=0, atol=1e-15)
+    assert np.loadtxt(res / "loss.txt").shape == (2,)
+    assert _read_ply(str(res / "pred/0001/robot.ply")).shape == (1500, 3) and _read_ply(str(res / "gt/0001/robot.ply")).shape == (1500, 3)
+    pos_ms, dir_ms = np.loadtxt(res / "pos_mean_std.txt"), np.loadtxt(res / "dir_mean_std.txt")
+    print("pos mean / std", pos_ms, "dir mean / std", dir_ms)
+    assert abs(pos_ms[0]) <= POS_TOL and abs(dir_ms[0]) <= DIR_TOL_FLAT
