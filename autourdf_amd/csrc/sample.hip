@@ -160,6 +160,24 @@ extern "C" int creg_visibility_f64(const double* tri, const int32_t* tri_link, i
     return CREG_OK;
 }
 
+// the clear and raster passes of creg_visibility_f64 on their own: the same two kernels, into the caller's (C,H,W) buffer
+// (a depth is a positive double, so its bit pattern in the unsigned buffer IS the double; untouched pixels hold +inf)
+extern "C" int creg_raster_depth_f64(const double* tri, const int32_t* tri_link, int32_t n_tri, const double* link_T, int32_t n_links,
+                                     const double* cams, int32_t n_cams, double fov_deg, double aspect, double near_val, double far_val,
+                                     int32_t width, int32_t height, double* depth, creg_stream_t stream) {
+    CREG_REQUIRE(tri && tri_link && link_T && cams && depth, "creg_raster_depth_f64: null pointer");
+    CREG_REQUIRE(n_tri >= 1 && n_links >= 1 && n_cams >= 1 && width >= 1 && height >= 1 && fov_deg > 0 && fov_deg < 180 &&
+                 near_val > 0 && far_val > near_val, "creg_raster_depth_f64: bad argument");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t npx = (size_t)n_cams * width * height;
+    CamParams c{tan(fov_deg * 3.14159265358979323846 / 360.0), aspect, near_val, far_val, width, height};
+    hipLaunchKernelGGL(k_depth_clear, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, s, (unsigned long long*)depth, npx);
+    hipLaunchKernelGGL(k_raster_depth, dim3(cdiv(n_tri, 256), n_cams), dim3(256), 0, s, tri, tri_link, (int)n_tri, (int)n_links, link_T, cams, c,
+                       (unsigned long long*)depth);
+    CREG_LAUNCH_CHECK();
+    return CREG_OK;
+}
+
 extern "C" int creg_sample_mesh_f64(const double* tri, const double* cum_area, const int32_t* tri_link, int32_t n_tri,
                                     const double* link_T, int32_t n_links, const double* u, int64_t n, double* out,
                                     int32_t* link_out, creg_stream_t stream) {

@@ -13,6 +13,11 @@ same farthest-point down-sampling to ``num_points`` (:346,349; ``creg_fps_f64``)
 geometry-faithful but include surfaces a camera ring would not see.  PyBullet, OpenGL and Open3D are not
 needed.  Mesh formats: STL (binary / ASCII) and OBJ; COLLADA visuals raise.  The sampling and the
 down-sampling have no CPU fallback.
+
+``data_collection(..., source="depth")`` builds the frames the reference's way instead: one depth buffer per camera,
+every pixel back-projected, the per-camera clouds fused (``SimEnv.depth_cloud``); with ``SimEnv(ground_flag=True)`` the
+robot stands on a ground plane that is removed per camera by RANSAC plane segmentation at the reference's parameters
+(``ops.segment_plane``: 0.001, 6, 1000; sim_data.py:311-319).
 """
 import os
 import struct
@@ -399,12 +404,27 @@ class UrdfRobot:
         return np.array([[float(q.get(n, 0.0)) for n in names] for q in q_by_joint_list], np.float64).reshape(-1, len(names))
 
 
+def ground_mesh(size, cells):
+    """(2 cells^2, 3, 3) triangles of a cells x cells grid of quads over [-size, size]^2 at z = 0.  Tessellated because the
+    rasteriser does not clip: it drops a facet with a vertex at or behind a camera's near plane, so one large quad would vanish
+    from every camera that stands over it, while small cells lose only a strip at the camera's feet."""
+    cells = int(cells)
+    if cells < 1 or not size > 0:
+        raise ValueError("ground_mesh: size > 0 and cells >= 1")
+    t = np.linspace(-float(size), float(size), cells + 1)
+    x0, y0 = (a.reshape(-1) for a in np.meshgrid(t[:-1], t[:-1], indexing="ij"))
+    x1, y1 = (a.reshape(-1) for a in np.meshgrid(t[1:], t[1:], indexing="ij"))
+    z = np.zeros_like(x0)
+    a, b, c, d = (np.stack(v, 1) for v in ((x0, y0, z), (x1, y0, z), (x1, y1, z), (x0, y1, z)))
+    return np.stack([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 1).reshape(-1, 3, 3)
+
+
 class SimEnv:
     """The part of the reference's SimEnv (sim_data.py:15-64) that describes the robot: revolute joints in URDF
     order with their limits (:66-82), the first ``dof`` of them driven, the rest parked at mid range (:131-157)."""
 
     def __init__(self, urdf_path, base_position=[0, 0, 0], base_orientation=[0, 0, 0], gui=False, dof=5,
-                 ground_flag=False, radius=1.5, num_cameras=3, global_scale=1.0, package_dirs=()):
+                 ground_flag=False, radius=1.5, num_cameras=3, global_scale=1.0, package_dirs=(), ground_size=None, ground_cells=32):
         if gui:
             raise NotImplementedError("gui=True needs PyBullet's viewer (out of scope)")
         self.dof = dof
@@ -417,7 +437,10 @@ class SimEnv:
         self.dof_list = self.joint_list[:dof]
         self.joint_limits = np.array([self.joint_params[j] for j in self.dof_list])
         self._dev = None
+        self._dev_raster = None
         self._setup_cameras(radius, num_cameras)
+        # the ground the reference stands its robot on (ground_flag): seen by the raster passes of depth_cloud only
+        self.ground_tri = ground_mesh(radius if ground_size is None else ground_size, ground_cells) if ground_flag else None
 
     def _setup_cameras(self, radius, num_cameras=20, cam_angle=20):
         """The reference's camera ring (sim_data.py:88-116): fewer than 20 cameras evenly on a circle at `cam_angle` degrees
@@ -460,6 +483,39 @@ class SimEnv:
                          torch.as_tensor(r.tri_link, device=d))
         return self._dev
 
+    def _raster_mesh(self):
+        """Device triangles the depth cameras see: the robot's and, with a ground, its cells on link index L (an identity pose
+        row appended to link_T)."""
+        if self._dev_raster is None:
+            tri, _, own = self._device_mesh()
+            if self.ground_tri is not None:
+                g = torch.as_tensor(self.ground_tri, device=tri.device)
+                tri = torch.cat([tri, g]).contiguous()
+                own = torch.cat([own, torch.full((g.shape[0],), len(self.robot.links), dtype=own.dtype, device=own.device)])
+            self._dev_raster = (tri, own)
+        return self._dev_raster
+
+    def depth_cloud(self, joint_positions, width=800, height=800, link_T=None, rng=None, remove_ground=True):
+        """The posed robot as the camera ring's depth images see it: one depth buffer per camera (creg_raster_depth_f64, with the
+        ground if the env has one), every finite pixel back-projected (creg_depth_points_f64) -> (points (M,3), offsets (C+1)),
+        camera c owning rows offsets[c]:offsets[c+1].  With a ground, each camera's cloud goes through ops.segment_plane at the
+        reference's parameters (0.001, 6, 1000; hypotheses drawn from ``rng``, a numpy Generator, default seed 0) and loses its
+        plane's inliers (``remove_ground=False`` keeps them)."""
+        tri, own = self._raster_mesh()
+        T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=tri.device) if link_T is None else link_T
+        if self.ground_tri is not None:
+            T = torch.cat([T, torch.eye(4, dtype=T.dtype, device=T.device)[None]])
+        cams = torch.as_tensor(self.cam_frames, device=tri.device)
+        c = self.cameras[0]
+        depth = ops.raster_depth(tri, own, T.contiguous(), cams, c['fov'], c['aspect'], c['near_val'], c['far_val'], width, height)
+        pts, off = ops.depth_points(depth, cams, c['fov'], c['aspect'])
+        if self.ground_tri is None or not remove_ground or pts.shape[0] == 0:
+            return pts, off
+        _, mask, _, _ = ops.segment_plane(pts, off, distance_threshold=0.001, ransac_n=6, num_iterations=1000,
+                                          rng=np.random.default_rng(0) if rng is None else rng)
+        gone = torch.cat([torch.zeros(1, dtype=torch.int64, device=pts.device), torch.cumsum(mask.to(torch.int64), 0)])
+        return pts[~mask], off - gone[off]
+
     def set_joint_positions(self, commands, manual_positions=0):
         """Joint name -> position: commanded for the driven joints, mid range (+ manual offset) for the others.
         (The reference reads the positions back from the physics step; here they are exact.)"""
@@ -479,6 +535,7 @@ class SimEnv:
 
     def reset(self):
         self._dev = None
+        self._dev_raster = None
 
 
 def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list):
@@ -498,7 +555,8 @@ def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list)
 
 
 def data_collection(env, data_path=None, width=800, height=800, visualize=False, angle_list=None, ground_flag=False,
-                    noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None):
+                    noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None,
+                    source="surface"):
     """One sequence: for every row of ``angle_list`` pose the robot, sample surface points, keep those that at least one
     camera of the ring sees (``occlusion``: depth buffers of ``width`` x ``height`` like the reference's rendered images,
     sim_data.py:286-306; more samples are drawn until ``oversample * num_points`` visible ones exist), add the
@@ -506,17 +564,31 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     sim_data.py:333-343), farthest-point down-sample to ``num_points`` (:346,349) and save.
     ``link_T`` (P,L,4,4), optional: device link poses of all rows at once (ops.urdf_fk); row ``jp_id`` poses step ``jp_id``
     in place of the host forward kinematics.
+    ``source="depth"`` takes the points the reference's way instead (sim_data.py:283-329): the fused back-projected depth
+    images of the camera ring at ``width`` x ``height`` (``SimEnv.depth_cloud``), so the density follows the pixels;
+    ``ground_flag=True`` then removes the ground per camera and needs an env built with ``ground_flag=True``.  Noise,
+    down-sampling and saving are the same; ``oversample`` and ``occlusion`` do not apply.  (``source="surface"`` ignores
+    ``ground_flag``.)
     Returns (collision=False, list of PointCloud) like the reference (self-collision checking is PyBullet's)."""
     if visualize:
         raise NotImplementedError("visualize=True needs Open3D's viewer (out of scope)")
+    if source not in ("surface", "depth"):
+        raise ValueError(f"data_collection: source must be 'surface' or 'depth', got {source!r}")
+    if source == "depth" and ground_flag and env.ground_tri is None:
+        raise ValueError("data_collection: ground_flag=True needs an env built with SimEnv(..., ground_flag=True)")
     rng = np.random.default_rng(seed)
     noise, record = [], []
     for jp_id, cmd in enumerate(np.asarray(angle_list)):
         q = env.set_joint_positions(cmd)
         want = oversample * num_points
         pose = {} if link_T is None else {"link_T": link_T[jp_id]}
-        pts = env.sample_surface(q, want, rng, **pose)
-        if occlusion:
+        if source == "depth":
+            pts, _ = env.depth_cloud(q, width, height, rng=rng, remove_ground=ground_flag, **pose)
+            if pts.shape[0] < num_points:
+                raise RuntimeError(f"only {pts.shape[0]} depth pixels of the camera ring hit the robot")
+        else:
+            pts = env.sample_surface(q, want, rng, **pose)
+        if occlusion and source == "surface":
             kept = pts[env.visible(q, pts, width, height, **pose)]
             draws = 1
             while kept.shape[0] < want and draws < 16:            # interior / hidden surfaces: draw until enough are visible
@@ -542,46 +614,66 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
 
 
 def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, noise=True, num_points=5000,
-            num_cameras=20, root="."):
+            num_cameras=20, root=".", source="surface", ground=False, pix=800):
     """`epochs` sequences of `num_step` frames under data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/
     -- the directory layout of the reference's collect() (sim_data.py:465-531), which match() globs
     (mlp_reg.py:424).  robot_params needs the reference's keys 'gt' (URDF path), 'dof' and optionally 'sim_ori'.
-    The self-collision rejection of seeds is PyBullet's and is not reproduced: seeds are 0..epochs-1."""
+    The self-collision rejection of seeds is PyBullet's and is not reproduced: seeds are 0..epochs-1.
+    ``source="depth"`` collects depth-camera frames of ``pix`` x ``pix`` images, ``ground`` stands the robot on the ground
+    plane and removes it per camera (the reference's --pix / --ground); the ground needs the depth source."""
+    if ground and source != "depth":
+        raise ValueError("collect: ground=True needs source='depth' (the surface sampler has no ground to remove)")
     paths = []
     for seed in range(epochs):
         data_path = os.path.join(root, f"data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/")
         os.makedirs(data_path, exist_ok=True)
         np.random.seed(seed)                                       # the ring of >= 20 cameras draws from the global state
         env = SimEnv(os.path.join(root, robot_params["gt"]), base_orientation=robot_params.get("sim_ori", [0, 0, 0]),
-                     dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras)
+                     dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras, ground_flag=ground)
         a_list = angle_list(num_step, step_size, robot_params["dof"], env.joint_limits, np.array([scale] * robot_params["dof"]), seed)
-        data_collection(env, data_path=data_path, angle_list=a_list, noise_flag=noise, num_points=num_points, seed=seed)
+        data_collection(env, data_path=data_path, width=pix, height=pix, angle_list=a_list, ground_flag=ground, noise_flag=noise,
+                        num_points=num_points, seed=seed, source=source)
         env.reset()
         paths.append(data_path)
     return paths
 
 
-def main(argv=None):
-    """python -m autourdf_amd.sim_data --robot wx200_5 [...]: the reference's flags (sim_data.py:537-551) minus the
-    rendering ones; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json."""
+def _parser():
     import argparse
-    import json
     ap = argparse.ArgumentParser()
     ap.add_argument('--robot', type=str, default='franka')
+    ap.add_argument('--pix', type=int, default=800, help="width and height of the depth buffers")
+    ap.add_argument('--depth', action='store_true', help="depth-camera frames (fused back-projected depth images) instead of surface samples")
+    ap.add_argument('--ground', action='store_true', help="stand the robot on a ground plane and remove it per camera (needs --depth)")
     ap.add_argument('--scale', type=float, default=0.9)
     ap.add_argument('--step_size', type=int, default=4)
     ap.add_argument('--num_step', type=int, default=10)
     ap.add_argument('--epoch', type=int, default=5)
     ap.add_argument('--no_noise', action='store_true')
     ap.add_argument('--num_points', type=int, default=5000)
-    ap.add_argument('--num_cameras', type=int, default=20, help="only names the output directory here")
+    ap.add_argument('--num_cameras', type=int, default=20)
+    return ap
+
+
+def parse_args(argv=None):
+    ap = _parser()
     args = ap.parse_args(argv)
+    if args.ground and not args.depth:
+        ap.error("--ground needs --depth: only the depth-camera frames have a ground to remove")
+    return args
+
+
+def main(argv=None):
+    """python -m autourdf_amd.sim_data --robot wx200_5 [...]: the reference's flags (sim_data.py:537-551) minus --gui / --vis,
+    plus --depth; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json."""
+    import json
+    args = parse_args(argv)
     with open('parameters.json') as f:
         params = json.load(f)[args.robot]
     if 'gt' not in params:
         raise SystemExit(f"parameters.json has no 'gt' URDF path for {args.robot!r} (use the reference's parameters.json)")
     for p in collect(args.robot, params, args.num_step, args.step_size, args.epoch, args.scale, not args.no_noise,
-                     args.num_points, args.num_cameras):
+                     args.num_points, args.num_cameras, source="depth" if args.depth else "surface", ground=args.ground, pix=args.pix):
         print(p)
 
 

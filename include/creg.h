@@ -434,6 +434,63 @@ int creg_visibility_f64(const double* tri, const int32_t* tri_link, int32_t n_tr
                         int32_t width, int32_t height, const double* pts, int64_t n, double eps, uint8_t* visible,
                         void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth-camera frames (Sim/sim_data.py:283-329: one depth image per camera, every pixel back-projected, the per-camera
+ * clouds fused; with a ground, Open3D's segment_plane removes it per camera, :311-319).
+ *
+ * creg_raster_depth_f64: the clear and raster passes of creg_visibility_f64 alone (the same kernels, no query points):
+ * depth (n_cams,height,width) fp64, linear depth along the view axis at the pixel centres, +inf where nothing was drawn. */
+int creg_raster_depth_f64(const double* tri, const int32_t* tri_link, int32_t n_tri, const double* link_T, int32_t n_links,
+                          const double* cams, int32_t n_cams, double fov_deg, double aspect, double near_val, double far_val,
+                          int32_t width, int32_t height, double* depth, creg_stream_t stream);
+/* Every finite pixel (c, y, x) of depth (n_cams,height,width) becomes one world point, the inverse of the projection above at
+ * the pixel centre:  nx = ((x + 0.5) / width - 0.5) * 2,  ny = ((1 - (y + 0.5) / height) - 0.5) * 2,
+ *   xc = nx * ((d * tan(fov / 2)) * aspect),  yc = ny * (d * tan(fov / 2)),
+ *   p = ((eye + d * forward) + xc * right) + yc * up      -- in exactly this order, no contraction.
+ * The rows are ordered camera-major, then row-major pixels: a count, an exclusive scan and a scatter, no atomics; the
+ * result is a pure function of the buffers.  Two calls, because the number of points is only known on the device:
+ *   creg_depth_points_count_f64 -> offsets (n_cams + 1) int64 on the device: camera c owns rows offsets[c]:offsets[c+1];
+ *                                  the per-block offsets stay in the workspace;
+ *   creg_depth_points_f64       -> points (capacity,3) fp64 from the SAME depth and workspace; capacity is the caller's
+ *                                  read of offsets[n_cams] (rows at or past capacity are dropped, never written).
+ * 1 <= n_cams <= 65535, width * height < 2^31.  workspace: creg_depth_points_workspace_bytes(n_cams, width, height). */
+size_t creg_depth_points_workspace_bytes(int32_t n_cams, int32_t width, int32_t height);
+int creg_depth_points_count_f64(const double* depth, int32_t n_cams, int32_t width, int32_t height, int64_t* offsets,
+                                void* workspace, size_t workspace_bytes, creg_stream_t stream);
+int creg_depth_points_f64(const double* depth, const double* cams, int32_t n_cams, double fov_deg, double aspect,
+                          int32_t width, int32_t height, const void* workspace, size_t workspace_bytes, double* points,
+                          int64_t capacity, creg_stream_t stream);
+/* Batched RANSAC plane segmentation (Open3D's PointCloud::segment_plane: distance_threshold, ransac_n, num_iterations) over
+ * n_segments segments of one packed cloud: points (n,3) fp64, offsets (n_segments + 1) int64, segment s = rows
+ * offsets[s]:offsets[s+1] (offsets outside [0, n] or running backwards are clamped).  samples (n_segments,n_hyp,ransac_n)
+ * int64: the hypotheses' point indices RELATIVE to their segment's start, drawn by the caller (the library draws no random
+ * numbers; an index may repeat within a hypothesis).  1 <= n < 2^31, n_hyp >= 1, 3 <= ransac_n <= 16, threshold > 0.
+ *   fit     per hypothesis the least-squares plane through its samples: centroid (sum in sample order / ransac_n) and the
+ *           unit eigenvector of the smallest eigenvalue of their scatter C (sums of centred products in sample order; the 3x3
+ *           solver of creg_knn_normals_f64), signed so that its component of largest magnitude is positive (ties: lowest
+ *           index); d = -((a cx + b cy) + c cz).
+ *           Rank test: a fit is INVALID when  e2(C) <= 1e-12 * trace(C)^2,  e2 = (C00 C11 - C01^2) + (C00 C22 - C02^2) +
+ *           (C11 C22 - C12^2) the sum of the principal 2x2 minors (= l0 l1 + l0 l2 + l1 l2 of the eigenvalues): the samples
+ *           deviate from one line by less than about 1e-6 of their extent -- all identical (C = 0), two distinct points,
+ *           exactly collinear ones (rounding leaves e2 / trace^2 near 1e-16).  Also invalid: an index outside the segment
+ *           (nothing is read), non-finite moments, a segment of fewer than ransac_n points.  An invalid hypothesis has a
+ *           plane of NaN and counts 0.
+ *   count   a point is an inlier when fabs(((a*x + b*y) + c*z) + d) < threshold, in this operation order; exact integers.
+ *   select  the valid hypothesis with the largest count, the smallest index among equals.
+ *   refit   the least-squares plane through the best hypothesis's inliers (centroid, then the scatter about it; fixed
+ *           reduction trees: two runs are identical), same sign rule.  If those inliers fail the rank test, or there are
+ *           none, the best hypothesis's own plane is returned.
+ * Outputs: plane (n_segments,4) the refit; mask (n) uint8 the inliers of the BEST HYPOTHESIS (not re-evaluated against the
+ * refit; 0 outside every segment); count (n_segments) int64 their number; best (n_segments) int32; hyp_planes
+ * (n_segments,n_hyp,4) fp64 and hyp_counts (n_segments,n_hyp) int32, either may be NULL.  A segment without a valid
+ * hypothesis (an empty one included) has count 0, best -1, a plane of zeros and no mask bits.  No early termination: all
+ * n_hyp hypotheses are always evaluated.  workspace: creg_segment_plane_workspace_bytes(n, n_segments, n_hyp). */
+size_t creg_segment_plane_workspace_bytes(int64_t n, int32_t n_segments, int32_t n_hyp);
+int creg_segment_plane_f64(const double* points, int64_t n, const int64_t* offsets, int32_t n_segments, const int64_t* samples,
+                           int32_t n_hyp, int32_t ransac_n, double threshold, double* plane, uint8_t* mask, int64_t* count,
+                           int32_t* best, double* hyp_planes, int32_t* hyp_counts, void* workspace, size_t workspace_bytes,
+                           creg_stream_t stream);
+
 /* Batched forward kinematics of a URDF joint table: every link pose of n_poses joint states in one launch (the evaluation
  * stage, Sim/evaluation.py:84-224 and :228-310, where PyBullet poses the robots one state at a time).
  * The table is in TOPOLOGICAL order -- a joint's parent link is `root` or the child of an earlier joint -- and holds, per
