@@ -1892,18 +1892,17 @@ static int icp_large_run(const creg_icp_problem& q, int64_t n, int32_t k, int64_
     //  overwrite the new call's counters, typically with "0 clusters running", and end its iteration loop early)
     if (!h_run) CREG_HIP(hipHostMalloc((void**)&h_run, sizeof(int) * 2 * ICP_LAG_RING, hipHostMallocPortable));
     if (h_last) { (void)hipEventSynchronize(h_last); (void)hipEventDestroy(h_last); h_last = nullptr; }
-    hipEvent_t ev[ICP_LAG_RING];
-    for (auto& e : ev) CREG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    std::vector<hipEvent_t> tev;                                      // (timing mode only)
+    ScopedEvents ev(ICP_LAG_RING), tev;                              // (tev: timing mode only)
+    for (auto& e : ev.v) CREG_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     int grid = nblk, rc_loop = CREG_OK;                              // live chunks as of the last batch whose counters were read
     bool converged = false;
     int64_t done = 0;
     for (int b = 0; !converged && done <= (int64_t)max_iteration; ++b) {
         const int batch = 16;
         for (int q = 0; q < batch; ++q, ++done) {
-            if (g_icp_nn_timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); tev.push_back(e); } }
+            if (g_icp_nn_timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); tev.v.push_back(e); } }
             hipLaunchKernelGGL(k_icp_nn, dim3(grid), dim3(64 * ICP_NNW), nn_smem, s, P, (int)n, k, (int)nf, th * th, max_iteration);
-            if (g_icp_nn_timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); tev.push_back(e); } }
+            if (g_icp_nn_timing) { hipEvent_t e; if (hipEventCreate(&e) == hipSuccess) { (void)hipEventRecord(e, s); tev.v.push_back(e); } }
 #ifdef CREG_STAMPS
             hipLaunchKernelGGL(k_icp_wall_fold, dim3(1), dim3(1), 0, s);
 #endif
@@ -1920,23 +1919,19 @@ static int icp_large_run(const creg_icp_problem& q, int64_t n, int32_t k, int64_
             grid = r[1] > 0 ? r[1] : 1;
         }
     }
-    if (rc_loop == CREG_OK && !converged) {                          // the last batch's counters (max_iteration reached, or one batch only)
-        // nothing to decide any more: k_icp_finish reads the device state
-    }
-    for (auto& e : ev) (void)hipEventDestroy(e);
+    // (the last batch's counters are not read: nothing is left to decide, k_icp_finish reads the device state)
     if (hipEventCreateWithFlags(&h_last, hipEventDisableTiming) == hipSuccess) {
         if (hipEventRecord(h_last, s) != hipSuccess) { (void)hipEventDestroy(h_last); h_last = nullptr; (void)hipStreamSynchronize(s); }
     } else { h_last = nullptr; (void)hipStreamSynchronize(s); }
     if (rc_loop != CREG_OK) { set_error("creg_masked_icp: HIP error in the iteration loop: %s", hipGetErrorString(hipGetLastError())); return rc_loop; }
     hipLaunchKernelGGL(k_icp_finish, dim3(k), dim3(256), 0, s, P, keep_translation);
     CREG_LAUNCH_CHECK();
-    if (!tev.empty()) {
+    if (!tev.v.empty()) {
         (void)hipStreamSynchronize(s);
-        for (size_t i = 0; i + 1 < tev.size(); i += 2) {
+        for (size_t i = 0; i + 1 < tev.v.size(); i += 2) {
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, tev[i], tev[i + 1]) == hipSuccess) { g_icp_nn_us += 1e3 * ms; ++g_icp_nn_launches; }
         }
-        for (auto e : tev) (void)hipEventDestroy(e);
     }
     return CREG_OK;
 }

@@ -1434,7 +1434,6 @@ struct Plan {
     bool graph_ready;
     int graph_epochs;
     int B;                    // problems the workspace holds
-    int nz;                   // problems per launch right now (grid.z): B for run, 1 for probe / profile
     size_t bstride;           // bytes between consecutive problems' workspaces
     int smem_bd;
     int branches;             // parallel chains in the captured graph (groups of problems)
@@ -1451,6 +1450,15 @@ struct Plan {
                               //   take a stream that shares a hardware queue; 0: not probed (one chain, or the probe is switched off)
     bool target_blocks_valid; // ys4 / ybox hold the k-d leaves of every problem's last run_batch frame (probe / profile overwrite them)
 };
+
+// The problems one launch covers: the first one's workspace and how many follow it, bstride apart (the launch's grid.z).
+struct Slice { Ws W; int nz; };
+static Slice slice_of(const Plan* P, int first, int count) { return Slice{ws_shift(P->W, (size_t)first * P->bstride), count}; }
+// chain gi of P->branches: contiguous groups of B / branches problems, the first B % branches of them one larger
+static Slice chain_slice(const Plan* P, int gi) {
+    const int q = P->B / P->branches, r = P->B % P->branches;
+    return slice_of(P, gi * q + (gi < r ? gi : r), q + (gi < r ? 1 : 0));
+}
 
 static bool make_dims(const creg_train_shape* s, Dims* D) {
     if (!s || s->rot < 0 || s->rot > 3 || s->k < 1 || s->k > 256 || (s->hidden != 64 && s->hidden != 128 && s->hidden != 256 && s->hidden != 512) || s->epochs < 1 || s->n_pred < 1 || s->n_tgt < 1 || s->n_pred >= (1ll << 31) ||
@@ -1541,16 +1549,16 @@ static void by_nc(int H, F f) {            // H in {64, 128, 256, 512}
         default: f(std::integral_constant<int, 8>{}); break;
     }
 }
-static void launch_l2(Plan* P, int par, hipStream_t s) {
-    const Dims& D = P->D; const Ws& W = P->W;
+static void launch_l2(const Plan* P, const Slice& S, int par, hipStream_t s) {
+    const Dims& D = P->D;
     by_nc(D.H, [&](auto nc) {
-        hipLaunchKernelGGL((k_l2<decltype(nc)::value>), dim3(D.H2 / 16, 1, P->nz), dim3(L2_THREADS), 0, s, D, W, par, P->bstride); });
+        hipLaunchKernelGGL((k_l2<decltype(nc)::value>), dim3(D.H2 / 16, 1, S.nz), dim3(L2_THREADS), 0, s, D, S.W, par, P->bstride); });
 }
-static void launch_head(Plan* P, int par, hipStream_t s) {
-    const Dims& D = P->D; const Ws& W = P->W;
+static void launch_head(const Plan* P, const Slice& S, int par, hipStream_t s) {
+    const Dims& D = P->D;
     by_nc(D.H, [&](auto nc) {
-        if (D.OA + D.OB > 8) hipLaunchKernelGGL((k_head<decltype(nc)::value, true>), dim3(D.K, 1, P->nz), dim3(512), 0, s, D, W, par, P->bstride);
-        else hipLaunchKernelGGL((k_head<decltype(nc)::value>), dim3(D.K, 1, P->nz), dim3(512), 0, s, D, W, par, P->bstride);
+        if (D.OA + D.OB > 8) hipLaunchKernelGGL((k_head<decltype(nc)::value, true>), dim3(D.K, 1, S.nz), dim3(512), 0, s, D, S.W, par, P->bstride);
+        else hipLaunchKernelGGL((k_head<decltype(nc)::value>), dim3(D.K, 1, S.nz), dim3(512), 0, s, D, S.W, par, P->bstride);
     });
 }
 // the k_bd instance of a shape: NC = H / 64; the B role's 8 waves own KW = H2 / 8 rows of W2 each ('q': H2 = 96 NC, 'dq': 64 NC)
@@ -1563,10 +1571,10 @@ static void by_bd(const Dims& D, F f) {
         else f(k_bd<NC, 8 * NC>);
     });
 }
-static void launch_bd(Plan* P, int epoch, hipStream_t s) {
-    const Dims& D = P->D; const Ws& W = P->W;
+static void launch_bd(const Plan* P, const Slice& S, int epoch, hipStream_t s) {
+    const Dims& D = P->D;
     const int per = D.H / B2_CB + dw_blocks(D);
-    by_bd(D, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(per * P->nz), dim3(BD_THREADS), P->smem_bd, s, D, W, epoch, P->bstride, P->nz); });
+    by_bd(D, [&](auto kern) { hipLaunchKernelGGL(kern, dim3(per * S.nz), dim3(BD_THREADS), P->smem_bd, s, D, S.W, epoch, P->bstride, S.nz); });
 }
 static void launch_nn(const Dims& D, const Ws& W, size_t bstride, int nz, hipStream_t s, int par = 0) {
     const EngineEpi epi{W.sgn_x, W.cnt4, W.lossp_x, W.lossp_y, bstride, &W.state[par].stopped};
@@ -1631,16 +1639,16 @@ constexpr int NKERN = 5;
 // `ev` (optional): NKERN + 1 events recorded before kernel 0 and after each kernel.
 // Entering epoch e, x1[e & 1] and h2[e & 1] hold the activations of the current parameters (k_l1 / k_l2 for epoch 0,
 // k_bd's B role / k_l2 of the previous epoch afterwards).
-static void enqueue_epoch(Plan* P, int epoch, hipStream_t s, hipEvent_t* ev = nullptr) {
-    const Dims& D = P->D; const Ws& W = P->W;
+static void enqueue_epoch(const Plan* P, const Slice& S, int epoch, hipStream_t s, hipEvent_t* ev = nullptr) {
+    const Dims& D = P->D;
     const int par = epoch & 1;
     auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], s); };
     mark(0);
-    launch_head(P, par, s); mark(1);
-    launch_nn(D, W, P->bstride, P->nz, s, par); mark(2);
-    hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, P->nz), dim3(256), 0, s, D, W, epoch, D.nbx, D.nby, P->bstride); mark(3);
-    launch_bd(P, epoch, s); mark(4);
-    launch_l2(P, par ^ 1, s); mark(5);        // the next epoch's hidden activation: next encoder activation (B) x updated hidden rows (D)
+    launch_head(P, S, par, s); mark(1);
+    launch_nn(D, S.W, P->bstride, S.nz, s, par); mark(2);
+    hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, S.nz), dim3(256), 0, s, D, S.W, epoch, D.nbx, D.nby, P->bstride); mark(3);
+    launch_bd(P, S, epoch, s); mark(4);
+    launch_l2(P, S, par ^ 1, s); mark(5);        // the next epoch's hidden activation: next encoder activation (B) x updated hidden rows (D)
 }
 
 // One launch copies up to 16 (source, destination, dword count) ranges: a problem's 10 parameter tensors + offsets in,
@@ -1686,24 +1694,25 @@ static int ps_sort_smem(const Dims& D) {       // a cluster can hold every point
     const int np = pow2_at_least((D.NP + BS - 1) / BS * BS);
     return (np < YS_CHUNK ? np : YS_CHUNK) * 8;
 }
-static void launch_sorts(Plan* P, hipStream_t s, int nz, bool keep_target_blocks = false) {
+static void launch_sorts(const Plan* P, const Slice& S, hipStream_t s, bool keep_target_blocks = false) {
     const Dims& D = P->D;
     // (keep_target_blocks: the launch only verifies the caller's claim -- see k_sort_y)
-    if (D.nyb) hipLaunchKernelGGL(k_sort_y, dim3(cdiv(D.NT, YS_CHUNK), 1, nz), dim3(1024), ys_sort_smem(D), s, D, P->W, P->bstride, ys_sort_npow(D), keep_target_blocks ? 1 : 0);
-    if (D.npb) hipLaunchKernelGGL(k_sort_p, dim3(D.K, 1, nz), dim3(512), ps_sort_smem(D), s, D, P->W, P->bstride);
+    if (D.nyb) hipLaunchKernelGGL(k_sort_y, dim3(cdiv(D.NT, YS_CHUNK), 1, S.nz), dim3(1024), ys_sort_smem(D), s, D, S.W, P->bstride, ys_sort_npow(D), keep_target_blocks ? 1 : 0);
+    if (D.npb) hipLaunchKernelGGL(k_sort_p, dim3(D.K, 1, S.nz), dim3(512), ps_sort_smem(D), s, D, S.W, P->bstride);
 }
 
-// Inputs of `n` problems into their workspaces: the parameter / offset copies of all of them in one launch (per
+// Inputs of the slice's problems into their workspaces: the parameter / offset copies of all of them in one launch (per
 // COPY_MAX ranges), then one k_prep and one k_l1 launch with the problems in grid.z.
-static int stage_inputs(Plan* P, const creg_train_args* args, int n, hipStream_t s) {
+static int stage_inputs(const Plan* P, const Slice& S, const creg_train_args* args, hipStream_t s) {
     const Dims& D = P->D;
+    const int n = S.nz;
     ParamMap pm[10];
     const int np = param_map(D, pm);
     CopyTable T; T.count = 0;
     PrepBatch pb;
     for (int b = 0; b < n; ++b) {
         const creg_train_args* a = args + b;
-        const Ws W = ws_shift(P->W, (size_t)b * P->bstride);
+        const Ws W = ws_shift(S.W, (size_t)b * P->bstride);
         for (int i = 0; i < np; ++i) {
             CREG_REQUIRE(a->params[i], "creg_train: params[%d] of problem %d is null", i, b);
             copy_table_add(T, a->params[i], W.P + pm[i].off, sizeof(float) * pm[i].count, s);
@@ -1716,14 +1725,9 @@ static int stage_inputs(Plan* P, const creg_train_args* args, int n, hipStream_t
     const int mx = D.NP > D.NT ? D.NP : D.NT;
     int blocks = cdiv(mx > D.NPAR ? mx : D.NPAR, 256);
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_prep, dim3(blocks, 1, n), dim3(256), 0, s, D, P->W, P->bstride, pb);
-    hipLaunchKernelGGL(k_l1, dim3(cdiv(D.H, 4), 1, n), dim3(256), 0, s, D, P->W, 0, P->bstride);
-    {   // the first epoch's hidden activation (later ones: the k_l2 launch that ends every epoch)
-        const int nz_keep = P->nz;
-        P->nz = n;
-        launch_l2(P, 0, s);
-        P->nz = nz_keep;
-    }
+    hipLaunchKernelGGL(k_prep, dim3(blocks, 1, n), dim3(256), 0, s, D, S.W, P->bstride, pb);
+    hipLaunchKernelGGL(k_l1, dim3(cdiv(D.H, 4), 1, n), dim3(256), 0, s, D, S.W, 0, P->bstride);
+    launch_l2(P, S, 0, s);      // the first epoch's hidden activation (later ones: the k_l2 launch that ends every epoch)
     CREG_LAUNCH_CHECK();
     return CREG_OK;
 }
@@ -1732,66 +1736,49 @@ static int stage_inputs(Plan* P, const creg_train_args* args, int n, hipStream_t
 using namespace creg;
 
 // EPG consecutive epochs captured as one graph (G independent branches over contiguous groups of problems).  On any
-// failure the capture is ended, and every stream / event / graph created here is destroyed before returning.
+// failure the capture is ended; every stream / event / graph created here is released when the function returns.
 static int capture_epochs(Plan* P, int epg) {
     // captured on a private stream (torch's current stream is usually the null stream, which cannot be captured); the
     // instantiated graph is then launched on the caller's stream.
     const int G = P->branches;
-    hipStream_t cs = nullptr, cs2[16] = {nullptr};
-    hipEvent_t ef = nullptr, ej[16] = {nullptr};
-    hipGraph_t g = nullptr;
-    bool capturing = false;
-    const Ws Wall = P->W;
-    const int nz_all = P->nz;
-    hipError_t err = hipSuccess;
-    const char* what = "";
-#define CAP_TRY(call) do { if (err == hipSuccess) { err = (call); if (err != hipSuccess) what = #call; } } while (0)
-    CAP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    CAP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    capturing = err == hipSuccess;
+    ScopedStream cs, cs2[16];
+    ScopedEvents ev(16);                                     // [0]: the fork, [gi]: the join of branch gi
+    hipEvent_t& ef = ev[0];
+    hipEvent_t* ej = ev.v.data();
+    ScopedGraph g;
+    FirstError fe;
+    CREG_TRY(fe, hipStreamCreateWithFlags(&cs.h, hipStreamNonBlocking));
+    CREG_TRY(fe, hipStreamBeginCapture(cs.h, hipStreamCaptureModeThreadLocal));
+    const bool capturing = fe.ok();
     if (G > 1) {
         // fork / join through events, so the instantiated graph has parallel chains: the runtime feeds them to
         // different hardware queues and the latency-bound kernels of one group overlap the long launches of the
         // other.  Problems never interact, so results do not depend on G (stress-tested: tests/test_gpu_parity.py).
-        CAP_TRY(hipEventCreateWithFlags(&ef, hipEventDisableTiming));
-        CAP_TRY(hipEventRecord(ef, cs));
-        int first = 0;
-        for (int gi = 0; gi < G && err == hipSuccess; ++gi) {
-            const int cnt = P->B / G + (gi < P->B % G ? 1 : 0);
-            hipStream_t st = cs;
-            if (gi > 0) {
-                CAP_TRY(hipStreamCreateWithFlags(&cs2[gi], hipStreamNonBlocking));
-                CAP_TRY(hipStreamWaitEvent(cs2[gi], ef, 0));
-                st = cs2[gi];
-            }
-            if (err != hipSuccess) break;
-            P->W = ws_shift(Wall, (size_t)first * P->bstride); P->nz = cnt;
-            for (int i = 0; i < epg; ++i) enqueue_epoch(P, i, st);
-            if (gi > 0) {
-                CAP_TRY(hipEventCreateWithFlags(&ej[gi], hipEventDisableTiming));
-                CAP_TRY(hipEventRecord(ej[gi], st));
-            }
-            first += cnt;
+        CREG_TRY(fe, hipEventCreateWithFlags(&ef, hipEventDisableTiming));
+        CREG_TRY(fe, hipEventRecord(ef, cs.h));
+    }
+    for (int gi = 0; gi < G && fe.ok(); ++gi) {
+        hipStream_t st = cs.h;
+        if (gi > 0) {
+            CREG_TRY(fe, hipStreamCreateWithFlags(&cs2[gi].h, hipStreamNonBlocking));
+            CREG_TRY(fe, hipStreamWaitEvent(cs2[gi].h, ef, 0));
+            st = cs2[gi].h;
         }
-        P->W = Wall; P->nz = nz_all;
-        for (int gi = 1; gi < G; ++gi) if (ej[gi]) CAP_TRY(hipStreamWaitEvent(cs, ej[gi], 0));
-    } else {
-        if (err == hipSuccess) for (int i = 0; i < epg; ++i) enqueue_epoch(P, i, cs);
+        if (!fe.ok()) break;
+        const Slice S = chain_slice(P, gi);
+        for (int i = 0; i < epg; ++i) enqueue_epoch(P, S, i, st);
+        if (gi > 0) {
+            CREG_TRY(fe, hipEventCreateWithFlags(&ej[gi], hipEventDisableTiming));
+            CREG_TRY(fe, hipEventRecord(ej[gi], st));
+        }
     }
-    if (capturing) {
-        const hipError_t e2 = hipStreamEndCapture(cs, &g);          // always end the capture, also after a failure
-        if (err == hipSuccess && e2 != hipSuccess) { err = e2; what = "hipStreamEndCapture"; }
-    }
-    CAP_TRY(hipGraphInstantiate(&P->gexec, g, nullptr, nullptr, 0));
-#undef CAP_TRY
-    if (g) (void)hipGraphDestroy(g);
-    for (int gi = 1; gi < 16; ++gi) { if (cs2[gi]) (void)hipStreamDestroy(cs2[gi]); if (ej[gi]) (void)hipEventDestroy(ej[gi]); }
-    if (ef) (void)hipEventDestroy(ef);
-    if (cs) (void)hipStreamDestroy(cs);
-    if (err != hipSuccess) {
+    for (int gi = 1; gi < G; ++gi) if (ej[gi]) CREG_TRY(fe, hipStreamWaitEvent(cs.h, ej[gi], 0));
+    if (capturing) fe.note(hipStreamEndCapture(cs.h, &g.h), "hipStreamEndCapture");      // always end the capture, also after a failure
+    CREG_TRY(fe, hipGraphInstantiate(&P->gexec, g.h, nullptr, nullptr, 0));
+    if (!fe.ok()) {
         (void)hipGetLastError();
         if (P->gexec) { (void)hipGraphExecDestroy(P->gexec); P->gexec = nullptr; }
-        creg::set_error("creg_train_plan_run_batch: graph capture failed: %s: %s", what, hipGetErrorString(err));
+        creg::set_error("creg_train_plan_run_batch: graph capture failed: %s: %s", fe.what, hipGetErrorString(fe.err));
         return CREG_EHIP;
     }
     P->graph_ready = true;
@@ -1867,38 +1854,27 @@ static int pick_chain_streams(Plan* P, hipStream_t s) {
 }
 
 // chain-stream mode: chain gi's EPG epochs as a linear graph (captured on a temporary stream: an instantiated graph runs on any)
-static int chain_first(const Plan* P, int gi) { int f = 0; for (int i = 0; i < gi; ++i) f += P->B / P->branches + (i < P->B % P->branches ? 1 : 0); return f; }
-static int chain_count(const Plan* P, int gi) { return P->B / P->branches + (gi < P->B % P->branches ? 1 : 0); }
 static int capture_chains(Plan* P, int epg) {
-    const Ws Wall = P->W;
-    const int nz_all = P->nz;
-    hipError_t err = hipSuccess;
-    const char* what = "";
-#define CAP_TRY(call) do { if (err == hipSuccess) { err = (call); if (err != hipSuccess) what = #call; } } while (0)
-    if (!P->cfork) CAP_TRY(hipEventCreateWithFlags(&P->cfork, hipEventDisableTiming));
-    hipStream_t cs = nullptr;
-    CAP_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    for (int gi = 0; gi < P->branches && err == hipSuccess; ++gi) {
-        hipGraph_t g = nullptr;
-        if (gi > 0 && !P->cjoin[gi]) CAP_TRY(hipEventCreateWithFlags(&P->cjoin[gi], hipEventDisableTiming));
+    FirstError fe;
+    if (!P->cfork) CREG_TRY(fe, hipEventCreateWithFlags(&P->cfork, hipEventDisableTiming));
+    ScopedStream cs;
+    CREG_TRY(fe, hipStreamCreateWithFlags(&cs.h, hipStreamNonBlocking));
+    for (int gi = 0; gi < P->branches && fe.ok(); ++gi) {
+        ScopedGraph g;
+        if (gi > 0 && !P->cjoin[gi]) CREG_TRY(fe, hipEventCreateWithFlags(&P->cjoin[gi], hipEventDisableTiming));
         if (P->cexec[gi]) { (void)hipGraphExecDestroy(P->cexec[gi]); P->cexec[gi] = nullptr; }      // (a retry after a failed capture)
-        CAP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        if (err == hipSuccess) {
-            P->W = ws_shift(Wall, (size_t)chain_first(P, gi) * P->bstride); P->nz = chain_count(P, gi);
-            for (int i = 0; i < epg; ++i) enqueue_epoch(P, i, cs);
-            P->W = Wall; P->nz = nz_all;
-            const hipError_t e2 = hipStreamEndCapture(cs, &g);
-            if (e2 != hipSuccess) { err = e2; what = "hipStreamEndCapture"; }
+        CREG_TRY(fe, hipStreamBeginCapture(cs.h, hipStreamCaptureModeThreadLocal));
+        if (fe.ok()) {
+            const Slice S = chain_slice(P, gi);
+            for (int i = 0; i < epg; ++i) enqueue_epoch(P, S, i, cs.h);
+            fe.note(hipStreamEndCapture(cs.h, &g.h), "hipStreamEndCapture");
         }
-        CAP_TRY(hipGraphInstantiate(&P->cexec[gi], g, nullptr, nullptr, 0));
-        if (g) (void)hipGraphDestroy(g);
+        CREG_TRY(fe, hipGraphInstantiate(&P->cexec[gi], g.h, nullptr, nullptr, 0));
     }
-    if (cs) (void)hipStreamDestroy(cs);
-#undef CAP_TRY
-    if (err != hipSuccess) {
+    if (!fe.ok()) {
         (void)hipGetLastError();
         for (int gi = 0; gi < 8; ++gi) if (P->cexec[gi]) { (void)hipGraphExecDestroy(P->cexec[gi]); P->cexec[gi] = nullptr; }
-        creg::set_error("creg_train_plan_run_batch: chain graph capture failed: %s: %s", what, hipGetErrorString(err));
+        creg::set_error("creg_train_plan_run_batch: chain graph capture failed: %s: %s", fe.what, hipGetErrorString(fe.err));
         return CREG_EHIP;
     }
     P->graph_ready = true;
@@ -1926,7 +1902,7 @@ extern "C" int creg_train_plan_create(const creg_train_shape* shape, void* works
     Plan* P = new Plan();
     P->shape = *shape; P->D = D; P->base = (char*)workspace; P->bytes = workspace_bytes;
     carve(D, P->base, &P->W);
-    P->B = batch_of(shape); P->nz = P->B; P->bstride = one;
+    P->B = batch_of(shape); P->bstride = one;
     // How the problems of a batch share the GPU (round 4, profiles/r04_chains_by_batch.log; bench.py --graph-branches):
     //   graph_branches < 0: -n CHAIN STREAMS -- the batch is cut into n contiguous groups, every group's epochs are a LINEAR graph
     //     (replayed from pre-built packets: 0.6-1.2 ms of host time per 300-epoch train) on its own stream; chain 0 uses the
@@ -1977,17 +1953,14 @@ extern "C" int creg_train_plan_run_batch(creg_train_plan* plan, const creg_train
         CREG_REQUIRE(a->m && a->y && a->local_pts && a->seg_offsets && a->params && a->best_m && a->best_pred && a->result,
                      "creg_train_plan_run_batch: null pointer in problem %d", b);
     }
-    {
-        int rc = stage_inputs(P, args, n, s);
-        if (rc) return rc;
-    }
+    const Slice all = slice_of(P, 0, P->B);
+    if (int rc = stage_inputs(P, all, args, s)) return rc;
     {   // the target frame's k-d leaves survive from the previous run when the caller vouches for every problem's frame
         bool keep = P->target_blocks_valid;
         for (int b = 0; b < n; ++b) keep = keep && args[b].y_unchanged != 0;
-        launch_sorts(P, s, P->B, keep);
+        launch_sorts(P, all, s, keep);
         P->target_blocks_valid = true;
     }
-    P->nz = P->B;
     int e = 0;
     if (P->shape.use_graph && D.epochs >= 2) {
         // One graph holds EPG consecutive epochs (even count: the epoch number enters the kernels only
@@ -2009,33 +1982,28 @@ extern "C" int creg_train_plan_run_batch(creg_train_plan* plan, const creg_train
                 const int rc = pick_chain_streams(P, s);           // streams in hardware queues of their own (measured, see there)
                 if (rc) { P->target_blocks_valid = false; return rc; }
             }
-            const Ws Wall = P->W;
             auto st_of = [&](int gi) { return gi == 0 ? s : P->cst[gi]; };
-            hipError_t cerr = hipSuccess;
-            const char* cwhat = "";
-#define CH_TRY(call) do { if (cerr == hipSuccess) { cerr = (call); if (cerr != hipSuccess) cwhat = #call; } } while (0)
-            CH_TRY(hipEventRecord(P->cfork, s));
-            for (int gi = 1; gi < P->branches; ++gi) CH_TRY(hipStreamWaitEvent(P->cst[gi], P->cfork, 0));
-            for (; cerr == hipSuccess && e + P->graph_epochs <= D.epochs; e += P->graph_epochs)
-                for (int gi = 0; gi < P->branches; ++gi) CH_TRY(hipGraphLaunch(P->cexec[gi], st_of(gi)));
-            for (int gi = 0; cerr == hipSuccess && gi < P->branches; ++gi) {
-                P->W = ws_shift(Wall, (size_t)chain_first(P, gi) * P->bstride); P->nz = chain_count(P, gi);
-                for (int e2 = e; e2 < D.epochs; ++e2) enqueue_epoch(P, e2, st_of(gi));
-                P->W = Wall; P->nz = P->B;
+            FirstError fe;
+            CREG_TRY(fe, hipEventRecord(P->cfork, s));
+            for (int gi = 1; gi < P->branches; ++gi) CREG_TRY(fe, hipStreamWaitEvent(P->cst[gi], P->cfork, 0));
+            for (; fe.ok() && e + P->graph_epochs <= D.epochs; e += P->graph_epochs)
+                for (int gi = 0; gi < P->branches; ++gi) CREG_TRY(fe, hipGraphLaunch(P->cexec[gi], st_of(gi)));
+            for (int gi = 0; fe.ok() && gi < P->branches; ++gi) {
+                const Slice S = chain_slice(P, gi);
+                for (int e2 = e; e2 < D.epochs; ++e2) enqueue_epoch(P, S, e2, st_of(gi));
             }
             // the join is enqueued ALSO after a failure: chains that did start must not be left running on the workspace, un-joined,
             // beside whatever the caller does next (a retry would stage inputs under them)
             for (int gi = 1; gi < P->branches; ++gi) {
                 if (hipEventRecord(P->cjoin[gi], P->cst[gi]) != hipSuccess || hipStreamWaitEvent(s, P->cjoin[gi], 0) != hipSuccess) {
                     (void)hipStreamSynchronize(P->cst[gi]);
-                    if (cerr == hipSuccess) { cerr = hipErrorUnknown; cwhat = "joining a chain stream"; }
+                    fe.note(hipErrorUnknown, "joining a chain stream");
                 }
             }
-#undef CH_TRY
-            if (cerr != hipSuccess) {
+            if (!fe.ok()) {
                 (void)hipGetLastError();
                 P->target_blocks_valid = false;                    // nothing of this run may be vouched for by the next one
-                creg::set_error("creg_train_plan_run_batch: %s: %s", cwhat, hipGetErrorString(cerr));
+                creg::set_error("creg_train_plan_run_batch: %s: %s", fe.what, hipGetErrorString(fe.err));
                 return CREG_EHIP;
             }
             e = D.epochs;
@@ -2043,7 +2011,7 @@ extern "C" int creg_train_plan_run_batch(creg_train_plan* plan, const creg_train
             for (; e + P->graph_epochs <= D.epochs; e += P->graph_epochs) CREG_HIP(hipGraphLaunch(P->gexec, s));
         }
     }
-    for (; e < D.epochs; ++e) enqueue_epoch(P, e, s);
+    for (; e < D.epochs; ++e) enqueue_epoch(P, all, e, s);
     hipLaunchKernelGGL(k_params_home, dim3(64, 1, P->B), dim3(256), 0, s, D, P->W, P->bstride, D.epochs & 1, 0);
     CREG_LAUNCH_CHECK();
     // results out, parameters back into the callers' tensors
@@ -2083,10 +2051,11 @@ extern "C" int creg_train_plan_resume(creg_train_plan* plan, const creg_train_ar
                  "creg_train_plan_resume: step %d / epochs_run %d + %d epochs exceed the plan's %d", from->step, from->epochs_run, n_epochs, D.epochs);
     CREG_REQUIRE(from->lr >= 0.0 && from->sched_bad >= 0 && from->count >= 0, "creg_train_plan_resume: negative lr or counter");
     hipStream_t s = (hipStream_t)stream;
-    int rc = stage_inputs(P, a, 1, s);          // parameters into the parity-0 buffer, the activations of epoch "0" from them, state and moments zeroed
+    const Slice one = slice_of(P, 0, 1);
+    int rc = stage_inputs(P, one, a, s);        // parameters into the parity-0 buffer, the activations of epoch "0" from them, state and moments zeroed
     if (rc) return rc;
     P->target_blocks_valid = false;
-    launch_sorts(P, s, 1);
+    launch_sorts(P, one, s);
     ParamMap pm[10];
     const int np = param_map(D, pm);
     {
@@ -2104,10 +2073,7 @@ extern "C" int creg_train_plan_resume(creg_train_plan* plan, const creg_train_ar
     }
     const ResumeState rs{from->lr, from->sched_best, from->step, from->epochs_run, from->sched_bad, from->count, from->best_epoch, from->stopped ? 1 : 0, from->min_loss};
     hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, s, D, P->W, rs);
-    const int nz_keep = P->nz;
-    P->nz = 1;
-    for (int e = 0; e < n_epochs; ++e) enqueue_epoch(P, e, s);
-    P->nz = nz_keep;
+    for (int e = 0; e < n_epochs; ++e) enqueue_epoch(P, one, e, s);
     hipLaunchKernelGGL(k_params_home, dim3(64, 1, 1), dim3(256), 0, s, D, P->W, P->bstride, n_epochs & 1, from->step);
     if (state_out) hipLaunchKernelGGL(k_get_state, dim3(1), dim3(64), 0, s, P->W, n_epochs & 1, state_out);
     CREG_LAUNCH_CHECK();
@@ -2133,12 +2099,12 @@ extern "C" int creg_train_plan_probe(creg_train_plan* plan, const creg_train_arg
     CREG_REQUIRE(P && a && a->m && a->y && a->local_pts && a->seg_offsets && a->params, "creg_train_plan_probe: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const Dims& D = P->D; const Ws& W = P->W;
-    int rc = stage_inputs(P, a, 1, s);
+    const Slice one = slice_of(P, 0, 1);
+    int rc = stage_inputs(P, one, a, s);
     if (rc) return rc;
     P->target_blocks_valid = false;
-    launch_sorts(P, s, 1);
-    P->nz = 1;
-    launch_head(P, 0, s);
+    launch_sorts(P, one, s);
+    launch_head(P, one, 0, s);
     launch_nn(D, W, 0, 1, s);
     hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, 1), dim3(256), 0, s, D, W, 0, D.nbx, D.nby, (size_t)0);
     CREG_LAUNCH_CHECK();
@@ -2162,14 +2128,14 @@ extern "C" int creg_train_plan_profile(creg_train_plan* plan, const creg_train_a
     const int br = P->shape.use_graph ? P->branches : 1;
     const int nzb = P->B / br + (P->B % br ? 1 : 0);
     std::vector<creg_train_args> all((size_t)nzb, *a);
-    int rc = stage_inputs(P, all.data(), nzb, s);
+    const Slice S = slice_of(P, 0, nzb);
+    int rc = stage_inputs(P, S, all.data(), s);
     if (rc) return rc;
     P->target_blocks_valid = false;
-    launch_sorts(P, s, nzb);
-    P->nz = nzb;
-    std::vector<hipEvent_t> ev((size_t)(NKERN + 1) * n_epochs);
-    for (auto& e : ev) CREG_HIP(hipEventCreate(&e));
-    for (int e = 0; e < n_epochs; ++e) enqueue_epoch(P, e, s, ev.data() + (NKERN + 1) * e);
+    launch_sorts(P, S, s);
+    ScopedEvents ev((size_t)(NKERN + 1) * n_epochs);
+    for (auto& e : ev.v) CREG_HIP(hipEventCreate(&e));
+    for (int e = 0; e < n_epochs; ++e) enqueue_epoch(P, S, e, s, ev.v.data() + (NKERN + 1) * e);
     CREG_LAUNCH_CHECK();
     CREG_HIP(hipStreamSynchronize(s));
     double acc[NKERN] = {0};
@@ -2188,13 +2154,13 @@ extern "C" int creg_train_plan_profile(creg_train_plan* plan, const creg_train_a
     const Dims& D = P->D; const Ws& W = P->W;
     CREG_HIP(hipEventRecord(ev[0], s));
     for (int i = 0; i < REP; ++i)
-        launch_nn(D, W, P->bstride, P->nz, s);
+        launch_nn(D, W, P->bstride, S.nz, s);
     CREG_HIP(hipEventRecord(ev[1], s));
     CREG_HIP(hipStreamSynchronize(s));
     float ms = 0.f;
     CREG_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
     us_out[6] = ms * 1000.f / REP;
-    us_out[7] = (float)P->nz;       // problems carried by that launch
+    us_out[7] = (float)S.nz;        // problems carried by that launch
     // us_out[8..11]: k_bd, k_l2, k_head, k_gradc the same way (measurement hooks: every k_bd launch is one more Adam step on
     // the plan's copies of the parameters, alternating between the two buffers; the caller's tensors are not written back)
     auto b2b = [&](auto launch, float* out) -> int {
@@ -2211,16 +2177,14 @@ extern "C" int creg_train_plan_profile(creg_train_plan* plan, const creg_train_a
         memset(z->startD, 0xff, sizeof(z->startD)); z->armed = 1;
         CREG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bd_st), z, sizeof(*z))); delete z; }
 #endif
-    if (int rc2 = b2b([&](int i) { launch_bd(P, i, s); }, us_out + 8)) return rc2;
+    if (int rc2 = b2b([&](int i) { launch_bd(P, S, i, s); }, us_out + 8)) return rc2;
 #ifdef CREG_BD_STAMPS
     { const int zero = 0; CREG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_bd_st), &zero, sizeof(int), offsetof(BdStamps, armed))); }
 #endif
-    if (int rc2 = b2b([&](int i) { launch_l2(P, i & 1, s); }, us_out + 9)) return rc2;
-    if (int rc2 = b2b([&](int i) { launch_head(P, i & 1, s); }, us_out + 10)) return rc2;
-    if (int rc2 = b2b([&](int i) { hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, P->nz), dim3(256), 0, s, D, W, i, D.nbx, D.nby, P->bstride); }, us_out + 11)) return rc2;
+    if (int rc2 = b2b([&](int i) { launch_l2(P, S, i & 1, s); }, us_out + 9)) return rc2;
+    if (int rc2 = b2b([&](int i) { launch_head(P, S, i & 1, s); }, us_out + 10)) return rc2;
+    if (int rc2 = b2b([&](int i) { hipLaunchKernelGGL(k_gradc, dim3(D.K, 1, S.nz), dim3(256), 0, s, D, W, i, D.nbx, D.nby, P->bstride); }, us_out + 11)) return rc2;
     CREG_LAUNCH_CHECK();
-    P->nz = P->B;
-    for (auto& e : ev) (void)hipEventDestroy(e);
     return CREG_OK;
 }
 

@@ -2002,3 +2002,73 @@ def test_train_plan_reports_its_search_form(dev):
     with pytest.warns(RuntimeWarning, match="exhaustive nearest-neighbour search"):
         r = ops.TrainPlan("q", 8, 64, 2048, 70000, epochs=4, device=dev)
     assert not r.info["pruned_target_search"] and not r.info["pruned_predicted_search"]
+
+
+@pytest.mark.parametrize("graph_branches", [0, 2])
+def test_train_plan_calls_leave_nothing_behind_for_the_next(dev, graph_branches):
+    """Every entry point of a plan says which problems its launches cover as an argument, so none of them can leave a launch
+    geometry behind: run_batch, probe, profile, resume and run_batch again on ONE plan -- the second run_batch gives the bits of the
+    first, and both those of a fresh plan.  7 epochs = one graph of 6 + one eager epoch per chain; graph_branches 0 takes the chain
+    streams (two chains of 3 + 2 problems: their captures, the chain tail, the stream pick), 2 the two-branch graph."""
+    from autourdf_amd import ops
+    from oracle import models
+    rng = np.random.default_rng(11)
+    K, per, batch = 3, 64, 5
+    centres = np.array([[0.0, 0.0, 0.0], [0.3, 0.1, 0.0], [0.1, 0.4, 0.2]])
+    cl = [rng.normal(size=(per, 3)) * 0.05 for _ in range(K)]
+    mats = np.tile(np.eye(4), (K, 1, 1))
+    mats[:, :3, 3] = centres
+    world = np.concatenate([c + t for c, t in zip(cl, centres)])
+    m = torch.tensor(mats, dtype=torch.float32, device=dev)
+    pts, off = ops.pack_clusters([torch.tensor(c, dtype=torch.float32) for c in cl], dev)
+    ys = [torch.tensor(world @ _rot_z(0.02).T + 0.001 * (b + 1), dtype=torch.float32, device=dev) for b in range(batch)]
+    assert pts.shape[0] == ys[0].shape[0] == K * per
+    torch.manual_seed(5)
+    sd = models.QRegMLP(True, 64).state_dict()
+    mk = lambda: [sd[kk].clone().to(dev) for kk in ops.Q_PARAM_ORDER]
+    new_plan = lambda: ops.TrainPlan("q", K, 64, K * per, K * per, epochs=7, use_graph=True, device=dev, batch=batch, graph_branches=graph_branches)
+
+    def run(plan):       # (best_m, best_pred, result, loss_hist, lr_hist) + the trained parameters of every problem, on the host
+        params = [mk() for _ in range(batch)]
+        outs = plan.run_batch([(m, ys[b], pts, off, params[b]) for b in range(batch)])
+        return [[t.cpu() for t in list(outs[b]) + params[b]] for b in range(batch)]
+
+    plan = new_plan()
+    if graph_branches == 0:
+        assert plan.info["graph_branches"] == 2
+    first = run(plan)
+    plan.probe(m, ys[0], pts, off, mk())
+    plan.profile(m, ys[0], pts, off, mk(), n_epochs=2)
+    pa = mk()
+    plan.resume(m, ys[0], pts, off, pa, {"exp_avg": [torch.zeros_like(p) for p in pa], "exp_avg_sq": [torch.zeros_like(p) for p in pa],
+                                         "lr": float(np.float32(2e-4))}, 1, patience=1)
+    second = run(plan)
+    fresh = run(new_plan())
+    for b in range(batch):
+        assert len(first[b]) == 5 + len(ops.Q_PARAM_ORDER)
+        for one, two, three in zip(first[b], second[b], fresh[b]):
+            assert torch.equal(two, one) and torch.equal(one, three)
+
+
+def test_masked_icp_launch_timing_changes_no_result(dev):
+    """The many-workgroup ICP with its launch-timing hook on (icp_nn_counters(timing=True): two events around every search launch,
+    read and released at the end of the call) against the same call with it off: same poses, points and iteration counts, and the
+    timed call has counted its launches.  One cluster of 1100 sources against 1100 targets."""
+    from autourdf_amd import ops
+    rng = np.random.default_rng(13)
+    base = rng.normal(size=(1100, 3)) * [0.06, 0.04, 0.03]
+    frame = base @ _rot_z(0.03).T + [0.003, 0.001, -0.002] + rng.normal(scale=3e-4, size=base.shape)
+    assert ops.masked_icp_regime(len(base), len(frame), 1) == "many_workgroups"
+    local, off = ops.pack_clusters([base], dev, torch.float64)
+    M = _cuda(np.eye(4)[None], dev)
+    world32 = ops.cluster_transform(local.to(torch.float32), off, M.to(torch.float32))
+    go = lambda: [t.cpu() for t in ops.masked_icp(local, world32, off, _cuda(frame, dev), M)]
+    try:
+        ops.icp_nn_counters(reset=True, timing=True)
+        timed = go()
+        launches = ops.icp_nn_counters()["nn_launches_timed"]
+    finally:
+        ops.icp_nn_counters(reset=True, timing=False)
+    plain = go()
+    assert launches > 0
+    assert all(torch.equal(a, b) for a, b in zip(timed, plain)) and int(plain[2][0]) >= 1
