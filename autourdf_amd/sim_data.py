@@ -18,6 +18,13 @@ down-sampling have no CPU fallback.
 every pixel back-projected, the per-camera clouds fused (``SimEnv.depth_cloud``); with ``SimEnv(ground_flag=True)`` the
 robot stands on a ground plane that is removed per camera by RANSAC plane segmentation at the reference's parameters
 (``ops.segment_plane``: 0.001, 6, 1000; sim_data.py:311-319).
+
+Self-colliding poses are rejected as the reference's generator does (sim_data.py:200-208, :276-281, :473-527), by this
+project's own contract: the posed ``<visual>`` triangles of every non-adjacent link pair, mesh against mesh, for all poses of
+a sequence in one launch (``ops.mesh_collide`` / ``SimEnv.collisions``; include/creg.h states the contract).  PyBullet's
+check -- convex hulls of the ``<collision>`` geometry with Bullet's margins after a physics step -- cannot be pinned without
+PyBullet and is not imitated.  ``data_collection(..., check_collision=True)`` stops a sequence at its first colliding step,
+``collect(..., reject_collisions=True)`` / ``--reject_collisions`` skips colliding seeds.
 """
 import os
 import struct
@@ -270,7 +277,8 @@ def _axis_angle(axis, q):
 
 class UrdfRobot:
     """Kinematic tree + visual triangles of a URDF.  ``links`` in file order; ``joints`` in file order (PyBullet
-    numbers joints the same way); ``tri`` (F,3,3) in link frames, ``tri_link`` (F,), ``cum_area`` (F,)."""
+    numbers joints the same way); ``tri`` (F,3,3) in link frames, ``tri_link`` (F,), ``cum_area`` (F,), ``tri_start`` (L+1,)
+    int64: link l owns rows tri_start[l]:tri_start[l+1] of ``tri``."""
 
     def __init__(self, urdf_path, global_scale=1.0, package_dirs=()):
         self.path = os.path.abspath(urdf_path)
@@ -318,6 +326,9 @@ class UrdfRobot:
         keep = area > 0                                          # degenerate facets carry no surface
         self.tri, self.tri_link, area = self.tri[keep], self.tri_link[keep], area[keep]
         self.cum_area = np.cumsum(area)
+        if np.any(np.diff(self.tri_link) < 0):
+            raise ValueError(f"{urdf_path}: tri_link is not non-decreasing (the triangles of a link must be contiguous)")
+        self.tri_start = np.searchsorted(self.tri_link, np.arange(len(self.links) + 1), side="left").astype(np.int64)
 
     def _resolve(self, filename, package_dirs):
         if filename.startswith("package://"):
@@ -340,6 +351,20 @@ class UrdfRobot:
             if os.path.exists(c):
                 return c
         raise FileNotFoundError(f"mesh {filename!r} of {self.path} not found (tried {cands[:3]} ...)")
+
+    def collision_pairs(self, excluded_pairs=()):
+        """(M,2) int32 link pairs the self-collision check tests: every i < j of links that own triangles, minus parent-child
+        pairs (joined links intersect at every pose) and minus ``excluded_pairs`` [(name, name), ...] in either order; a name
+        that is no link is ignored, like the reference's ``link_name_to_index.get`` (sim_data.py:210-219)."""
+        skip = {frozenset((self.link_index[j["parent"]], self.link_index[j["child"]])) for j in self.joints}
+        for a, b in excluded_pairs:
+            ia, ib = self.link_index.get(a), self.link_index.get(b)
+            if ia is not None and ib is not None:
+                skip.add(frozenset((ia, ib)))
+        owns = np.diff(self.tri_start) > 0
+        n = len(self.links)
+        pairs = [(i, j) for i in range(n) for j in range(i + 1, n) if owns[i] and owns[j] and frozenset((i, j)) not in skip]
+        return np.asarray(pairs, np.int32).reshape(-1, 2)
 
     def fk(self, q_by_joint, base=None):
         """Link poses (L,4,4) float64 for joint positions {name: value} (missing joints at 0)."""
@@ -424,7 +449,8 @@ class SimEnv:
     order with their limits (:66-82), the first ``dof`` of them driven, the rest parked at mid range (:131-157)."""
 
     def __init__(self, urdf_path, base_position=[0, 0, 0], base_orientation=[0, 0, 0], gui=False, dof=5,
-                 ground_flag=False, radius=1.5, num_cameras=3, global_scale=1.0, package_dirs=(), ground_size=None, ground_cells=32):
+                 ground_flag=False, radius=1.5, num_cameras=3, global_scale=1.0, package_dirs=(), ground_size=None, ground_cells=32,
+                 excluded_pairs=()):
         if gui:
             raise NotImplementedError("gui=True needs PyBullet's viewer (out of scope)")
         self.dof = dof
@@ -438,6 +464,8 @@ class SimEnv:
         self.joint_limits = np.array([self.joint_params[j] for j in self.dof_list])
         self._dev = None
         self._dev_raster = None
+        self._dev_collide = {}
+        self.excluded_pairs = [tuple(pr) for pr in excluded_pairs]   # parameters.json's 'excluded_pairs' (link names)
         self._setup_cameras(radius, num_cameras)
         # the ground the reference stands its robot on (ground_flag): seen by the raster passes of depth_cloud only
         self.ground_tri = ground_mesh(radius if ground_size is None else ground_size, ground_cells) if ground_flag else None
@@ -533,9 +561,42 @@ class SimEnv:
         u = torch.as_tensor(rng.random((n, 3)), device=tri.device)
         return ops.sample_mesh(tri, cum, own, T, u)
 
+    def collisions(self, link_T, use_excluded=False):
+        """Self and floor contacts of P poses in one launch (creg_mesh_collide_f64): link_T (P,L,4,4) -- or (L,4,4) -- device
+        poses (ops.urdf_fk).  Returns one (self_contact, floor_contact) per pose: self_contact lists (link_a, link_b, count,
+        tri_a, tri_b) for every tested link pair with colliding triangles -- their number and the smallest colliding pair as
+        rows of ``robot.tri``; the tested pairs are ``robot.collision_pairs()``, minus the env's ``excluded_pairs`` when
+        ``use_excluded``.  floor_contact lists the non-root links whose posed box reaches below z = 0, and is empty unless the
+        env was built with ``ground_flag=True`` (the root stands on the ground)."""
+        tri = self._device_mesh()[0]
+        r = self.robot
+        key = bool(use_excluded)
+        if key not in self._dev_collide:
+            host = r.collision_pairs(self.excluded_pairs if key else ())
+            self._dev_collide[key] = (host, torch.as_tensor(host, device=tri.device), torch.as_tensor(r.tri_start, device=tri.device))
+        host, pairs, tri_start = self._dev_collide[key]
+        count, first, box = ops.mesh_collide(tri, tri_start, link_T, pairs, want_boxes=True)
+        count, first, low = count.cpu().numpy(), first.cpu().numpy(), box[:, :, 2].cpu().numpy()
+        root = r.link_index[r.root]
+        out = []
+        for p in range(count.shape[0]):
+            self_c = [(r.links[host[m, 0]], r.links[host[m, 1]], int(count[p, m]), int(first[p, m, 0]), int(first[p, m, 1]))
+                      for m in np.flatnonzero(count[p])]
+            floor_c = [r.links[l] for l in np.flatnonzero(low[p] < 0) if l != root] if self.ground_tri is not None else []
+            out.append((self_c, floor_c))
+        return out
+
+    def self_collision_check(self, joint_positions, link_T=None, use_excluded=False):
+        """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
+        `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""
+        if link_T is None:
+            link_T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=self._device_mesh()[0].device)
+        return self.collisions(link_T, use_excluded)[0]
+
     def reset(self):
         self._dev = None
         self._dev_raster = None
+        self._dev_collide = {}
 
 
 def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list):
@@ -556,7 +617,7 @@ def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list)
 
 def data_collection(env, data_path=None, width=800, height=800, visualize=False, angle_list=None, ground_flag=False,
                     noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None,
-                    source="surface"):
+                    source="surface", check_collision=False):
     """One sequence: for every row of ``angle_list`` pose the robot, sample surface points, keep those that at least one
     camera of the ring sees (``occlusion``: depth buffers of ``width`` x ``height`` like the reference's rendered images,
     sim_data.py:286-306; more samples are drawn until ``oversample * num_points`` visible ones exist), add the
@@ -569,16 +630,34 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     ``ground_flag=True`` then removes the ground per camera and needs an env built with ``ground_flag=True``.  Noise,
     down-sampling and saving are the same; ``oversample`` and ``occlusion`` do not apply.  (``source="surface"`` ignores
     ``ground_flag``.)
-    Returns (collision=False, list of PointCloud) like the reference (self-collision checking is PyBullet's)."""
+    ``check_collision=True`` checks every row for self and floor contacts before any frame is made (one ``ops.urdf_fk`` over
+    all rows unless ``link_T`` was given, one ``SimEnv.collisions`` launch); ``collision_flag=True`` then applies the env's
+    ``excluded_pairs``, as in the reference.  At the first colliding step s it prints ``collision detected`` with the pairs,
+    generates and saves only the steps before s, writes no ``noise.txt`` and returns (True, record): the reference breaks at
+    that step (sim_data.py:276-281).  With no colliding row the clouds and files are those of ``check_collision=False``.
+    Returns (collision, list of PointCloud) like the reference; collision is False when nothing was checked."""
     if visualize:
         raise NotImplementedError("visualize=True needs Open3D's viewer (out of scope)")
     if source not in ("surface", "depth"):
         raise ValueError(f"data_collection: source must be 'surface' or 'depth', got {source!r}")
     if source == "depth" and ground_flag and env.ground_tri is None:
         raise ValueError("data_collection: ground_flag=True needs an env built with SimEnv(..., ground_flag=True)")
+    stop = None
+    if check_collision and len(angle_list):
+        poses = link_T
+        if poses is None:
+            qs = [env.set_joint_positions(cmd) for cmd in np.asarray(angle_list)]
+            poses = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
+        for step, (self_c, floor_c) in enumerate(env.collisions(poses[:len(angle_list)], use_excluded=collision_flag)):
+            if len(self_c) + len(floor_c) > 0:
+                print('collision detected', self_c, floor_c)
+                stop = step
+                break
     rng = np.random.default_rng(seed)
     noise, record = [], []
     for jp_id, cmd in enumerate(np.asarray(angle_list)):
+        if stop is not None and jp_id >= stop:
+            break
         q = env.set_joint_positions(cmd)
         want = oversample * num_points
         pose = {} if link_T is None else {"link_T": link_T[jp_id]}
@@ -608,33 +687,70 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
         if data_path is not None:
             save_step_data(jp_id, cloud, q, data_path, env.dof_list)
         record.append(cloud)
+    if stop is not None:
+        return True, record
     if noise_flag and data_path is not None:
         np.savetxt(data_path + "noise.txt", np.array(noise).reshape(-1, 3), fmt="%.6f")
     return False, record
 
 
+def sequence_collides(env, a_list, use_excluded=False):
+    """The link pairs that collide somewhere in the sequence ``a_list`` (num_step, dof): a list of (link_a, link_b) names, a
+    floor contact as ('ground', link); empty when every step is free.  One ``ops.urdf_fk`` and one ``SimEnv.collisions`` launch
+    for the whole sequence."""
+    qs = [env.set_joint_positions(cmd) for cmd in np.asarray(a_list)]
+    if not qs:
+        return []
+    link_T = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
+    found = []
+    for self_c, floor_c in env.collisions(link_T, use_excluded):
+        for pr in [(c[0], c[1]) for c in self_c] + [("ground", l) for l in floor_c]:
+            if pr not in found:
+                found.append(pr)
+    return found
+
+
 def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, noise=True, num_points=5000,
-            num_cameras=20, root=".", source="surface", ground=False, pix=800):
+            num_cameras=20, root=".", source="surface", ground=False, pix=800,
+            reject_collisions=False, max_seeds=100):
     """`epochs` sequences of `num_step` frames under data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/
     -- the directory layout of the reference's collect() (sim_data.py:465-531), which match() globs
     (mlp_reg.py:424).  robot_params needs the reference's keys 'gt' (URDF path), 'dof' and optionally 'sim_ori'.
-    The self-collision rejection of seeds is PyBullet's and is not reproduced: seeds are 0..epochs-1.
+    Seeds are 0..epochs-1 by default.  ``reject_collisions=True`` runs the reference's loop instead (:473-527): seeds 0, 1, 2, ...
+    are tried in turn, the whole ``angle_list`` of a seed is checked before any frame is made (``sequence_collides``, with
+    robot_params' 'excluded_pairs' applied when its 'collision_exclusion' is true), a colliding seed is skipped with a printed
+    line naming its pairs and writes nothing, and the loop stops at `epochs` kept seeds.  After ``max_seeds`` seeds it raises,
+    naming the pair that collided most often: the one to put into 'excluded_pairs'.
     ``source="depth"`` collects depth-camera frames of ``pix`` x ``pix`` images, ``ground`` stands the robot on the ground
     plane and removes it per camera (the reference's --pix / --ground); the ground needs the depth source."""
     if ground and source != "depth":
         raise ValueError("collect: ground=True needs source='depth' (the surface sampler has no ground to remove)")
-    paths = []
-    for seed in range(epochs):
-        data_path = os.path.join(root, f"data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/")
-        os.makedirs(data_path, exist_ok=True)
+    paths, tally, seed = [], {}, 0
+    use_excluded = bool(robot_params.get("collision_exclusion", False))
+    while len(paths) < epochs:
+        if reject_collisions and seed >= max_seeds:
+            worst = max(tally, key=tally.get) if tally else None
+            raise RuntimeError(f"collect: only {len(paths)} of {epochs} collision-free seeds among the first {max_seeds}; the pair "
+                               f"that collided most often is {worst} ({tally.get(worst, 0)} seeds): if its links may touch, add it "
+                               f"to the robot's 'excluded_pairs' and set 'collision_exclusion'")
         np.random.seed(seed)                                       # the ring of >= 20 cameras draws from the global state
         env = SimEnv(os.path.join(root, robot_params["gt"]), base_orientation=robot_params.get("sim_ori", [0, 0, 0]),
-                     dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras, ground_flag=ground)
+                     dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras, ground_flag=ground,
+                     excluded_pairs=robot_params.get("excluded_pairs", []))
         a_list = angle_list(num_step, step_size, robot_params["dof"], env.joint_limits, np.array([scale] * robot_params["dof"]), seed)
-        data_collection(env, data_path=data_path, width=pix, height=pix, angle_list=a_list, ground_flag=ground, noise_flag=noise,
-                        num_points=num_points, seed=seed, source=source)
+        hit = sequence_collides(env, a_list, use_excluded) if reject_collisions else []
+        if hit:
+            print(f"seed {seed}: collision detected {hit}, skipped")
+            for pr in hit:
+                tally[pr] = tally.get(pr, 0) + 1
+        else:
+            data_path = os.path.join(root, f"data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/")
+            os.makedirs(data_path, exist_ok=True)
+            data_collection(env, data_path=data_path, width=pix, height=pix, angle_list=a_list, ground_flag=ground, noise_flag=noise,
+                            num_points=num_points, seed=seed, source=source)
+            paths.append(data_path)
         env.reset()
-        paths.append(data_path)
+        seed += 1
     return paths
 
 
@@ -652,6 +768,7 @@ def _parser():
     ap.add_argument('--no_noise', action='store_true')
     ap.add_argument('--num_points', type=int, default=5000)
     ap.add_argument('--num_cameras', type=int, default=20)
+    ap.add_argument('--reject_collisions', action='store_true', help="skip seeds whose sequence self-collides (or touches the ground), like the reference's collect()")
     return ap
 
 
@@ -665,7 +782,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     """python -m autourdf_amd.sim_data --robot wx200_5 [...]: the reference's flags (sim_data.py:537-551) minus --gui / --vis,
-    plus --depth; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json."""
+    plus --depth and --reject_collisions; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json."""
     import json
     args = parse_args(argv)
     with open('parameters.json') as f:
@@ -673,7 +790,8 @@ def main(argv=None):
     if 'gt' not in params:
         raise SystemExit(f"parameters.json has no 'gt' URDF path for {args.robot!r} (use the reference's parameters.json)")
     for p in collect(args.robot, params, args.num_step, args.step_size, args.epoch, args.scale, not args.no_noise,
-                     args.num_points, args.num_cameras, source="depth" if args.depth else "surface", ground=args.ground, pix=args.pix):
+                     args.num_points, args.num_cameras, source="depth" if args.depth else "surface", ground=args.ground, pix=args.pix,
+                     reject_collisions=args.reject_collisions):
         print(p)
 
 

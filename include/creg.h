@@ -509,6 +509,44 @@ int creg_urdf_fk_f64(const int32_t* parent, const int32_t* child, const int32_t*
                      int32_t n_poses, const double* base, double* link_T, double* joint_lines, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Self-collision of posed link meshes: all listed link pairs of all poses in one call, triangle mesh against triangle mesh.
+ * The reference's generator asks PyBullet for self contacts and abandons the sequence at the first one
+ * (Sim/sim_data.py:200-208, :276-281): convex hulls of the <collision> geometry with Bullet's margins, after a physics step.
+ * PyBullet is not part of this build, so that check can NOT be pinned and is not imitated; the contract below is this
+ * project's own.
+ *   geometry   tri (n_tri,9) fp64: triangles in link frames (the <visual> triangles the frames are made of); link l owns rows
+ *              tri_start[l] .. tri_start[l+1] (tri_start (n_links+1) int64, non-decreasing, 0 .. n_tri; values outside are
+ *              clamped, nothing outside tri is read).  link_T (n_poses,n_links,16): row-major 4x4 poses, bottom row unread.
+ *   vertex     w_i = ((R_i0*v_0 + R_i1*v_1) + R_i2*v_2) + t_i   -- in exactly this order, no contraction.
+ *   pair       triangles (a, b) collide iff (1) their posed axis-aligned boxes overlap -- the box is the exact min / max of
+ *              the three posed vertices, closed comparisons lo_a <= hi_b && lo_b <= hi_a on all three axes -- and (2) some
+ *              edge of one properly pierces the other: the three edges of a against b and the three of b against a.
+ *   piercing   orient(p,q,r,s) = ((u x v)_x*w_x + (u x v)_y*w_y) + (u x v)_z*w_z with u = q-p, v = r-p, w = s-p and
+ *              (u x v) = (u_y*v_z - u_z*v_y, u_z*v_x - u_x*v_z, u_x*v_y - u_y*v_x).  Edge (p,q) properly pierces (a,b,c) when
+ *              orient(a,b,c,p) and orient(a,b,c,q) have strictly opposite signs AND orient(p,q,a,b), orient(p,q,b,c),
+ *              orient(p,q,c,a) are all > 0 or all < 0.  A zero anywhere is "no": touching, an edge through a vertex or
+ *              through an edge, and coplanar overlap are not collisions; links mounted flush do not collide.  A mesh wholly
+ *              INSIDE another is not detected (no edge pierces a face).
+ *   culling    link boxes, boxes of 256-triangle chunks and tile union boxes are exact min / max of the same posed vertices,
+ *              so with (1) in the contract they are exactly conservative: culling changes no output.
+ * pairs (n_pairs,2) int32 link indices; which pairs to test (adjacent links intersect at every pose and are left out by the
+ * caller: UrdfRobot.collision_pairs).  Outputs:
+ *   count (n_poses,n_pairs) int32     colliding triangle pairs (a in link pairs[m][0], b in link pairs[m][1]); there is no early
+ *                                     exit on the first hit.
+ *   first (n_poses,n_pairs,2) int32   the lexicographically smallest such (a, b), rows of tri, or (-1,-1).
+ *   link_box (n_poses,n_links,6)      min xyz | max xyz of the link's posed vertices, +inf | -inf for a link without triangles;
+ *                                     may be NULL.
+ * A pair that names a link outside [0, n_links), or one link twice, gives count 0 and (-1,-1).  n_pairs == 0 is valid and
+ * fills link_box only.  Only integer atomics (add, 64-bit min of (a << 32) | b): two runs are identical.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_pairs < 0, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, a workspace smaller
+ * than creg_mesh_collide_workspace_bytes(n_tri, n_links, n_poses, n_pairs) (posed vertices, chunk and link boxes, keys).
+ * Limits: colliding triangle pairs per link pair and pose < 2^31. */
+size_t creg_mesh_collide_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs);
+int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                          int64_t n_poses, const int32_t* pairs, int64_t n_pairs, int32_t* count, int32_t* first,
+                          double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A1  the whole `train` loop (mlp_reg.py:17-152) as one device-resident plan: per epoch
  * pose -> sin/cos features -> MLP -> pose -> calculate_pc -> L1 Chamfer -> backward -> Adam ->
  * ReduceLROnPlateau, best-loss tracking and early stop, with no host round trip per epoch
