@@ -39,34 +39,38 @@ class _HostInverse:
         return torch.from_numpy(inv).to(M.device, non_blocking=True)
 
 
-class SequenceRegistrar:
-    def __init__(self, mats0, clusters0, n_tgt, rot="q", hidden=512, epochs=300, use_graph=True, device=None,
-                 seed=0):
-        self._init_state(mats0, clusters0, rot, hidden, _lib.device(torch.device(device) if device is not None else None), seed)
-        self.plan = ops.TrainPlan(rot, self.K, hidden, self.pts.shape[0], n_tgt, epochs=epochs, use_graph=use_graph,
-                                  device=self.device)
+class _SequenceState:
+    """What one sequence carries from frame to frame: its two models and their parameter lists ("Step" / "Anchor"), the current
+    poses and clusters, and the frame-0 clusters that "Anchor" and `--mlp_icp` keep registering."""
 
-    def _init_state(self, mats0, clusters0, rot, hidden, device, seed, models=None):
-        self.device = device
-        self.rot, self.K = rot, len(clusters0)
+    def __init__(self, mats0, clusters0, rot, hidden, device, seed, models=None):
         if models is not None:                       # caller-made (model, model_rf), e.g. the drop-in's _make_models()
-            self.model, self.model_rf = models[0].to(self.device), models[1].to(self.device)
+            self.model, self.model_rf = models[0].to(device), models[1].to(device)
         else:
             gen_state = torch.random.get_rng_state()
             torch.manual_seed(seed)                  # the reference leaves the MLP init unseeded (SURVEY 0.4)
             ctor = {"q": lambda: QRegMLP(True, hidden_dim=hidden), "dq": lambda: DQRegMLP(hidden_dim=hidden),
                     "6d": lambda: RRegMLP(hidden_dim=hidden), "rpy": lambda: RegMLP(True, hidden_dim=hidden)}[rot]
-            self.model, self.model_rf = ctor().to(self.device), ctor().to(self.device)
+            self.model, self.model_rf = ctor().to(device), ctor().to(device)
             torch.random.set_rng_state(gen_state)
         order = ops.DQ_PARAM_ORDER if rot == "dq" else ops.Q_PARAM_ORDER
         self.p_step = [dict(self.model.named_parameters())[n].data for n in order]
         self.p_anchor = [dict(self.model_rf.named_parameters())[n].data for n in order]
-        self.m = torch.as_tensor(mats0, dtype=torch.float32).to(self.device).contiguous()
-        self.pts, self.off = ops.pack_clusters(clusters0, self.device)
+        self.m = torch.as_tensor(mats0, dtype=torch.float32).to(device).contiguous()
+        self.pts, self.off = ops.pack_clusters(clusters0, device)
         self.pts_init, self.off_init = self.pts.clone(), self.off.clone()
-        self.local64, _ = ops.pack_clusters(clusters0, self.device, torch.float64)   # what resample_cluster returned last
+        self.local64, _ = ops.pack_clusters(clusters0, device, torch.float64)   # what resample_cluster returned last
         self.local64_init = self.local64             # step_cluster_np of the reference: assigned once (mlp_reg.py:248/253)
+
+
+class SequenceRegistrar(_SequenceState):
+    def __init__(self, mats0, clusters0, n_tgt, rot="q", hidden=512, epochs=300, use_graph=True, device=None,
+                 seed=0):
+        self.device = _lib.device(torch.device(device) if device is not None else None)
+        super().__init__(mats0, clusters0, rot, hidden, self.device, seed)
         self.host_inverse = _HostInverse(self.device)
+        self.plan = ops.TrainPlan(rot, len(clusters0), hidden, self.pts.shape[0], n_tgt, epochs=epochs, use_graph=use_graph,
+                                  device=self.device)
 
     def step(self, frame64: torch.Tensor, frame32: torch.Tensor = None):
         """Register the next frame ((N,3) fp64 on the device).  Returns (poses (K,4,4) fp32, result (4))."""
@@ -94,15 +98,11 @@ class BatchRegistrar:
         self.S = n_sequences
         self.host_inverse = _HostInverse(self.device)
         seeds = list(seeds) if seeds is not None else list(range(n_sequences))
-        self.seqs = []
-        for s in range(n_sequences):
-            r = SequenceRegistrar.__new__(SequenceRegistrar)
-            SequenceRegistrar._init_state(r, mats0, clusters0, rot, hidden, self.device, seeds[s],
-                                          None if models is None else models[s])
-            self.seqs.append(r)
+        self.seqs = [_SequenceState(mats0, clusters0, rot, hidden, self.device, seeds[s], None if models is None else models[s])
+                     for s in range(n_sequences)]
         self.plan = ops.TrainPlan(rot, len(clusters0), hidden, self.seqs[0].pts.shape[0], n_tgt, epochs=epochs,
                                   use_graph=use_graph, device=self.device, batch=n_sequences, graph_branches=graph_branches,
-                                 nn_search=nn_search)
+                                  nn_search=nn_search)
 
     def _train(self, problems, lr, same_target=False):
         """One batched `train` (mlp_reg.py:17-152) of the S problems (m, y, pts, offsets, params); a seam so the
@@ -124,9 +124,21 @@ class BatchRegistrar:
                 X6 = torch.as_tensor(feat, dtype=torch.float64, device=f.device).contiguous()
                 km.append(ops.kmeans_lloyd_nd(X6, torch.cat([c, torch.zeros_like(c)], 1).contiguous()))
             return km
-        if frames64[0].shape[0] <= ops.KMEANS_BATCH_MAX_N and self.S <= 16 and inits[0].shape[0] <= 128:      # all S in one launch
-            return ops.kmeans_lloyd_batch(frames64, inits)
-        return [ops.kmeans_lloyd(f, c) for f, c in zip(frames64, inits)]
+        return ops.kmeans_lloyd_each(frames64, inits)
+
+    def _resegment(self, frames64, Ms):
+        """The tail of a round (resample_cluster, mlp_reg.py:172-237) around its poses Ms (per sequence (K,4,4): float32 from train,
+        float64 from masked_icp): k-means of every frame seeded at the translations, while the host inverts the poses in their own
+        dtype, then the frames' points grouped into the pose frames; poses and clusters become every sequence's state."""
+        M_all = torch.stack(Ms)
+        ev = self.host_inverse.mark()
+        t_all = M_all[:, :, :3, 3].to(torch.float64).contiguous()                 # one cast and one slice for all sequences
+        km = self._kmeans(frames64, list(t_all))
+        inv_all = self.host_inverse(M_all, ev)                                    # LAPACK inverse, as mlp_reg.py:211
+        groups = ops.group_to_local_each(frames64, [res[1] for res in km], list(inv_all), m_is_inverse=True)
+        for r, M, (local, off) in zip(self.seqs, Ms, groups):
+            r.local64, r.off = local, off            # what resample_cluster returns (the cluster/NNNN.npz contents)
+            r.pts, r.m = local.to(torch.float32), M.to(torch.float32)
 
     def step(self, frames64, frames32=None):
         """frames64: list of S (N,3) fp64 device tensors (the next frame of every sequence)."""
@@ -134,62 +146,24 @@ class BatchRegistrar:
         step = self._train([(r.m, y, r.pts, r.off, r.p_step) for r, y in zip(self.seqs, ys)], lr=2e-4)
         anchor = self._train([(o[0], y, r.pts_init, r.off_init, r.p_anchor)
                               for r, y, o in zip(self.seqs, ys, step)], lr=1e-4, same_target=True)
-        out = []
         # epochs each train ran (result[1]; < the plan's epochs after an early stop) -- bench.py reports them
         self.last_epochs = (torch.stack([o[2][1] for o in step]), torch.stack([o[2][1] for o in anchor]))
-        M_all = torch.stack([o[0] for o in anchor])                               # (S,K,4,4) float32: what train returned
-        ev = self.host_inverse.mark()
-        t_all = M_all[:, :, :3, 3].to(torch.float64).contiguous()                 # one cast and one slice for all sequences
-        inits = [t_all[i] for i in range(self.S)]
-        km = self._kmeans(frames64, inits)
-        inv_all = self.host_inverse(M_all, ev)                                    # float32 LAPACK inverse, as mlp_reg.py:211
-        invs = [inv_all[i] for i in range(self.S)]
-        if self.S <= ops.GROUP_BATCH_MAX and len({f.shape[0] for f in frames64}) == 1:
-            groups = ops.group_to_local_batch(frames64, [res[1] for res in km], invs, m_is_inverse=True)     # all S in one launch pair
-        else:
-            groups = [ops.group_to_local(f, res[1], I, m_is_inverse=True) for f, res, I in zip(frames64, km, invs)]
-        for r, o, (local, off) in zip(self.seqs, anchor, groups):
-            m2 = o[0]
-            r.off = off
-            r.local64 = local                        # what resample_cluster returns (the cluster/NNNN.npz contents)
-            r.pts, r.m = local.to(torch.float32), m2
-            out.append((m2, o[2]))
-        return out
+        self._resegment(frames64, [o[0] for o in anchor])
+        return [(o[0], o[2]) for o in anchor]
 
-
-def _step_mlp_icp(self, frames64, frames32=None):
-    """The `--mlp_icp` frame of match() (mlp_reg.py:296-332) for all S sequences: ONE batched "Step" train on the
-    current (re-sampled) clusters, ONE masked-ICP launch (clusters x sequences) started from the trained poses whose
-    SOURCES are the frame-0 clusters (the reference never reassigns `step_cluster_np`, mlp_reg.py:248,325) and whose
-    mask boxes are those of the trained clouds of the current segmentation (`pred_pcd_np`), ONE k-means launch.
-    Returns [(poses (K,4,4) fp64, train result (4))] per sequence."""
-    ys = frames32 if frames32 is not None else [f.to(torch.float32) for f in frames64]
-    step = self._train([(r.m, y, r.pts, r.off, r.p_step) for r, y in zip(self.seqs, ys)], lr=2e-4)
-    probs = [(r.local64_init, o[1], r.off_init, f, o[0].to(torch.float64), r.off) for r, f, o in zip(self.seqs, frames64, step)]
-    if len(probs) <= ops.ICP_BATCH_MAX:
-        icp = ops.masked_icp_batch(probs)
-    else:
-        icp = [ops.masked_icp(*p) for p in probs]
-    Ms = [M for M, _, _ in icp]
-    M_all = torch.stack(Ms)                                                       # (S,K,4,4) float64: masked_icp's poses
-    ev = self.host_inverse.mark()
-    inits = [M[:, :3, 3].contiguous() for M in Ms]
-    km = self._kmeans(frames64, inits)
-    out = []
-    inv_all = self.host_inverse(M_all, ev)                                        # float64 LAPACK inverse (mlp_reg.py:211,326)
-    invs = [inv_all[i] for i in range(self.S)]
-    if len(self.seqs) <= ops.GROUP_BATCH_MAX and len({f.shape[0] for f in frames64}) == 1:
-        groups = ops.group_to_local_batch(frames64, [res[1] for res in km], invs, m_is_inverse=True)
-    else:
-        groups = [ops.group_to_local(f, res[1], I, m_is_inverse=True) for f, res, I in zip(frames64, km, invs)]
-    for r, M, o, (local, off) in zip(self.seqs, Ms, step, groups):
-        r.local64, r.off = local, off
-        r.pts, r.m = r.local64.to(torch.float32), M.to(torch.float32)
-        out.append((M, o[2]))
-    return out
-
-
-BatchRegistrar.step_mlp_icp = _step_mlp_icp
+    def step_mlp_icp(self, frames64, frames32=None):
+        """The `--mlp_icp` frame of match() (mlp_reg.py:296-332) for all S sequences: ONE batched "Step" train on the
+        current (re-sampled) clusters, ONE masked-ICP launch (clusters x sequences) started from the trained poses whose
+        SOURCES are the frame-0 clusters (the reference never reassigns `step_cluster_np`, mlp_reg.py:248,325) and whose
+        mask boxes are those of the trained clouds of the current segmentation (`pred_pcd_np`), ONE k-means launch.
+        Returns [(poses (K,4,4) fp64, train result (4))] per sequence."""
+        ys = frames32 if frames32 is not None else [f.to(torch.float32) for f in frames64]
+        step = self._train([(r.m, y, r.pts, r.off, r.p_step) for r, y in zip(self.seqs, ys)], lr=2e-4)
+        icp = ops.masked_icp_each([(r.local64_init, o[1], r.off_init, f, o[0].to(torch.float64), r.off)
+                                   for r, f, o in zip(self.seqs, frames64, step)])
+        Ms = [M for M, _, _ in icp]
+        self._resegment(frames64, Ms)
+        return [(M, o[2]) for M, o in zip(Ms, step)]
 
 
 class IcpRegistrar:
@@ -217,7 +191,7 @@ class IcpRegistrar:
 
 
 class BatchIcpRegistrar:
-    """S sequences of identical frame size through IcpRegistrar's steps in lock-step: the S ICP launches
+    """S sequences through IcpRegistrar's steps in lock-step: where the frames have one size the S ICP launches
     share one launch (grid clusters x sequences) and the S re-segmentations one k-means launch (no host sync in a
     round).  Results equal S separate IcpRegistrars (the batched k-means is bit-identical to the
     multi-launch one)."""
@@ -226,28 +200,14 @@ class BatchIcpRegistrar:
         self.regs = [IcpRegistrar(mats0, clusters0, device) for _ in range(n_sequences)]
 
     def step(self, frames64):
-        if len(self.regs) <= ops.ICP_BATCH_MAX and len({(r.local.shape[0], f.shape[0]) for r, f in zip(self.regs, frames64)}) == 1:
-            # all sequences' clusters in one launch; the mask boxes (K3 of the current poses) are evaluated inside it
-            icp = ops.masked_icp_batch([(r.local, None, r.off, f, r.M) for r, f in zip(self.regs, frames64)])
-        else:
-            icp = [ops.masked_icp(r.local, ops.cluster_transform(r.local.to(torch.float32), r.off, r.M.to(torch.float32)),
-                                  r.off, f, r.M) for r, f in zip(self.regs, frames64)]
-        k = icp[0][0].shape[0]
-        M_all = torch.stack([M_new for M_new, _, _ in icp])                       # (S,K,4,4): one cast, one K5 launch, one slice
-        dq_all = ops.se3_to_dq(M_all.to(torch.float32).reshape(-1, 4, 4)).reshape(len(icp), k, 8)
-        t_all = M_all[:, :, :3, 3].contiguous()
-        res = [(M_new, dq_all[i], n_it) for i, (M_new, _, n_it) in enumerate(icp)]
-        inits = [t_all[i] for i in range(len(icp))]
-        if frames64[0].shape[0] <= ops.KMEANS_BATCH_MAX_N and len(self.regs) <= 16 and k <= 128:
-            km = ops.kmeans_lloyd_batch(frames64, inits)
-        else:
-            km = [ops.kmeans_lloyd(f, c) for f, c in zip(frames64, inits)]
-        if len(self.regs) <= ops.GROUP_BATCH_MAX and len({f.shape[0] for f in frames64}) == 1:
-            groups = ops.group_to_local_batch(frames64, [kr[1] for kr in km], [o[0] for o in res])
-        else:
-            groups = [ops.group_to_local(f, kr[1], o[0]) for f, o, kr in zip(frames64, res, km)]
-        for r, o, (local, off) in zip(self.regs, res, groups):
+        # in one launch the mask boxes (K3 of the current poses) are evaluated inside it
+        icp = ops.masked_icp_each([(r.local, None, r.off, f, r.M) for r, f in zip(self.regs, frames64)])
+        Ms = [M_new for M_new, _, _ in icp]
+        M_all = torch.stack(Ms)                                                   # (S,K,4,4): one cast, one K5 launch, one slice
+        dq_all = ops.se3_to_dq(M_all.to(torch.float32).reshape(-1, 4, 4)).reshape(len(Ms), -1, 8)
+        km = ops.kmeans_lloyd_each(frames64, list(M_all[:, :, :3, 3].contiguous()))
+        groups = ops.group_to_local_each(frames64, [kr[1] for kr in km], Ms)
+        for r, M_new, (local, off) in zip(self.regs, Ms, groups):
             r.local, r.off = local, off
-            r.M = o[0]
-        return res
-
+            r.M = M_new
+        return [(M_new, dq, n_it) for (M_new, _, n_it), dq in zip(icp, dq_all)]

@@ -17,6 +17,7 @@ Run as ``python -m autourdf_amd.mlp_reg --robot wx200_5`` from a directory holdi
 ``parameters.json`` and ``data/raw/...`` (what scripts/registration.sh does).
 """
 import argparse
+import contextlib
 import glob
 import json
 import os
@@ -204,6 +205,14 @@ class _FileWriter:
         if self._err is not None and not propagating:
             raise self._err
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        # "propagating" is the exception leaving THIS block: sys.exc_info() is also set when the caller merely runs inside somebody's
+        # `except` block, and a genuine writer failure was then swallowed
+        self.close(propagating=exc_type is not None)
+
 
 _FETCH_STREAM = {}
 
@@ -228,29 +237,20 @@ def _fetch_and_save(save_dirs, t, stacked, ev, losses):
 def register_sequence(seg, step_matrices, step_cluster_np, save_dir=None, mlp_icp=False, models=None, loss_log=None):
     """Frames 1..T-1 of one sequence (the loop body of ``match``, mlp_reg.py:293-378), on arrays.
     Returns (list of (K,4,4) poses per frame incl. frame 0, best losses)."""
+    poses, best_losses = [np.asarray(step_matrices)], []
+    with _FileWriter() if save_dir is not None else contextlib.nullcontext() as writer:
+        _register_frames(seg, step_matrices, step_cluster_np, models=models, mlp_icp=mlp_icp, save_dir=save_dir, writer=writer,
+                         poses=poses, best_losses=best_losses)
+    return poses, best_losses
+
+
+def _register_frames(seg, step_matrices, step_cluster_np, *, models, mlp_icp, save_dir, writer, poses, best_losses):
     K = len(step_cluster_np)
     m_t = torch.tensor(np.asarray(step_matrices), dtype=torch.float32).to(DEVICE)
     cl_t = [torch.tensor(step_cluster_np[i], dtype=torch.float32).to(DEVICE) for i in range(K)]
     cl_init = [c.clone() for c in cl_t]
     icp_src = step_cluster_np            # mlp_reg.py:248/253: assigned once; masked_icp's source for EVERY frame (:325)
     model, model_rf = models if models is not None else _make_models()
-    poses, best_losses = [np.asarray(step_matrices)], []
-    writer = _FileWriter() if save_dir is not None else None
-    # (whether an exception of THIS frame loop is on its way out is tracked here: sys.exc_info() in a `finally` is also set when the
-    #  caller merely runs inside somebody's `except` block, and a genuine writer failure was then swallowed -- ADVICE r5)
-    failed = False
-    try:
-        _register_frames(seg, K, m_t, cl_t, cl_init, icp_src, model, model_rf, mlp_icp, save_dir, writer, poses, best_losses)
-    except BaseException:
-        failed = True
-        raise
-    finally:
-        if writer is not None:
-            writer.close(propagating=failed)
-    return poses, best_losses
-
-
-def _register_frames(seg, K, m_t, cl_t, cl_init, icp_src, model, model_rf, mlp_icp, save_dir, writer, poses, best_losses):
     for i in range(0, seg.data_size - 1):
         target_np = np.array(seg.pc_list[i + 1].points)
         target = torch.tensor(target_np, dtype=torch.float32).to(DEVICE)
@@ -278,25 +278,36 @@ def _register_frames(seg, K, m_t, cl_t, cl_init, icp_src, model, model_rf, mlp_i
             writer.submit(save_pc_npz, new_seg_np, save_dir + f"cluster/{(i + 1):04}.npz")
 
 
-def match(data_dir, idx):
-    """One sequence ("video"): frame-0 state (fresh k-means++ for the very first sequence, otherwise
-    reloaded from the first output directory, mlp_reg.py:242-253), then frames 1..T-1."""
-    save_dir_list = sorted(glob.glob(f"data/part/{ROBOT}_{NUM_SEG}_seg/{STEP_SZIE}_deg_{NUM_CAMERAS}_cams/*/"))
-    if len(save_dir_list) == 0:
+def _out_dir(data_dir=None):
+    """The run's output directory, or the one of the sequence read from `data_dir` inside it."""
+    base = f"data/part/{ROBOT}_{NUM_SEG}_seg/{STEP_SZIE}_deg_{NUM_CAMERAS}_cams/"
+    return base if data_dir is None else base + data_dir.split("/")[-2] + "/"
+
+
+def _frame0_state():
+    """The frame-0 state every sequence starts from (mlp_reg.py:242-253): (poses, clusters) reloaded from the first output directory,
+    or a fresh k-means++ of the first raw sequence when there is no output yet."""
+    done = sorted(glob.glob(_out_dir() + "*/"))
+    if len(done) == 0:
         seg0 = Segments(RAW_PATH_LIST[0])
         seg0.k_means_cluster(0, NUM_SEG, NORMAL)
-        step_matrices = np.array(seg0.init_matrix_list)
-        step_cluster_np = seg0.init_segment_list
-    else:
-        first_dir = save_dir_list[0]
-        step_matrices = np.load(first_dir + "matrix/0000.npy")
-        step_cluster_np = load_pc_npz(first_dir + "cluster/0000.npz")
-    sub_dir = data_dir.split("/")[-2]
-    save_dir = f"data/part/{ROBOT}_{NUM_SEG}_seg/{STEP_SZIE}_deg_{NUM_CAMERAS}_cams/{sub_dir}/"
+        return np.array(seg0.init_matrix_list), seg0.init_segment_list
+    return np.load(done[0] + "matrix/0000.npy"), load_pc_npz(done[0] + "cluster/0000.npz")
+
+
+def _write_frame0(save_dir, step_matrices, step_cluster_np):
     os.makedirs(save_dir + "cluster", exist_ok=True)
     os.makedirs(save_dir + "matrix", exist_ok=True)
     np.save(save_dir + "matrix/0000.npy", step_matrices)
     save_pc_npz(step_cluster_np, save_dir + "cluster/0000.npz")
+
+
+def match(data_dir, idx):
+    """One sequence ("video"): frame-0 state (fresh k-means++ for the very first sequence, otherwise
+    reloaded from the first output directory, mlp_reg.py:242-253), then frames 1..T-1."""
+    step_matrices, step_cluster_np = _frame0_state()
+    save_dir = _out_dir(data_dir)
+    _write_frame0(save_dir, step_matrices, step_cluster_np)
     seg = Segments(data_dir)
     _, best_losses = register_sequence(seg, step_matrices, step_cluster_np, save_dir, mlp_icp=MLP_ICP)
     if LOSS:
@@ -306,16 +317,8 @@ def match(data_dir, idx):
 def _ensure_frame0(first_dir):
     """The frame-0 state every sequence starts from (mlp_reg.py:242-253), written once into the first sequence's
     output directory if no output exists yet."""
-    base = f"data/part/{ROBOT}_{NUM_SEG}_seg/{STEP_SZIE}_deg_{NUM_CAMERAS}_cams/"
-    if sorted(glob.glob(base + "*/")):
-        return
-    seg0 = Segments(RAW_PATH_LIST[0])
-    seg0.k_means_cluster(0, NUM_SEG, NORMAL)
-    sd = base + first_dir.split("/")[-2] + "/"
-    os.makedirs(sd + "cluster", exist_ok=True)
-    os.makedirs(sd + "matrix", exist_ok=True)
-    np.save(sd + "matrix/0000.npy", np.array(seg0.init_matrix_list))
-    save_pc_npz(seg0.init_segment_list, sd + "cluster/0000.npz")
+    if not glob.glob(_out_dir() + "*/"):
+        _write_frame0(_out_dir(first_dir), *_frame0_state())
 
 
 def match_all(data_dirs):
@@ -327,42 +330,27 @@ def match_all(data_dirs):
     masked-ICP launch per step (mlp_reg.py:296-332)."""
     from .engine import BatchRegistrar
     segs = [Segments(d) for d in data_dirs]
-    same = len({(sg.data_size, len(sg.pc_list[0].points)) for sg in segs}) == 1 and \
-        all(len(p.points) == len(segs[0].pc_list[0].points) for sg in segs for p in sg.pc_list)
-    if not same or len(segs) < 1:
+    same = len({(sg.data_size, len(p.points)) for sg in segs for p in sg.pc_list}) == 1       # one length, one frame size
+    if same:
+        step_matrices, step_cluster_np = _frame0_state()
+        n = len(segs[0].pc_list[0].points)
+        # a frame-0 state from another run / the first raw sequence may hold another point count than these frames: "Anchor" (n0
+        # points) and "Step" (n points) would need two plan shapes -- match() keys its plans on both
+        same = sum(len(c) for c in step_cluster_np) == n
+    if not same:
         for i, d in enumerate(data_dirs):
             match(d, i)
         return
-    base = f"data/part/{ROBOT}_{NUM_SEG}_seg/{STEP_SZIE}_deg_{NUM_CAMERAS}_cams/"
-    done = sorted(glob.glob(base + "*/"))
-    if len(done) == 0:                                   # frame-0 state from the first raw sequence (mlp_reg.py:244-249)
-        seg0 = Segments(RAW_PATH_LIST[0])
-        seg0.k_means_cluster(0, NUM_SEG, NORMAL)
-        step_matrices, step_cluster_np = np.array(seg0.init_matrix_list), seg0.init_segment_list
-    else:
-        step_matrices, step_cluster_np = np.load(done[0] + "matrix/0000.npy"), load_pc_npz(done[0] + "cluster/0000.npz")
-    n = len(segs[0].pc_list[0].points)
-    if sum(len(c) for c in step_cluster_np) != n:
-        # the frame-0 state comes from another run / the first raw sequence and holds another point count than these
-        # frames: "Anchor" (n0 points) and "Step" (n points) would need two plan shapes -- match() keys its plans on both
-        for i, d in enumerate(data_dirs):
-            match(d, i)
-        return
-    save_dirs = [base + d.split("/")[-2] + "/" for d in data_dirs]
+    save_dirs = [_out_dir(d) for d in data_dirs]
     for sd in save_dirs:
-        os.makedirs(sd + "cluster", exist_ok=True)
-        os.makedirs(sd + "matrix", exist_ok=True)
-        np.save(sd + "matrix/0000.npy", step_matrices)
-        save_pc_npz(step_cluster_np, sd + "cluster/0000.npz")
+        _write_frame0(sd, step_matrices, step_cluster_np)
     models = [_make_models() for _ in segs]
     hidden = models[0][0].encoder[0].out_features        # 512, but 3 for --r rpy (RegMLP(6, 3), mlp_reg.py:285)
     reg = BatchRegistrar(np.asarray(step_matrices, np.float32), [np.asarray(c, np.float64) for c in step_cluster_np], n,
                          len(segs), ROT, hidden, EPOCHS, USE_GRAPH, DEVICE, models=models)
     reg.normal = NORMAL                                  # --normal: the re-segmentation over [xyz | 0.5 n], per sequence, inside the lock-step round
     losses = [[] for _ in segs]
-    writer = _FileWriter()
-    failed = False
-    try:
+    with _FileWriter() as writer:
         for i in range(segs[0].data_size - 1):
             frames = [torch.as_tensor(np.asarray(sg.pc_list[i + 1].points), dtype=torch.float64, device=DEVICE) for sg in segs]
             out = reg.step_mlp_icp(frames) if MLP_ICP else reg.step(frames)
@@ -374,11 +362,6 @@ def match_all(data_dirs):
             ev = torch.cuda.Event()
             ev.record()
             writer.submit(_fetch_and_save, save_dirs, i + 1, stacked, ev, losses)
-    except BaseException:
-        failed = True
-        raise
-    finally:
-        writer.close(propagating=failed)
     if LOSS:
         for sd, l in zip(save_dirs, losses):
             np.savetxt(sd + "loss.txt", l)

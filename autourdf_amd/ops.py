@@ -179,6 +179,13 @@ def knn_normals(X: torch.Tensor, radius: float, max_nn: int, want_normals: bool 
 
 KMEANS_ND_MAX_N, KMEANS_ND_MAX_K = (1 << 24) - 1, 128      # creg_kmeans_lloyd_nd_f64: one workgroup, centres in LDS (labels too up to 16384 points, in the workspace above)
 KMEANS_BATCH_MAX_N = 16384         # labels + centres in one CU's LDS; the frame too up to 5120 points, from L2 above
+KMEANS_BATCH_MAX, KMEANS_BATCH_MAX_K = 16, 128             # frames per launch (KMS_MAXB in kmeans.hip), centres in LDS
+
+
+def _batchable(limit, *lists):
+    """The `_each` helpers' rule: 1..limit problems, and every problem has the shapes of the first."""
+    B = len(lists[0])
+    return 1 <= B <= limit and all(len(l) == B and all(t.shape == l[0].shape for t in l) for l in lists)
 
 
 def kmeans_lloyd_batch(Xs, inits, max_iter: int = 300, tol: float = 1e-4):
@@ -200,6 +207,13 @@ def kmeans_lloyd_batch(Xs, inits, max_iter: int = 300, tol: float = 1e-4):
                                              arr([o[1] for o in outs]), arr([o[2] for o in outs]), arr([o[3] for o in outs]),
                                              _p(ws), ws_bytes, _stream()), "creg_kmeans_lloyd_batch_f64")
     return outs
+
+
+def kmeans_lloyd_each(Xs, inits):
+    """`kmeans_lloyd_batch` where the frames fit one launch, `kmeans_lloyd` per frame, in order, otherwise."""
+    if _batchable(KMEANS_BATCH_MAX, Xs, inits) and Xs[0].shape[0] <= KMEANS_BATCH_MAX_N and inits[0].shape[0] <= KMEANS_BATCH_MAX_K:
+        return kmeans_lloyd_batch(Xs, inits)
+    return [kmeans_lloyd(X, c) for X, c in zip(Xs, inits)]
 
 
 def kmeans_assign(X: torch.Tensor, C: torch.Tensor, use_mfma: bool = False) -> torch.Tensor:
@@ -245,6 +259,13 @@ def group_to_local_batch(Xs, labels, Ms, m_is_inverse: bool = False):
     _lib.check(L.creg_group_to_local_batch_f64(arr(Xs), n, arr(labels), k, arr(Ms), int(bool(m_is_inverse)), B, arr([o[0] for o in outs]),
                                                arr([o[1] for o in outs]), _stream()), "creg_group_to_local_batch_f64")
     return outs
+
+
+def group_to_local_each(Xs, labels, Ms, m_is_inverse: bool = False):
+    """`group_to_local_batch` where the frames fit one pair of launches, `group_to_local` per frame, in order, otherwise."""
+    if _batchable(GROUP_BATCH_MAX, Xs, labels, Ms):
+        return group_to_local_batch(Xs, labels, Ms, m_is_inverse=m_is_inverse)
+    return [group_to_local(X, l, M, m_is_inverse=m_is_inverse) for X, l, M in zip(Xs, labels, Ms)]
 
 
 def icp_p2p_batch(problems, th: float = 1.0, max_iteration: int = 100000):
@@ -941,6 +962,19 @@ def masked_icp_batch(problems, scale: float = 1.2, th: float = 1.0, max_iteratio
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     _lib.check(L.creg_masked_icp_batch_f64(arr, B, n, k, nf, float(scale), float(th), int(max_iteration),
                                            int(bool(ori)), _p(ws), ws_bytes, _stream()), "creg_masked_icp_batch_f64")
+    return outs
+
+
+def masked_icp_each(problems):
+    """`masked_icp_batch` where its (local, world, offsets, frame, M[, world_offsets]) problems fit one launch, `masked_icp` per
+    problem, in order, otherwise (`world` None: the clusters in their current pose, evaluated here by `cluster_transform`)."""
+    if 1 <= len(problems) <= ICP_BATCH_MAX and len({(p[0].shape, p[2].shape, p[3].shape) for p in problems}) == 1:
+        return masked_icp_batch(problems)
+    outs = []
+    for local, world, offsets, frame, M, *woff in problems:
+        if world is None:
+            world = cluster_transform(local.to(torch.float32), offsets, M.to(torch.float32))
+        outs.append(masked_icp(local, world, offsets, frame, M, world_offsets=woff[0] if woff else None))
     return outs
 
 

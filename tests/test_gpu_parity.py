@@ -577,6 +577,26 @@ def test_batch_icp_registrar_equals_separate_registrars(dev):
         assert torch.equal(r.local, b.local) and torch.equal(r.off, b.off)
 
 
+def test_batch_icp_registrar_with_unequal_frame_sizes_equals_separate_registrars(dev):
+    """Frames of 2048 and 1536 points cannot share a launch: every stage takes its per-sequence form, which is the calls
+    IcpRegistrar.step makes."""
+    from autourdf_amd.engine import BatchIcpRegistrar, IcpRegistrar
+    from autourdf_amd.synthetic import initial_segmentation, make_sequence
+    seqs = [make_sequence("wx200_5", 40 + s, 3, n) for s, n in enumerate((2048, 1536))]
+    mats, clusters, _ = initial_segmentation(seqs[0][0], 12, seed=3)
+    breg = BatchIcpRegistrar(mats, clusters, 2, dev)
+    singles = [IcpRegistrar(mats, clusters, dev) for _ in range(2)]
+    for f in (1, 2):
+        frames = [torch.as_tensor(s[f], dtype=torch.float64, device=dev) for s in seqs]
+        assert [fr.shape[0] for fr in frames] == [2048, 1536]
+        outs = breg.step(frames)
+        for r, fr, o in zip(singles, frames, outs):
+            M, dq, it = r.step(fr)
+            assert torch.equal(M, o[0]) and torch.equal(dq, o[1]) and torch.equal(it, o[2])
+    for r, b in zip(singles, breg.regs):
+        assert torch.equal(r.local, b.local) and torch.equal(r.off, b.off)
+
+
 # ------------------------------------------------------------------------------------------ A1
 def _train_case(golden, rot):
     g = golden("train_reference.npz")

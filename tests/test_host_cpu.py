@@ -285,12 +285,12 @@ def test_register_sequence_surfaces_a_writer_failure_inside_a_callers_except_blo
     def boom():
         raise ValueError("disk full")
 
-    def frames_ok(seg, K, m_t, cl_t, cl_init, icp_src, model, model_rf, mlp_icp, save_dir, writer, poses, best_losses):
+    def frames_ok(*a, writer, **kw):
         writer.submit(boom)
         time.sleep(0.2)
 
-    def frames_fail(*a):
-        a[10].submit(boom)
+    def frames_fail(*a, writer, **kw):
+        writer.submit(boom)
         time.sleep(0.2)
         raise KeyError("the frame loop's own error")
 
@@ -305,3 +305,203 @@ def test_register_sequence_surfaces_a_writer_failure_inside_a_callers_except_blo
     monkeypatch.setattr(mlp_reg, "_register_frames", frames_fail)
     with pytest.raises(KeyError):
         mlp_reg.register_sequence(*args, save_dir=str(tmp_path) + "/", models=(None, None))
+
+
+def test_file_writer_as_a_context_manager_reports_the_exception_leaving_its_own_block():
+    """`with _FileWriter()`: a worker error surfaces on leaving the block, never replaces an exception raised inside it, and does
+    surface when the block merely runs inside a caller's `except` (the exception leaving THIS block counts, not sys.exc_info())."""
+    import time
+    from autourdf_amd import mlp_reg
+
+    def boom():
+        raise ValueError("disk full")
+
+    done = []
+    with mlp_reg._FileWriter() as w:
+        w.submit(done.append, 1)
+    assert done == [1] and not w._t.is_alive()
+    with pytest.raises(ValueError, match="disk full"):
+        with mlp_reg._FileWriter() as w:
+            w.submit(boom)
+            time.sleep(0.2)
+    assert not w._t.is_alive()
+    with pytest.raises(KeyError):
+        with mlp_reg._FileWriter() as w:
+            w.submit(boom)
+            time.sleep(0.2)
+            raise KeyError("the frame loop's own error")
+    assert not w._t.is_alive()
+    with pytest.raises(ValueError, match="disk full"):
+        try:
+            raise RuntimeError("the caller is handling something else")
+        except RuntimeError:
+            with mlp_reg._FileWriter() as w:
+                w.submit(boom)
+                time.sleep(0.2)
+
+
+def _frame0_globals(monkeypatch, tmp_path, segments):
+    from autourdf_amd import mlp_reg
+    monkeypatch.chdir(tmp_path)
+    for name, v in dict(ROBOT="toy", NUM_SEG=3, STEP_SZIE=4, NUM_CAMERAS=20, NORMAL=False,
+                        RAW_PATH_LIST=["data/raw/toy/4_deg_20_cams/V0000/", "data/raw/toy/4_deg_20_cams/V0001/"]).items():
+        monkeypatch.setattr(mlp_reg, name, v, raising=False)
+    monkeypatch.setattr(mlp_reg, "Segments", segments)
+    return mlp_reg, "data/part/toy_3_seg/4_deg_20_cams/"
+
+
+def _files_under(root):
+    return sorted(os.path.relpath(os.path.join(d, f), root) for d, _, fs in os.walk(root) for f in fs)
+
+
+def test_frame0_state_is_reloaded_from_the_first_output_directory(monkeypatch, tmp_path):
+    def no_segments(path):
+        raise AssertionError("an existing output directory must be reloaded, not recomputed")
+
+    mlp_reg, base = _frame0_globals(monkeypatch, tmp_path, no_segments)
+    rng = np.random.default_rng(0)
+    mats, clusters = rng.normal(size=(3, 4, 4)), [rng.normal(size=(n, 3)) for n in (5, 2, 7)]
+    assert mlp_reg._out_dir() == base and mlp_reg._out_dir("data/raw/toy/4_deg_20_cams/V0001/") == base + "V0001/"
+    mlp_reg._write_frame0(base + "V0001/", mats, clusters)
+    os.makedirs(base + "V0002")                           # a later directory without a frame-0 state: the FIRST one is read
+    before = _files_under(tmp_path)
+    assert before == [base + "V0001/cluster/0000.npz", base + "V0001/matrix/0000.npy"]
+    m, c = mlp_reg._frame0_state()
+    np.testing.assert_array_equal(m, np.load(base + "V0001/matrix/0000.npy"))
+    np.testing.assert_array_equal(m, mats)
+    with np.load(base + "V0001/cluster/0000.npz") as z:
+        assert list(z.keys()) == ["0", "1", "2"] and len(c) == 3
+        for i in range(3):
+            np.testing.assert_array_equal(c[i], z[str(i)])
+            np.testing.assert_array_equal(c[i], clusters[i])
+    mlp_reg._ensure_frame0("data/raw/toy/4_deg_20_cams/V0000/")
+    assert _files_under(tmp_path) == before               # nothing written
+
+
+def test_frame0_state_is_computed_from_the_first_raw_sequence_and_written_once(monkeypatch, tmp_path):
+    made = []
+
+    class StubSegments:
+        def __init__(self, path):
+            made.append(path)
+
+        def k_means_cluster(self, idx, n_seg, normal):
+            made.append((idx, n_seg, normal))
+            self.init_matrix_list = [np.eye(4) * (i + 1) for i in range(n_seg)]
+            self.init_segment_list = [np.full((i + 2, 3), float(i)) for i in range(n_seg)]
+
+    mlp_reg, base = _frame0_globals(monkeypatch, tmp_path, StubSegments)
+    m, c = mlp_reg._frame0_state()
+    assert made == ["data/raw/toy/4_deg_20_cams/V0000/", (0, 3, False)] and _files_under(tmp_path) == []
+    assert m.shape == (3, 4, 4) and m[2, 0, 0] == 3.0 and [x.shape[0] for x in c] == [2, 3, 4]
+    mlp_reg._ensure_frame0("data/raw/toy/4_deg_20_cams/V0007/")      # written under the name of the sequence it is given
+    assert _files_under(tmp_path) == [base + "V0007/cluster/0000.npz", base + "V0007/matrix/0000.npy"]
+    np.testing.assert_array_equal(np.load(base + "V0007/matrix/0000.npy"), m)
+    for a, b in zip(mlp_reg.load_pc_npz(base + "V0007/cluster/0000.npz"), c):
+        np.testing.assert_array_equal(a, b)
+    n_made = len(made)
+    mlp_reg._ensure_frame0("data/raw/toy/4_deg_20_cams/V0008/")      # output exists now: neither computed nor written again
+    assert len(made) == n_made and not os.path.exists(base + "V0008")
+
+
+def _record(monkeypatch, ops, names):
+    """Replace ops.<name> by recorders: calls = [(name, args, kwargs)], each returning (name, index of the call)."""
+    calls = []
+    for name in names:
+        def rec(*a, _name=name, **kw):
+            calls.append((_name, a, kw))
+            return (_name, len(calls) - 1)
+        monkeypatch.setattr(ops, name, rec)
+    return calls
+
+
+def test_kmeans_lloyd_each_takes_the_batch_launch_exactly_up_to_its_limits(monkeypatch):
+    import torch
+    from autourdf_amd import ops
+    assert (ops.KMEANS_BATCH_MAX, ops.KMEANS_BATCH_MAX_N, ops.KMEANS_BATCH_MAX_K) == (16, 16384, 128)
+    calls = _record(monkeypatch, ops, ["kmeans_lloyd_batch", "kmeans_lloyd"])
+
+    def case(B, n, k, ns=None):
+        Xs = [torch.zeros(n if ns is None else ns[b], 3, dtype=torch.float64) for b in range(B)]
+        inits = [torch.zeros(k, 3, dtype=torch.float64) for _ in range(B)]
+        del calls[:]
+        return Xs, inits, ops.kmeans_lloyd_each(Xs, inits)
+
+    for B, n, k in ((16, 16384, 128), (1, 7, 1)):
+        Xs, inits, out = case(B, n, k)
+        assert out == ("kmeans_lloyd_batch", 0) and len(calls) == 1
+        assert calls[0][1][0] is Xs and calls[0][1][1] is inits and calls[0][2] == {}
+    for B, n, k, ns in ((17, 64, 4, None), (2, 16385, 4, None), (2, 64, 129, None), (2, None, 4, (64, 48))):
+        Xs, inits, out = case(B, n, k, ns)
+        assert out == [("kmeans_lloyd", b) for b in range(B)]
+        for b, (name, a, kw) in enumerate(calls):
+            assert name == "kmeans_lloyd" and a[0] is Xs[b] and a[1] is inits[b] and len(a) == 2 and kw == {}
+    assert ops.kmeans_lloyd_each([], []) == []
+
+
+def test_group_to_local_each_takes_the_batch_launch_exactly_up_to_its_limit(monkeypatch):
+    import torch
+    from autourdf_amd import ops
+    assert ops.GROUP_BATCH_MAX == 16
+    calls = _record(monkeypatch, ops, ["group_to_local_batch", "group_to_local"])
+
+    def case(ns, inverse):
+        Xs = [torch.zeros(n, 3, dtype=torch.float64) for n in ns]
+        labels = [torch.zeros(n, dtype=torch.int32) for n in ns]
+        Ms = [torch.zeros(5, 4, 4, dtype=torch.float64) for _ in ns]
+        del calls[:]
+        return Xs, labels, Ms, ops.group_to_local_each(Xs, labels, Ms, m_is_inverse=inverse)
+
+    for inverse in (False, True):
+        Xs, labels, Ms, out = case([40] * 16, inverse)
+        assert out == ("group_to_local_batch", 0) and len(calls) == 1
+        assert [x is y for x, y in zip(calls[0][1], (Xs, labels, Ms))] == [True] * 3 and calls[0][2] == {"m_is_inverse": inverse}
+        for ns in ([40] * 17, [40, 24]):
+            Xs, labels, Ms, out = case(ns, inverse)
+            assert out == [("group_to_local", b) for b in range(len(ns))]
+            for b, (name, a, kw) in enumerate(calls):
+                assert name == "group_to_local" and kw == {"m_is_inverse": inverse}
+                assert len(a) == 3 and a[0] is Xs[b] and a[1] is labels[b] and a[2] is Ms[b]
+
+
+def test_masked_icp_each_takes_the_batch_launch_exactly_up_to_its_limit(monkeypatch):
+    import inspect
+    import torch
+    from autourdf_amd import ops
+    assert ops.ICP_BATCH_MAX == 16
+    signature = inspect.signature(ops.masked_icp)
+    calls = _record(monkeypatch, ops, ["masked_icp_batch", "masked_icp", "cluster_transform"])
+
+    def problems(ns, world="given", woff=False):
+        out = []
+        for n in ns:
+            p = (torch.zeros(n, 3, dtype=torch.float64), torch.zeros(n, 3) if world == "given" else None,
+                 torch.zeros(6, dtype=torch.int32), torch.zeros(50, 3, dtype=torch.float64), torch.ones(5, 4, 4, dtype=torch.float64))
+            out.append(p + (torch.ones(6, dtype=torch.int32),) if woff else p)
+        del calls[:]
+        return out
+
+    for world, woff in (("given", False), ("given", True), (None, False)):
+        probs = problems([40] * 16, world, woff)
+        assert ops.masked_icp_each(probs) == ("masked_icp_batch", 0)
+        assert len(calls) == 1 and len(calls[0][1]) == 1 and calls[0][1][0] is probs and calls[0][2] == {}
+    for ns in ([40] * 17, [40, 24]):
+        # six-tuples (the --mlp_icp frame): world_offsets arrives in masked_icp's `world_offsets`, `scale` keeps its default
+        probs = problems(ns, "given", True)
+        assert ops.masked_icp_each(probs) == [("masked_icp", b) for b in range(len(ns))]
+        for p, (name, a, kw) in zip(probs, calls):
+            bound = signature.bind(*a, **kw)
+            assert name == "masked_icp" and "scale" not in bound.arguments and bound.arguments["world_offsets"] is p[5]
+            assert [bound.arguments[k] is v for k, v in zip(("local", "world", "offsets", "frame", "M"), p)] == [True] * 5
+        # world None (BatchIcpRegistrar): the boxes are cluster_transform of the float32 casts, made right before each ICP
+        probs = problems(ns, None)
+        assert ops.masked_icp_each(probs) == [("masked_icp", 2 * b + 1) for b in range(len(ns))]
+        assert [c[0] for c in calls] == ["cluster_transform", "masked_icp"] * len(ns)
+        for b, p in enumerate(probs):
+            (_, ta, tkw), (_, a, kw) = calls[2 * b], calls[2 * b + 1]
+            assert tkw == {} and len(ta) == 3 and ta[1] is p[2]
+            assert ta[0].dtype == torch.float32 and ta[0].shape == p[0].shape and ta[2].dtype == torch.float32 and torch.equal(ta[2], p[4].float())
+            bound = signature.bind(*a, **kw)
+            assert bound.arguments["world"] == ("cluster_transform", 2 * b) and bound.arguments.get("world_offsets") is None
+            assert "scale" not in bound.arguments
+            assert [bound.arguments[k] is p[i] for k, i in (("local", 0), ("offsets", 2), ("frame", 3), ("M", 4))] == [True] * 4
