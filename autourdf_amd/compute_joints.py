@@ -212,3 +212,33 @@ def create_urdf(links, joint_data, cm, output_file="robot.urdf", mesh_dir="", ti
         os.makedirs(os.path.dirname(output_file), exist_ok=True)
     tree.write(output_file, encoding="utf-8", xml_declaration=True)
     print(f"URDF file saved as {output_file}")
+
+
+def set_inertials(urdf_file, inertials):
+    """Rewrite the <inertial> block of every link that ``inertials`` names (this project's own; ``link.link_inertia`` computes
+    the values): inertials = {link name: {"mass", "com" (3), "inertia" (ixx, ixy, ixz, iyy, iyz, izz about com)}} in the
+    MESH's frame.  The link's <visual><origin> (xyz t, rpy -> R, URDF's fixed-axis roll-pitch-yaw) maps the mesh into the link
+    frame: origin xyz = R com + t with rpy 0 0 0, inertia = R I R^T.  Links not named keep their block; every other element,
+    the indentation and the XML declaration stay as ``create_urdf`` wrote them.  A named link must already hold the block
+    ``create_urdf`` writes -- <inertial> with <origin>, <mass> and <inertia> -- since only attributes are rewritten:
+    ValueError naming the link otherwise, KeyError for a name the file does not have; nothing is written in either case."""
+    tree = ET.parse(urdf_file)
+    by_name = {l.get("name"): l for l in tree.getroot().findall("link")}
+    for name, val in inertials.items():
+        link = by_name[name]
+        origin = link.find("visual/origin")
+        attr = origin.attrib if origin is not None else {}         # URDF's defaults: no origin, or no attribute, is zero
+        t = np.array(attr.get("xyz", "0 0 0").split(), np.float64)
+        rpy = np.array(attr.get("rpy", "0 0 0").split(), np.float64)
+        Rm = R.from_euler("xyz", rpy).as_matrix()                  # extrinsic x, y, z: Rz(yaw) Ry(pitch) Rx(roll)
+        ixx, ixy, ixz, iyy, iyz, izz = np.asarray(val["inertia"], np.float64)
+        I = Rm @ np.array([[ixx, ixy, ixz], [ixy, iyy, iyz], [ixz, iyz, izz]]) @ Rm.T
+        com = Rm @ np.asarray(val["com"], np.float64) + t
+        inertial = link.find("inertial")
+        if inertial is None or any(inertial.find(k) is None for k in ("origin", "mass", "inertia")):
+            raise ValueError(f"{urdf_file}: link {name} has no <inertial> block with <origin>, <mass> and <inertia> to rewrite")
+        inertial.find("origin").attrib.update(xyz=" ".join(map(str, com)), rpy=" ".join(map(str, np.zeros(3))))
+        inertial.find("mass").set("value", str(float(val["mass"])))
+        inertial.find("inertia").attrib.update(ixx=str(I[0, 0]), ixy=str(I[0, 1]), ixz=str(I[0, 2]), iyy=str(I[1, 1]),
+                                               iyz=str(I[1, 2]), izz=str(I[2, 2]))
+    tree.write(urdf_file, encoding="utf-8", xml_declaration=True)

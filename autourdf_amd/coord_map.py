@@ -384,9 +384,11 @@ def _parser():
 
 
 def _cli_parser():
-    """The reference's flags plus this project's own: --voxel_size meshes the links (it overrides parameters.json's key)."""
+    """The reference's flags plus this project's own: --voxel_size meshes the links and --density (kg/m^3) fills the URDF's
+    inertial blocks from those meshes (each overrides parameters.json's key of the same name)."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
+    parser.add_argument('--density', type=float, default=None)
     return parser
 
 
@@ -395,19 +397,25 @@ def main(argv=None):
     discovery, kinematic tree, joint axes, link clouds, their ICP refinement, the link meshes and the URDF file.  Paths
     are the reference's, relative to the working directory, and ``parameters.json`` is read from there.  The links are
     meshed (``{i:04}.ply`` and ``{i:04}.stl`` in the link directory, the files the URDF names) when the robot's entry has a
-    ``voxel_size`` or ``--voxel_size`` is given; the option wins."""
+    ``voxel_size`` or ``--voxel_size`` is given; the option wins.  With a ``density`` (the key or ``--density``, kg/m^3; the
+    option wins) the meshes' mass properties replace the placeholder ``<inertial>`` blocks (``link_inertia``,
+    ``set_inertials``); a density without a voxel size is a ValueError before anything is written."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import create_urdf, estimate_joint_axes_from_tree
-    from .link import link_mesh, refine_links_clusters, save_links, visualize_links
+    from .compute_joints import create_urdf, estimate_joint_axes_from_tree, set_inertials
+    from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("autourdf_amd.coord_map needs an MI355X: no GPU is visible and there is no CPU path")
     with open('parameters.json') as f:
         robot_params = json.load(f)[args.robot]
+    voxel_size = args.voxel_size if args.voxel_size is not None else robot_params.get('voxel_size')
+    density = args.density if args.density is not None else robot_params.get('density')
+    if density is not None and voxel_size is None:
+        raise ValueError("a density needs the link meshes: give --voxel_size (or a voxel_size key in parameters.json) with it")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -454,17 +462,19 @@ def main(argv=None):
     sub_link_path = [link_path + path.split('/')[-2] + '/' for path in sub_part_path][:1]
     save_links(cm_list, cluster_idx, sub_link_path, START, END)
     refine_links_clusters(sub_link_path, START, END, dof)
-    voxel_size = args.voxel_size if args.voxel_size is not None else robot_params.get('voxel_size')
     if voxel_size is None:
         print("skipped (out of scope): the cluster / link viewers and plots, visualize_links, link_mesh (meshing), "
               "visualize_kinematic_tree and visualize_urdf")
     else:
         visualize_links(sub_link_path, START, END, dof, False)
         link_mesh(sub_link_path, dof, voxel_size, False)
+        inertials = link_inertia(sub_link_path, dof, density) if density is not None else None
         print("skipped (out of scope): the cluster / link viewers and plots, visualize_kinematic_tree and visualize_urdf")
     os.makedirs(f'data/urdf/{ROBOT}_{NUM_SEG}_seg/', exist_ok=True)
     urdf_path = f'data/urdf/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams.urdf'
     create_urdf(links, joint_data, cm_list[0], urdf_path, sub_link_path[0])
+    if density is not None:
+        set_inertials(urdf_path, inertials[0])
     return urdf_path
 
 

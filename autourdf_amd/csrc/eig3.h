@@ -80,4 +80,51 @@ __device__ inline void smallest_eigvec(const double Cin[6], double* nrm) {
     }
 }
 
+// All three eigenpairs of the symmetric 3x3 A = (a00, a01, a02, a11, a12, a22) by cyclic Jacobi rotations: w ascending, row k of
+// V (row-major 3x3) the unit eigenvector of w[k], its largest component positive for k = 0, 1 and row 2 = row 0 x row 1.
+// smallest_eigvec's closed form keeps half the digits of two nearly equal eigenvalues (acos near +-1), which every symmetric
+// body has; rotations keep all of them.  Eight sweeps of (0,1), (0,2), (1,2), a zero pivot skipped; a NaN in A gives NaNs.
+__device__ inline void sym3_eig_jacobi(const double A[6], double* w, double* V) {
+    double a[3][3] = {{A[0], A[1], A[2]}, {A[1], A[3], A[4]}, {A[2], A[4], A[5]}};
+    double v[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};         // columns: eigenvectors
+    for (int sweep = 0; sweep < 8; ++sweep) {
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2, r = 3 - p - q;
+            const double apq = a[p][q];
+            if (apq == 0.0) continue;
+            const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+            const double t = (theta < 0.0 ? -1.0 : 1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+            a[p][p] = a[p][p] - t * apq;
+            a[q][q] = a[q][q] + t * apq;
+            a[p][q] = a[q][p] = 0.0;
+            const double arp = a[r][p], arq = a[r][q];
+            a[r][p] = a[p][r] = c * arp - s * arq;
+            a[r][q] = a[q][r] = s * arp + c * arq;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double vkp = v[k][p], vkq = v[k][q];
+                v[k][p] = c * vkp - s * vkq;
+                v[k][q] = s * vkp + c * vkq;
+            }
+        }
+    }
+    int o0 = 0, o1 = 1, o2 = 2, tmp;                             // ascending, ties keep their column order
+    if (a[o1][o1] < a[o0][o0]) { tmp = o0; o0 = o1; o1 = tmp; }
+    if (a[o2][o2] < a[o1][o1]) { tmp = o1; o1 = o2; o2 = tmp; }
+    if (a[o1][o1] < a[o0][o0]) { tmp = o0; o0 = o1; o1 = tmp; }
+    const int order[3] = {o0, o1, o2};
+    for (int k = 0; k < 3; ++k) {
+        const int col = order[k];
+        w[k] = a[col][col];
+        double e[3] = {v[0][col], v[1][col], v[2][col]};
+        int big = fabs(e[1]) > fabs(e[0]) ? 1 : 0;
+        if (fabs(e[2]) > fabs(e[big])) big = 2;
+        const double sign = e[big] < 0.0 ? -1.0 : 1.0;
+        for (int i = 0; i < 3; ++i) V[3 * k + i] = sign * e[i];
+    }
+    cross3(V, V + 3, V + 6);
+}
+
 }  // namespace creg

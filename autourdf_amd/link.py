@@ -145,3 +145,35 @@ def link_mesh(path_list, dof, vsize, vis_flow):
         meshes = ops.voxel_mesh(pts, off, vsize, smooth=True, keep=keep)
         for i, m in enumerate(meshes):
             write_stl(link_dir + f'{i:04}.stl', m["stl_records"].cpu().numpy())
+
+
+def link_inertia(path_list, dof, density, closure_tol=1e-9):
+    """Mass properties of the meshes ``link_mesh`` wrote (this project's own; DESIGN N4): the {i:04}.stl files of every
+    directory go through one ``ops.mesh_inertia`` call, density (kg/m^3) a scalar or one value per link.  Writes
+    ``inertial.json`` into the directory and returns, per directory, {"link_{i}": {mass, volume, com, inertia, principal}} with
+    com (3) and inertia (ixx, ixy, ixz, iyy, iyz, izz, about com) in the mesh's frame -- what ``set_inertials`` takes.
+    ValueError naming the file for a mesh whose volume is not positive (inward-oriented or empty) or whose closure
+    |sum n| / sum |n| exceeds closure_tol: rounding leaves a few 2^-53 log2 F there, one missing facet of F about 1 / F."""
+    import json
+    dev = _lib.device()
+    out = []
+    for link_dir in path_list:
+        files = [link_dir + f'{i:04}.stl' for i in range(dof + 1)]
+        # the float32 vertices go to f64 unchanged, so vertices shared by facets stay identical and the surface closed
+        tris = [read_stl(f)[:, 1:4].astype(np.float64) for f in files]
+        start = np.concatenate([[0], np.cumsum([len(t) for t in tris])]).astype(np.int64)
+        res = ops.mesh_inertia(torch.as_tensor(np.concatenate(tris).reshape(-1, 3, 3), device=dev).contiguous(),
+                               torch.as_tensor(start, device=dev), density)
+        res = {k: res[k].cpu().numpy() for k in ("mass", "volume", "closure", "com", "inertia", "principal")}
+        links = {}
+        for i, f in enumerate(files):
+            if not res["volume"][i] > 0:
+                raise ValueError(f"{f}: volume {res['volume'][i]} is not positive -- the mesh is empty or oriented inwards")
+            if not res["closure"][i] <= closure_tol:
+                raise ValueError(f"{f}: the surface is not closed (|sum n| / sum |n| = {res['closure'][i]:.3e} > {closure_tol})")
+            links[f"link_{i}"] = {"mass": float(res["mass"][i]), "volume": float(res["volume"][i]), "com": res["com"][i].tolist(),
+                                  "inertia": res["inertia"][i].tolist(), "principal": res["principal"][i].tolist()}
+        with open(link_dir + 'inertial.json', 'w') as fh:
+            json.dump(links, fh, indent=1)
+        out.append(links)
+    return out

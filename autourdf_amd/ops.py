@@ -531,6 +531,39 @@ def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
     return (count, first, boxes) if want_boxes else (count, first)
 
 
+MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")
+
+
+def mesh_inertia(tri, tri_start, density=1.0):
+    """Mass properties of closed link meshes (creg_mesh_inertia_f64; the contract is in include/creg.h): tri (F,3,3) f64 and
+    tri_start (L+1) int64 on the device, as ``mesh_collide`` takes them, density a scalar or (L) -> a dict of device tensors:
+    sums (L,14), volume, area, closure, mass (L), com (L,3), inertia (L,6) = ixx ixy ixz iyy iyz izz about com, principal (L,3)
+    ascending and axes (L,3,3).  One set of launches for all L; nothing is read back, so only shapes and dtypes raise (the
+    kernel clamps tri_start into 0 .. F)."""
+    L = _lib.load()
+    tri, tri_start = _need(tri, torch.float64, "tri"), _need(tri_start, torch.int64, "tri_start")
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or tri_start.dim() != 1 or tri_start.shape[0] < 2:
+        raise ValueError(f"mesh_inertia: tri (F,3,3) / tri_start (L+1) with L >= 1 expected, got {tuple(tri.shape)}, "
+                         f"{tuple(tri_start.shape)}")
+    F, n_links, dev = tri.shape[0], tri_start.shape[0] - 1, tri.device
+    if isinstance(density, torch.Tensor):
+        density = _need(density, torch.float64, "density")
+        if density.dim() == 0:
+            density = density.expand(n_links).contiguous()
+    else:
+        density = torch.as_tensor(np.full(n_links, float(density)) if np.ndim(density) == 0
+                                  else np.ascontiguousarray(density, np.float64), device=dev)
+    if tuple(density.shape) != (n_links,):
+        raise ValueError(f"mesh_inertia: density must be a scalar or ({n_links}), got {tuple(density.shape)}")
+    shapes = dict(sums=(14,), volume=(), area=(), closure=(), mass=(), com=(3,), inertia=(6,), principal=(3,), axes=(3, 3))
+    out = {k: torch.empty((n_links,) + shapes[k], dtype=torch.float64, device=dev) for k in MESH_INERTIA_KEYS}
+    ws_bytes = L.creg_mesh_inertia_workspace_bytes(F, n_links)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    _lib.check(L.creg_mesh_inertia_f64(_p(tri) if F else None, _p(tri_start), F, n_links, _p(density), *[_p(out[k]) for k in MESH_INERTIA_KEYS],
+                                       _p(ws), ws_bytes, _stream()), "creg_mesh_inertia_f64")
+    return out
+
+
 # ------------------------------------------------------------------------------ N2 pose distance maps
 def coord_dist_map(M: torch.Tensor, bounding_box: float, diff: bool = True):
     """CoordMap.coord_dist_map (coord_map.py:230-307) for poses M (T,K,4,4) f64 on the device:

@@ -547,6 +547,51 @@ int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start, int64_t n
                           double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mass properties of closed, outward-oriented link meshes: every link of a call in one set of launches, no host
+ * synchronisation.  The reference writes mass 1.0, ixx = iyy = izz = 0.1 and the visual's origin into every <inertial> block
+ * ("example values, adjust as needed", PointCloud/compute_joints.py:334-339); this contract is the project's own.
+ *   geometry   tri (n_tri,9) fp64 and tri_start (n_links+1) int64 as creg_mesh_collide_f64 takes them (values outside
+ *              0 .. n_tri are clamped, nothing outside tri is read); density (n_links) fp64.
+ *   triangle   with r = the first vertex of the link's first triangle: a = v0 - r, b = v1 - r, c = v2 - r, e1 = b - a,
+ *              e2 = c - a, s = (a + b) + c, cross(u,v) = (u_y*v_z - u_z*v_y, u_z*v_x - u_x*v_z, u_x*v_y - u_y*v_x),
+ *              n = cross(e1,e2), g = cross(b,c), d = (a_x*g_x + a_y*g_y) + a_z*g_z, and the 14 terms
+ *                0..2   n_x, n_y, n_z              3   sqrt((n_x*n_x + n_y*n_y) + n_z*n_z)              4   d
+ *                5..7   d*s_x, d*s_y, d*s_z        8..13   d*(((s_i*s_j + a_i*a_j) + b_i*b_j) + c_i*c_j), ij = xx xy xz yy yz zz
+ *              -- in exactly this order, no contraction.  The longest path of a term has 8 roundings (a_i, a_i + b_i, s_i,
+ *              s_i*s_j, the three additions behind it, the product with d; d itself is 6 deep).
+ *   sums       sums (n_links,14): the terms of the link's triangles added in a tree that depends on the link's triangle
+ *              count alone.  Leaves are the triangles in order, padded with zeros to a multiple of 256; every 256 leaves go
+ *              through: four groups of 64, each summed as a butterfly (x_i + x_(i^32), then ^16 ... ^1), then
+ *              ((w0 + w1) + w2) + w3 -- depth 9.  The per-chunk results are the leaves of the next level, same tree, until
+ *              one value is left; at least one such level runs.  Depth 9*(1 + max(1, ceil(log256(ceil(F_l/256))))), so with
+ *              k = 8 + that depth:  |sum - exact| <= k * 2^-53 * sum|term|,  k = 26 for F_l <= 65536, 35 for F_l <= 2^24 and
+ *              44 below 2^31: within 32 + ceil(log2 F_l) for every F_l >= 1.  This k counts the roundings of the longest
+ *              single path; it is a working bound, not a proof.  A product's relative error is the sum of its factors', so
+ *              to first order a term 8..13 carries d's 6 plus the bracket's 7 plus 1 = 14 roundings, not 8 (k = 32, 41, 50:
+ *              still inside the cap), and both counts are relative to the factors' own absolute sums, which
+ *              cancellation inside d can leave above |term|.  No floating-point atomics: two runs give the
+ *              same bits, and a link gives the same bits alone in a call or among others.
+ *              A link without triangles, or whose sum of d is 0, gets 14 zeros.
+ *   derived    from the (possibly zeroed) sums S, in this order:
+ *              volume = S4/6; area = S3/2; closure = sqrt((S0*S0 + S1*S1) + S2*S2)/S3 if S3 > 0 else 0; mass = density*volume;
+ *              m_i = (S(5+i)/24)/volume; com (n_links,3) = r_i + m_i; C_ij = S(8+ij)/120 - (volume*m_i)*m_j;
+ *              inertia (n_links,6) = ixx, ixy, ixz, iyy, iyz, izz of density*(tr(C) 1 - C) about com in the mesh's axes:
+ *              density*(C_yy + C_zz), -(density*C_xy), -(density*C_xz), density*(C_xx + C_zz), -(density*C_yz),
+ *              density*(C_xx + C_yy);
+ *              principal (n_links,3) ascending eigenvalues of the inertia tensor and axes (n_links,3,3), row k the unit
+ *              eigenvector of principal[k] (largest component positive for rows 0 and 1, row 2 = row 0 x row 1): eight
+ *              sweeps of cyclic Jacobi rotations.
+ *              For a link with zero sums volume, area, closure and mass are 0 and com, inertia, principal and axes are NaN.
+ *              A negative volume (an inward-oriented mesh) is reported as it is.
+ * CREG_EINVAL, nothing launched: n_links < 1 or > 65535, n_tri < 0 or >= 2^31, a null pointer, a workspace smaller than
+ * creg_mesh_inertia_workspace_bytes(n_tri, n_links) (14 doubles per 256-triangle chunk: floor(n_tri/256) + n_links + 1 slots). */
+size_t creg_mesh_inertia_workspace_bytes(int64_t n_tri, int32_t n_links);
+int creg_mesh_inertia_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, int32_t n_links, const double* density,
+                          double* sums, double* volume, double* area, double* closure, double* mass, double* com,
+                          double* inertia, double* principal, double* axes, void* workspace, size_t workspace_bytes,
+                          creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * A1  the whole `train` loop (mlp_reg.py:17-152) as one device-resident plan: per epoch
  * pose -> sin/cos features -> MLP -> pose -> calculate_pc -> L1 Chamfer -> backward -> Adam ->
  * ReduceLROnPlateau, best-loss tracking and early stop, with no host round trip per epoch
