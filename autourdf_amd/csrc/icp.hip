@@ -1871,7 +1871,7 @@ static int icp_large_run(const creg_icp_problem& q, int64_t n, int32_t k, int64_
     P.tcf = (float4*)(ws + L.tcf); P.tlmax = (unsigned*)(ws + L.tlmax);
     P.toff = q.tgt_offsets;                          // point-to-point mode (round 5): the cluster's own target segment, no mask
     const int nn_smem = ICP_NNW * ICP_G * (ICP_SB + 2) * 40;  // k_icp_nn: per wave 4 lane groups x ICP_SB (+2: bank offset) staged targets (x, y, z fp64, frame index, x, y, z float32)
-    { static int scr = -1; if (scr < 0) { const char* e = getenv("CREG_ICP_SCREEN"); scr = e ? atoi(e) != 0 : 1; } P.screen = scr; }
+    { static const int scr = [] { const char* e = getenv("CREG_ICP_SCREEN"); return e ? atoi(e) != 0 : 1; }(); P.screen = scr; }   // read once (thread-safe)
     CREG_HIP(hipFuncSetAttribute((const void*)k_icp_nn, hipFuncAttributeMaxDynamicSharedMemorySize, nn_smem));
     hipLaunchKernelGGL(k_icp_mask, dim3(k), dim3(1024), 0, s, P, (int)nf, (float)(0.5 * scale), q.world ? 0 : 1, 1);
     hipLaunchKernelGGL(k_icp_init, dim3(k), dim3(1024), 0, s, P, k);

@@ -1,6 +1,7 @@
 // kmeans.hip -- K2: Lloyd k-means in fp64 for 3-D points, sklearn.cluster.k_means(init=array,
-// n_init=1) semantics (reference mlp_reg.py:204, cluster_icp.py:67), plus the stable grouping /
-// change-of-frame step that follows it (mlp_reg.py:208-217).
+// n_init=1) semantics (reference mlp_reg.py:204, cluster_icp.py:67): the many-workgroup Lloyd loop, the stand-alone E-step and
+// the one-workgroup batched form for small frames (k_km_small).  The stable grouping / change-of-frame step that follows a
+// k-means (mlp_reg.py:208-217) is group.hip.
 //
 // Per Lloyd iteration ONE launch (bit-reproducible):
 //   k_assign[_mfma]  labels = first argmin_k fma(x2,b2,fma(x1,b1,fma(x0,b0,|c|^2))),  b = -2c; the per-cluster sums of
@@ -420,14 +421,6 @@ __device__ __forceinline__ void km_move(unsigned long long* sA, int lab, int pv,
     }
 }
 
-#ifndef CREG_STAMPS
-#define KM_PHASE(p_) do { } while (0)
-#define KM_BLK(p_) do { } while (0)
-#define KM_PP(p_) do { } while (0)
-#endif
-// Lloyd launches only: the M-step tail's operands (B = the rows `B` points at, writable), the relocation scratch (far: n
-// doubles, segv / segi: one entry per workgroup) and the label buffers.  A launch works on iteration t = f->n_iter: it
-// writes lab[t & 1] and compares with lab[(t - 1) & 1] (prev0 = "no label" at t = 0).
 #ifdef CREG_STAMPS
 // debug build only: 10 ns wall-clock ticks, per E-step launch relative to its first block's start: [0] launches [1] sum of mean-ish block start [2] sum of
 // last block end (arrival) [3] sum of tail end [4] blocks; scratch: g_km_w = {launch start (min), last arrival (max), tail end}
@@ -446,10 +439,19 @@ __global__ void k_km_fold() {
     for (int p = 0; p < 8; ++p) { if (g_km_w[2] != 0ull && g_km_ph[p] != 0ull) g_km_phs[p] += g_km_ph[p] - g_km_w[0]; g_km_ph[p] = 0ull; }
     g_km_w[0] = ~0ull; g_km_w[1] = 0ull; g_km_w[2] = 0ull; g_km_w[3] = 0ull;
 }
+#else
+#define KM_PHASE(p_) do { } while (0)
+#define KM_BLK(p_) do { } while (0)
+#define KM_PP(p_) do { } while (0)
 #endif
-struct KmTail { double* B; double* C2; double* Cw; double* far_d; double* segv; int* segi; int* lab[2]; const int* prev0; int max_iter; const int* inv;
-                double* ring; unsigned long long* genrep; unsigned long long* slots;
-                int nrow; const int* perm; int spin_limit; int rw; };                  // pruned form: rows of the sorted copy (dummies: perm < 0)
+// Lloyd launches only: the M-step tail's operands (B = the rows `B` points at, writable), the relocation scratch (far: n
+// doubles, segv / segi: one entry per workgroup) and the label buffers.  A launch works on iteration t = f->n_iter: it
+// writes lab[t & 1] and compares with lab[(t - 1) & 1] (prev0 = "no label" at t = 0).
+// KmTail{} is "no tail": a launch outside the Lloyd loop (final E-step, stand-alone assign).
+struct KmTail { double* B = nullptr; double* C2 = nullptr; double* Cw = nullptr; double* far_d = nullptr; double* segv = nullptr; int* segi = nullptr;
+                int* lab[2] = {nullptr, nullptr}; const int* prev0 = nullptr; int max_iter = 0; const int* inv = nullptr;
+                double* ring = nullptr; unsigned long long* genrep = nullptr; unsigned long long* slots = nullptr;
+                int nrow = 0; const int* perm = nullptr; int spin_limit = 0; int rw = 0; };   // pruned form: rows of the sorted copy (dummies: perm < 0)
 // persistent Lloyd kernel: centre rows of the iterations of ONE launch at distinct addresses (see k_km_persist), and copies of `gen`
 constexpr int KMP_RING = 320, KMP_GENREP = 8, KMP_GENREP_STRIDE = 512;       // (stride in 8-byte words: 4 KB apart)
 __host__ __device__ __forceinline__ size_t kmp_ring_stride(int k) { return ((size_t)4 * k + 15) & ~(size_t)15; }   // doubles, 128-byte multiple
@@ -1379,166 +1381,22 @@ __global__ __launch_bounds__(1024) void k_km_small(KmBatch A, int n, int k, int 
 
 static size_t kms_stride(int64_t n, int k) { return align_up(sizeof(double) * (14 * (size_t)k + n), 256); }
 
-// ---- grouping by label + inverse-pose change of frame ------------------------------------------
-// Every index is a compile-time constant (round 5): the row exchange of the partial pivoting is a conditional swap of the pivot row
-// with each later row in turn -- as a run-time row index it put the 4 x 8 matrix into scratch memory (272 bytes per lane, 93 scratch
-// instructions in k_group_scatter / k_group_scatter_big).  Same operations in the same order: bit-identical.
-__device__ __forceinline__ void inv4x4(const double* M, double* I) {      // Gauss-Jordan, partial pivoting
-    double a[4][8];
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { a[r][c] = M[4 * r + c]; a[r][4 + c] = (r == c) ? 1.0 : 0.0; }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        int p = c;                                        // first row of the largest |entry| in column c, rows c .. 3
-        double best = fabs(a[c][c]);
-#pragma unroll
-        for (int r = c + 1; r < 4; ++r) { const double v = fabs(a[r][c]); if (v > best) { best = v; p = r; } }
-#pragma unroll
-        for (int r = c + 1; r < 4; ++r) {
-            const bool sw = p == r;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { const double t = a[c][q], u = a[r][q]; a[c][q] = sw ? u : t; a[r][q] = sw ? t : u; }
-        }
-        const double inv = 1.0 / a[c][c];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) a[c][q] *= inv;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            if (r == c) continue;
-            const double fct = a[r][c];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) a[r][q] = fma(-fct, a[c][q], a[r][q]);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) I[4 * r + c] = a[r][4 + c];
+// ---- host driver -------------------------------------------------------------------------------------------------
+// Environment knobs, read once per process (the initialisation of a function-local static is thread-safe).  Measurement knobs
+// (tests/measure): CREG_KM_PRUNE=0 keeps the full sweep, CREG_KM_PERSIST=0 one launch per iteration, CREG_KM_PT = 1 | 2 | 4 /
+// CREG_KMP_PT = 2 | 4 | 8 force the points per thread of k_km_assign / the row slots per lane of the pruned kernels (0: by n).
+// Test knob: CREG_KM_SPIN_LIMIT, the polls before a waiting workgroup of the persistent kernel gives up (1 forces the fallback).
+struct KmKnobs { int prune, persist, spin_limit, pt, kmp_pt; };
+static const KmKnobs& km_knobs() {
+    static const KmKnobs K = [] {
+        auto num = [](const char* e, int unset) { return e ? atoi(e) : unset; };
+        const int spin = num(getenv("CREG_KM_SPIN_LIMIT"), 0), pt = num(getenv("CREG_KM_PT"), 0), kp = num(getenv("CREG_KMP_PT"), 0);
+        return KmKnobs{num(getenv("CREG_KM_PRUNE"), 1) != 0, num(getenv("CREG_KM_PERSIST"), 1) != 0, spin > 0 ? spin : (1 << 20),
+                       (pt == 1 || pt == 2 || pt == 4) ? pt : 0, (kp == 2 || kp == 4 || kp == 8) ? kp : 0};
+    }();
+    return K;
 }
 
-// grid.y = problem of a batch (the per-frame pointers come from the table)
-constexpr int GRP_MAXB = 16;
-struct GroupBatch { const double* X[GRP_MAXB]; const int* labels[GRP_MAXB]; const double* M[GRP_MAXB]; double* out[GRP_MAXB]; int* off[GRP_MAXB]; };
-
-__global__ __launch_bounds__(1024) void k_group_offsets(GroupBatch G, int n, int k) {
-    const int* __restrict__ labels = G.labels[blockIdx.y];
-    int* __restrict__ off = G.off[blockIdx.y];
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* cnt = (int*)smem;
-    for (int j = threadIdx.x; j <= k; j += 1024) cnt[j] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 1024) atomicAdd(&cnt[labels[i]], 1);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int j = 0; j < k; ++j) { const int c = cnt[j]; off[j] = run; run += c; }
-        off[k] = run;
-    }
-}
-
-// one wave per cluster walks the labels in order: ballot + prefix popcount gives the stable slot
-__global__ __launch_bounds__(64) void k_group_scatter(GroupBatch G, int n, int m_is_inverse) {
-    const double* __restrict__ X = G.X[blockIdx.y];
-    const int* __restrict__ labels = G.labels[blockIdx.y];
-    const int* __restrict__ off = G.off[blockIdx.y];
-    const double* __restrict__ M = G.M[blockIdx.y];
-    double* __restrict__ out = G.out[blockIdx.y];
-    const int j = blockIdx.x, lane = threadIdx.x;
-    __shared__ double I[16];                              // inv(M_j), by one lane (no device scratch)
-    if (m_is_inverse) { if (lane < 16) I[lane] = M[16 * j + lane]; }     // the caller inverted the pose (np.linalg.inv on the host)
-    else if (lane == 0) inv4x4(M + 16 * j, I);
-    __syncthreads();
-    int pos = off[j];
-    for (int base = 0; base < n; base += 64) {
-        const int i = base + lane;
-        const bool mine = (i < n) && (labels[i] == j);
-        const unsigned long long m = __ballot(mine);
-        if (mine) {
-            const int slot = pos + __popcll(m & ((1ull << lane) - 1ull));
-            const double p0 = X[3 * (size_t)i], p1 = X[3 * (size_t)i + 1], p2 = X[3 * (size_t)i + 2];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-                out[3 * (size_t)slot + a] = fma(I[4 * a + 2], p2, fma(I[4 * a + 1], p1, I[4 * a] * p0)) + I[4 * a + 3];
-        }
-        pos += __popcll(m);
-    }
-}
-
-// ---- the same grouping for large frames (n > 16384): counts over many workgroups, one 1024-thread workgroup per cluster
-// for the ordered compaction (the one-wave-per-cluster walk above took 1.85 ms at n = 262144, k = 128) ----
-__global__ __launch_bounds__(1024) void k_group_count(const int* __restrict__ labels, int n, int k, int* __restrict__ off) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    int* cnt = (int*)smem;
-    for (int j = threadIdx.x; j < k; j += 1024) cnt[j] = 0;
-    __syncthreads();
-    const int i0 = blockIdx.x * 4096 + threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const int i = i0 + 1024 * q; if (i < n) atomicAdd(&cnt[labels[i]], 1); }
-    __syncthreads();
-    for (int j = threadIdx.x; j < k; j += 1024) { const int c = cnt[j]; if (c) atomicAdd(&off[j + 1], c); }      // integers: order independent
-}
-
-// off[0] = 0, off[j + 1] = count of cluster j  ->  off[j + 1] = sum of the counts up to j  (k <= 4096: four per thread)
-__global__ __launch_bounds__(1024) void k_group_excl(int* __restrict__ off, int k) {
-    __shared__ int wsum[16];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int c[4], run = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const int j = 4 * tid + q; c[q] = j < k ? off[j + 1] : 0; run += c[q]; }
-    int inc = run;
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int base = inc - run;
-    for (int w = 0; w < wv; ++w) base += wsum[w];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const int j = 4 * tid + q; base += c[q]; if (j < k) off[j + 1] = base; }
-    if (tid == 0) off[0] = 0;
-}
-
-__global__ __launch_bounds__(1024) void k_group_scatter_big(const double* __restrict__ X, int n, const int* __restrict__ labels,
-                                                            const int* __restrict__ off, const double* __restrict__ M,
-                                                            double* __restrict__ out, int m_is_inverse) {
-    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    __shared__ double I[16];
-    __shared__ int wtot[2][16];
-    if (m_is_inverse) { if (tid < 16) I[tid] = M[16 * j + tid]; }
-    else if (tid == 0) inv4x4(M + 16 * j, I);
-    __syncthreads();
-    int pos = off[j];
-    for (int base = 0, r = 0; base < n; base += 4096, ++r) {
-        const int i0 = base + 4 * tid;                        // four consecutive points per thread: slots stay in index order
-        bool fl[4];
-        int c = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { fl[q] = (i0 + q < n) && labels[min(i0 + q, n - 1)] == j; c += fl[q]; }
-        int inc = c;
-        for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-        if (lane == 63) wtot[r & 1][wv] = inc;
-        __syncthreads();                                      // one barrier per round: the table alternates
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { const int v = wtot[r & 1][w]; before += w < wv ? v : 0; total += v; }
-        int slot = pos + before + inc - c;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-            if (fl[q]) {
-                const size_t i = (size_t)(i0 + q);
-                const double p0 = X[3 * i], p1 = X[3 * i + 1], p2 = X[3 * i + 2];
-#pragma unroll
-                for (int a = 0; a < 3; ++a)
-                    out[3 * (size_t)slot + a] = fma(I[4 * a + 2], p2, fma(I[4 * a + 1], p1, I[4 * a] * p0)) + I[4 * a + 3];
-                ++slot;
-            }
-        pos += total;
-    }
-}
-
-static int seg_count(int64_t n) { int s = (int)((n + 16383) / 16384); return s < 1 ? 1 : (s > 64 ? 64 : s); }
-
-// pruned E-step: points per workgroup and grid bits per axis of the spatial order
 // Geometry of the pruned E-step: G workgroups of 4 waves, each wave RW consecutive rows of the sorted copy (PT = ceil(RW / 64) row
 // slots per lane), rows = 4 G RW >= n + 64 (RW - 1) -- every one of the 64 Morton ranges starts on a WAVE boundary (the per-wave
 // filter is the level that must not straddle two ranges; 3 % dummy rows at n = 262144 instead of 12 % with workgroup-aligned runs).
@@ -1546,12 +1404,14 @@ static int seg_count(int64_t n) { int s = (int)((n + 16383) / 16384); return s <
 // lane while that gives at most 768 workgroups (three per CU), then four (512), then eight.  (Measured at n = 262144: 768 x 4 x 88
 // rows 16.0 us per Lloyd iteration, 576 x 4 x 128 -- 64 CUs with three workgroups -- 16.2: the late arrivals are the waves whose
 // box lies in the sparse end of the Morton order and keeps 40-55 centres, not the CUs with one workgroup more.)
-struct KmGeom { int G, RW, PT; };
+struct KmGeom {
+    int G, RW, PT;
+    int64_t rows() const { return (int64_t)4 * G * RW; }         // rows of the sorted copy: the points plus the dummies that align the 64 Morton ranges to the waves' runs
+};
 static KmGeom km_geometry(int64_t n) {
-    static int forced = -1;                                      // measurement knob CREG_KMP_PT (2 | 4 | 8)
-    if (forced < 0) { const char* e = getenv("CREG_KMP_PT"); forced = e ? atoi(e) : 0; }
+    const int forced = km_knobs().kmp_pt;
     for (int pt = 2; pt <= 8; pt *= 2) {
-        if ((forced == 2 || forced == 4 || forced == 8) && pt != forced) continue;
+        if (forced && pt != forced) continue;
         int64_t g = ((n - 64 + 64 * pt - 1) / (64 * pt) + 64 + 3) / 4;                          // 4 g - 64 waves of 64 pt rows cover n - 64
         if (g < 32) g = 32;
         if (g > 256) g = (g + 255) / 256 * 256;
@@ -1563,31 +1423,17 @@ static KmGeom km_geometry(int64_t n) {
     }
     return KmGeom{32, 1, 2};
 }
-static int km_pruned_pt(int64_t n) { return km_geometry(n).PT; }
-static int km_spin_limit() {                                     // polls before a waiting workgroup gives up (test knob CREG_KM_SPIN_LIMIT: 1 forces the fallback)
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("CREG_KM_SPIN_LIMIT"); v = e && atoi(e) > 0 ? atoi(e) : (1 << 20); }
-    return v;
-}
-static bool km_persist_enabled() {
-    static int v = -1;                                           // measurement knob: CREG_KM_PERSIST=0 keeps one launch per iteration
-    if (v < 0) { const char* e = getenv("CREG_KM_PERSIST"); v = e ? atoi(e) != 0 : 1; }
-    return v != 0;
-}
 static int km_cell_bits(int64_t n) { return n >= 131072 ? 6 : n >= 16384 ? 5 : n >= 2048 ? 4 : 3; }   // ~8 points per cell of a surface
-static bool km_pruned_enabled() {
-    static int v = -1;                                           // measurement knob (tests/measure): CREG_KM_PRUNE=0 keeps the full sweep
-    if (v < 0) { const char* e = getenv("CREG_KM_PRUNE"); v = e ? atoi(e) != 0 : 1; }
-    return v != 0;
+static int km_points_per_thread(int n) {                         // full-sweep VALU E-step
+    const int forced = km_knobs().pt;
+    return forced ? forced : n >= 32768 ? 2 : 1;                  // measured at n = 262144, k = 128: 13.5 / 11.7 / 15.0 us for 1 / 2 / 4
 }
 
 struct KmLayout { size_t xc, c2, b, cw, part, far, segv, segi, prev, lab2, flags, lab3, perm, inv, key, cell, box, ring, genrep, slots, total; };
-// rows of the sorted copy: the points plus the dummies that align the 64 Morton ranges to the waves' runs
-static int64_t km_rows(int64_t n) { const KmGeom g = km_geometry(n); return (int64_t)4 * g.G * g.RW; }
-static KmLayout km_layout(int64_t n, int k) {
+static KmLayout km_layout(int64_t n, int k, const KmGeom& geo) {
     KmLayout L; size_t o = 0;
     auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 256); return r; };
-    const int64_t nr = km_rows(n);                                // rows of the sorted copy: the points plus the dummies that align the ranges
+    const int64_t nr = geo.rows();
     L.xc = take(sizeof(double) * 3 * nr); L.c2 = take(sizeof(double) * 6 * k); L.b = take(sizeof(double) * 4 * k);
     L.cw = take(sizeof(double) * 4 * k); L.part = take(sizeof(unsigned long long) * 4 * k);      // part: the int64 accumulators
     L.far = take(sizeof(double) * n);
@@ -1606,48 +1452,72 @@ static KmLayout km_layout(int64_t n, int k) {
     L.total = o;
     return L;
 }
+// the caller's workspace as typed pointers
+struct KmWorkspace {
+    double *Xc, *C2, *B, *Cw; unsigned long long* acc; double *far_d, *segv; int *segi, *prev0, *lab2, *lab3, *perm, *inv, *key, *cell;
+    double *box, *ring; unsigned long long *genrep, *slots; KmFlags* flags;
+    KmWorkspace(void* base, const KmLayout& L) {
+        char* w = (char*)base;
+        Xc = (double*)(w + L.xc); C2 = (double*)(w + L.c2); B = (double*)(w + L.b); Cw = (double*)(w + L.cw);
+        acc = (unsigned long long*)(w + L.part); far_d = (double*)(w + L.far); segv = (double*)(w + L.segv); segi = (int*)(w + L.segi);
+        prev0 = (int*)(w + L.prev); lab2 = (int*)(w + L.lab2); lab3 = (int*)(w + L.lab3); perm = (int*)(w + L.perm); inv = (int*)(w + L.inv);
+        key = (int*)(w + L.key); cell = (int*)(w + L.cell); box = (double*)(w + L.box); ring = (double*)(w + L.ring);
+        genrep = (unsigned long long*)(w + L.genrep); slots = (unsigned long long*)(w + L.slots); flags = (KmFlags*)(w + L.flags);
+    }
+};
 
-static int km_points_per_thread(int n) {
-    static int forced = -1;                                      // measurement knob (tests/measure): CREG_KM_PT = 1 | 2 | 4
-    if (forced < 0) { const char* e = getenv("CREG_KM_PT"); forced = e ? atoi(e) : 0; }
-    if (forced == 1 || forced == 2 || forced == 4) return forced;
-    return n >= 32768 ? 2 : 1;                                  // measured at n = 262144, k = 128: 13.5 / 11.7 / 15.0 us for 1 / 2 / 4
+// A launch of 256-thread workgroups.  More than 48 KB of dynamic LDS needs the kernel's limit raised first: per device, not per
+// process, so on every call (a cached flag would leave a second GPU at the default).
+template <auto Kern, class... A>
+static int km_launch(int blocks, size_t smem, hipStream_t s, const A&... args) {
+    if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return 1;
+    hipLaunchKernelGGL(Kern, dim3(blocks), dim3(256), smem, s, args...);
+    return 0;
 }
 
-static int launch_assign(const double* X, int n, const double* B, int k, int* labels, const int* prev,
-                         KmFlags* f, int use_mfma, hipStream_t s, int raw = 0, unsigned long long* acc = nullptr,
-                         KmTail T = KmTail{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr}, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, 0}) {
-    constexpr int LDS_MAX = 128 * 1024;
+// Full-sweep E-step over X (n,3).  raw: B holds the centres (k,3), else their (-2c, |c|^2) rows; f / acc / T: a launch of the
+// Lloyd loop (labels from T.lab), else labels only.
+static int launch_assign(const double* X, int n, const double* B, int k, int* labels, KmFlags* f, int raw, unsigned long long* acc,
+                         const KmTail& T, int use_mfma, hipStream_t s) {
+    const int* const prev = nullptr;
     if (use_mfma) {
         const int ntile = cdiv(n, 16);
         int blocks = cdiv(ntile, 4);
         if (blocks > 2048) blocks = 2048;                        // a wave then walks several point tiles with its centres in registers
         const size_t smem = sizeof(double) * 5 * ((k + 15) & ~15) + sizeof(unsigned long long) * 4 * k;   // centre rows + the C-operand table + M-step sums
-#define CREG_KM_MFMA(NT_)                                                                                                        \
-        do {                                                                                                                      \
-            if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_km_assign_mfma<NT_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) != hipSuccess) return 1; \
-            hipLaunchKernelGGL(k_km_assign_mfma<NT_>, dim3(blocks), dim3(256), smem, s, X, n, B, k, labels, prev, f, raw, acc, T);  \
-        } while (0)
-        if (k <= 16) CREG_KM_MFMA(1);
-        else if (k <= 32) CREG_KM_MFMA(2);
-        else if (k <= 64) CREG_KM_MFMA(4);
-        else if (k <= 128) CREG_KM_MFMA(8);
-        else CREG_KM_MFMA(0);
-#undef CREG_KM_MFMA
-    } else {
-        const size_t smem = sizeof(double) * 8 * k;
-        const int pt = km_points_per_thread(n);
-#define CREG_KM_VALU(PT_)                                                                                                        \
-        do {                                                                                                                      \
-            if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_km_assign<PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX) != hipSuccess) return 1; \
-            hipLaunchKernelGGL(k_km_assign<PT_>, dim3(cdiv(n, 256 * PT_)), dim3(256), smem, s, X, n, B, k, labels, prev, f, raw, acc, T); \
-        } while (0)
-        if (pt == 4) CREG_KM_VALU(4);
-        else if (pt == 2) CREG_KM_VALU(2);
-        else CREG_KM_VALU(1);
-#undef CREG_KM_VALU
+        if (k <= 16) return km_launch<k_km_assign_mfma<1>>(blocks, smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+        if (k <= 32) return km_launch<k_km_assign_mfma<2>>(blocks, smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+        if (k <= 64) return km_launch<k_km_assign_mfma<4>>(blocks, smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+        if (k <= 128) return km_launch<k_km_assign_mfma<8>>(blocks, smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+        return km_launch<k_km_assign_mfma<0>>(blocks, smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
     }
-    return 0;
+    const size_t smem = sizeof(double) * 8 * k;
+    switch (km_points_per_thread(n)) {
+    case 4: return km_launch<k_km_assign<4>>(cdiv(n, 256 * 4), smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+    case 2: return km_launch<k_km_assign<2>>(cdiv(n, 256 * 2), smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+    default: return km_launch<k_km_assign<1>>(cdiv(n, 256), smem, s, X, n, B, k, labels, prev, f, raw, acc, T);
+    }
+}
+
+// One attempt of creg_kmeans_lloyd_f64: what every step of the driver works on.
+struct KmRun {
+    const double* X; int n, k, max_iter, use_mfma;
+    bool pruned;          // VALU form: E-step over the spatially sorted copy (T.nrow rows), centres pruned per workgroup; else full sweep in the caller's order
+    KmGeom geo; KmWorkspace W; KmTail T; hipStream_t s;
+};
+
+// pruned E-step and persistent kernel: centre rows, M-step sums, lower bounds, the workgroup's and the four waves' survivor lists
+static size_t km_pruned_smem(int k) { return sizeof(double) * 9 * k + sizeof(int) * 5 * k; }
+
+static int launch_assign_pruned(const KmRun& R, int* labels, int lloyd, unsigned long long* acc) {
+    const KmWorkspace& W = R.W;
+    const int blocks = R.T.nrow / (4 * R.T.rw);
+    const size_t smem = km_pruned_smem(R.k);
+    switch (R.geo.PT) {
+    case 8: return km_launch<k_km_assign_pruned<8>>(blocks, smem, R.s, W.Xc, R.n, W.B, R.k, W.box, labels, W.flags, lloyd, acc, R.T);
+    case 4: return km_launch<k_km_assign_pruned<4>>(blocks, smem, R.s, W.Xc, R.n, W.B, R.k, W.box, labels, W.flags, lloyd, acc, R.T);
+    default: return km_launch<k_km_assign_pruned<2>>(blocks, smem, R.s, W.Xc, R.n, W.B, R.k, W.box, labels, W.flags, lloyd, acc, R.T);
+    }
 }
 
 // the persistent kernel's grid must be resident all at once: 0 = not possible here (the caller keeps one launch per iteration)
@@ -1659,36 +1529,96 @@ static int persist_fits(int blocks, size_t smem) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_km_persist<PT>, 256, smem) != hipSuccess) return 0;
     return blocks <= (per_cu > 4 ? 4 : per_cu) * cus && blocks <= 1024;   // at most four per CU are counted on; one arrival slot each
 }
-static int launch_persist(const double* Xs, int n, double* B, int k, const double* box, KmFlags* f, unsigned long long* acc,
-                          const KmTail& T, int pt, hipStream_t s, bool probe_only) {
-    const size_t smem = sizeof(double) * 9 * k + sizeof(int) * 5 * k;   // centre rows, M-step sums, lower bounds, the workgroup's and the four waves' survivor lists
-    const int blocks = T.nrow / (4 * T.rw);
-#define CREG_KM_PERSIST(PT_)                                                                                                     \
-    do {                                                                                                                          \
-        if (!persist_fits<PT_>(blocks, smem)) return 1;                                                                           \
-        if (!probe_only) hipLaunchKernelGGL(k_km_persist<PT_>, dim3(blocks), dim3(256), smem, s, Xs, n, B, k, box, f, acc, T);     \
-    } while (0)
-    if (pt == 8) CREG_KM_PERSIST(8);
-    else if (pt == 4) CREG_KM_PERSIST(4);
-    else CREG_KM_PERSIST(2);
-#undef CREG_KM_PERSIST
+template <int PT>
+static int launch_persist(const KmRun& R, bool probe_only) {
+    const KmWorkspace& W = R.W;
+    const int blocks = R.T.nrow / (4 * R.T.rw);
+    const size_t smem = km_pruned_smem(R.k);
+    if (!persist_fits<PT>(blocks, smem)) return 1;
+    if (!probe_only) hipLaunchKernelGGL(k_km_persist<PT>, dim3(blocks), dim3(256), smem, R.s, W.Xc, R.n, W.B, R.k, W.box, W.flags, W.acc, R.T);
     return 0;
 }
 
-static int launch_assign_pruned(const double* Xs, int n, const double* B, int k, const double* box, int* labels, KmFlags* f,
-                                int lloyd, unsigned long long* acc, const KmTail& T, hipStream_t s) {
-    const size_t smem = sizeof(double) * 9 * k + sizeof(int) * 5 * k;   // centre rows, M-step sums, lower bounds, the workgroup's and the four waves' survivor lists
-#define CREG_KM_PRUNED(PT_)                                                                                                      \
-    do {                                                                                                                          \
-        if (smem > 48 * 1024 && hipFuncSetAttribute((const void*)k_km_assign_pruned<PT_>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return 1; \
-        hipLaunchKernelGGL(k_km_assign_pruned<PT_>, dim3(T.nrow / (4 * T.rw)), dim3(256), smem, s, Xs, n, B, k, box, labels, f, lloyd, acc, T); \
-    } while (0)
-    const int pt = km_pruned_pt(n);
-    if (pt == 8) CREG_KM_PRUNED(8);
-    else if (pt == 4) CREG_KM_PRUNED(4);
-    else CREG_KM_PRUNED(2);
-#undef CREG_KM_PRUNED
-    return 0;
+// One launch of the Lloyd loop: the E-step of iteration f->n_iter with the exact incremental sums, its last workgroup the M-step
+// tail; a launch after convergence (or after max_iter iterations) returns at once, and a launch that follows the discovery of an
+// empty cluster runs the deferred tail instead (see km_lloyd_entry).
+static int km_lloyd_step(const KmRun& R) {
+    return R.pruned ? launch_assign_pruned(R, nullptr, 1, R.W.acc)
+                    : launch_assign(R.W.Xc, R.n, R.W.B, R.k, nullptr, R.W.flags, 0, R.W.acc, R.T, R.use_mfma, R.s);
+}
+static int km_read_flags(const KmRun& R, KmFlags* host) {
+    CREG_LAUNCH_CHECK();
+    CREG_HIP(hipMemcpyAsync(host, R.W.flags, sizeof(KmFlags), hipMemcpyDeviceToHost, R.s));
+    CREG_HIP(hipStreamSynchronize(R.s));
+    return CREG_OK;
+}
+
+// stats, the spatial order of the pruned form, the centred copy and the first centre rows
+static int km_prepare(const KmRun& R, const double* init, double tol_rel) {
+    const KmWorkspace& W = R.W;
+    const int n = R.n, k = R.k, nrow = R.T.nrow;
+    hipStream_t s = R.s;
+    CREG_HIP(hipMemsetAsync(W.acc, 0, sizeof(unsigned long long) * 4 * k, s));
+    hipLaunchKernelGGL(k_km_stats, dim3(1), dim3(1024), 0, s, R.X, n, tol_rel, W.flags);
+    if (R.pruned) {
+        const int bits = km_cell_bits(n), ncell = 1 << (3 * bits);
+        int* gtot = W.cell + ncell;
+        CREG_HIP(hipMemsetAsync(W.cell, 0, sizeof(int) * ncell, s));
+        hipLaunchKernelGGL(k_km_cell_count, dim3(cdiv(n, 256)), dim3(256), 0, s, R.X, n, W.flags, bits, W.key, W.cell);
+        hipLaunchKernelGGL(k_km_cell_totals, dim3(64), dim3(256), 0, s, W.cell, ncell, gtot);
+        hipLaunchKernelGGL(k_km_cell_scan, dim3(64), dim3(256), 0, s, W.cell, ncell, R.geo.RW, gtot);
+        CREG_HIP(hipMemsetAsync(W.Xc, 0xFF, sizeof(double) * 3 * (size_t)nrow, s));     // dummy rows: NaN coordinates (ignored by the boxes' fmin / fmax) ...
+        CREG_HIP(hipMemsetAsync(W.perm, 0xFF, sizeof(int) * (size_t)nrow, s));          // ... and perm = -1
+        hipLaunchKernelGGL(k_km_cell_scatter, dim3(cdiv(n, 256)), dim3(256), 0, s, n, W.key, W.cell, W.perm, W.inv);
+    }
+    hipLaunchKernelGGL(k_km_center, dim3(cdiv(n > k ? n : k, 256)), dim3(256), 0, s, R.X, n, init, k, W.flags, W.Xc, W.C2, W.B, W.prev0, R.T.inv);
+    if (R.pruned) hipLaunchKernelGGL(k_km_boxes, dim3(R.geo.G), dim3(256), 0, s, W.Xc, nrow, 4 * R.geo.RW, W.box);
+    CREG_LAUNCH_CHECK();
+    if (R.pruned) CREG_HIP(hipMemsetAsync(W.genrep, 0, (size_t)((char*)(W.slots + 1024) - (char*)W.genrep), s));
+    return CREG_OK;
+}
+
+// Lloyd iterations until convergence or max_iter; *host = the flags after the last one.  *abandoned: the persistent kernel gave
+// up, nothing of this attempt is to be used.
+static int km_iterate(const KmRun& R, bool allow_persist, KmFlags* host, bool* abandoned) {
+    // Pruned form: ONE ordinary launch (an E-step, or the relocation a persistent launch left pending), then the persistent
+    // kernel, which iterates until convergence / max_iter / the next empty cluster; one host round trip per such pair.
+    int (*const launch_persist_pt)(const KmRun&, bool) = R.geo.PT == 8 ? launch_persist<8> : R.geo.PT == 4 ? launch_persist<4> : launch_persist<2>;
+    const bool persist = allow_persist && R.pruned && km_knobs().persist && launch_persist_pt(R, true) == 0;
+    for (int round = 0; persist && host->n_iter < R.max_iter && !host->done; ++round) {
+        // every pair completes at least the ordinary launch's step (an iteration, or a pending relocation)
+        CREG_REQUIRE(round <= 2 * R.max_iter + 2, "creg_kmeans_lloyd_f64: the Lloyd state machine makes no progress");
+        CREG_REQUIRE(km_lloyd_step(R) == 0, "creg_kmeans_lloyd_f64: cannot raise the dynamic LDS limit of the E-step");
+        CREG_REQUIRE(launch_persist_pt(R, false) == 0, "creg_kmeans_lloyd_f64: the persistent Lloyd kernel does not fit");
+        if (const int rc = km_read_flags(R, host)) return rc;
+        // a workgroup waited ~1 s for the others (the device was kept busy by other streams' kernels, so the grid was not
+        // resident together): the call starts over with one launch per iteration
+        if (host->abort) { *abandoned = true; return CREG_OK; }
+    }
+    while (host->n_iter < R.max_iter && !host->done) {
+        for (int b = 0; b < 32; ++b) {                           // 32 launches per host round trip
+            CREG_REQUIRE(km_lloyd_step(R) == 0, "creg_kmeans_lloyd_f64: cannot raise the dynamic LDS limit of the E-step");
+#ifdef CREG_STAMPS
+            hipLaunchKernelGGL(k_km_fold, dim3(1), dim3(1), 0, R.s);
+#endif
+        }
+        if (const int rc = km_read_flags(R, host)) return rc;
+    }
+    return CREG_OK;
+}
+
+// labels of the final centres in the caller's order, centres, inertia, iteration count
+static int km_finish(const KmRun& R, const KmFlags& host, double* centers, int* labels, double* inertia, int* n_iter) {
+    const KmWorkspace& W = R.W;
+    int* last = R.T.lab[(host.n_iter - 1) & 1];                  // the buffer that holds the labels of the last executed iteration
+    if (!host.strict)        // rerun the E-step alone so labels match the final centres (_kmeans.py:736-748)
+        CREG_REQUIRE((R.pruned ? launch_assign_pruned(R, last, 0, nullptr)
+                               : launch_assign(W.Xc, R.n, W.B, R.k, last, nullptr, 0, nullptr, KmTail{}, R.use_mfma, R.s)) == 0, "creg_kmeans_lloyd_f64: E-step launch failed");
+    if (R.pruned) hipLaunchKernelGGL(k_km_unsort, dim3(cdiv(R.T.nrow, 256)), dim3(256), 0, R.s, last, W.perm, R.T.nrow, labels);
+    else if (last != labels) CREG_HIP(hipMemcpyAsync(labels, last, sizeof(int) * (size_t)R.n, hipMemcpyDeviceToDevice, R.s));
+    hipLaunchKernelGGL(k_km_finish, dim3(1), dim3(1024), 0, R.s, R.pruned ? R.X : W.Xc, R.n, labels, R.k, W.C2, W.flags, centers, inertia, n_iter, R.pruned ? 1 : 0);
+    CREG_LAUNCH_CHECK();
+    return CREG_OK;
 }
 
 }  // namespace creg
@@ -1696,106 +1626,10 @@ using namespace creg;
 
 extern "C" size_t creg_kmeans_workspace_bytes(int64_t n, int32_t k) {
     if (n < 1 || k < 1) return 0;
-    return km_layout(n, k).total;
+    return km_layout(n, k, km_geometry(n)).total;
 }
 
-constexpr int KM_RETRY_WITHOUT_PERSIST = 1000;
 constexpr int KM_PERSIST_BACKOFF = 64;       // calls that skip the persistent kernel after an abandoned attempt
-static int km_lloyd_run(const double* X, int64_t n, const double* init, int32_t k,
-                        int32_t max_iter, double tol_rel, int32_t use_mfma, double* centers,
-                        int32_t* labels, double* inertia, int32_t* n_iter, void* workspace,
-                        size_t workspace_bytes, creg_stream_t stream, bool allow_persist) {
-    CREG_REQUIRE(X && init && centers && labels && inertia && n_iter && workspace, "creg_kmeans_lloyd_f64: null pointer");
-    CREG_REQUIRE(n >= 1 && n < (1ll << 31) && k >= 1 && k <= 1024 && max_iter >= 1,
-                 "creg_kmeans_lloyd_f64: need 1 <= n < 2^31, 1 <= k <= 1024, max_iter >= 1");
-    const KmLayout L = km_layout(n, k);
-    CREG_REQUIRE(workspace_bytes >= L.total, "creg_kmeans_lloyd_f64: workspace too small (%zu < %zu)", workspace_bytes, L.total);
-    hipStream_t s = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    double* Xc = (double*)(w + L.xc); double* C2 = (double*)(w + L.c2); double* B = (double*)(w + L.b);
-    double* Cw = (double*)(w + L.cw); unsigned long long* acc = (unsigned long long*)(w + L.part); double* far_d = (double*)(w + L.far);
-    // VALU form: the E-step runs over a spatially sorted copy of the frame and prunes the centres per workgroup (labels in
-    // the sorted order in two workspace buffers, put back in the caller's order at the end); matrix-core form: full sweep
-    const bool pruned = !use_mfma && km_pruned_enabled() && n < (1ll << 30);
-    int* lab[2] = {pruned ? (int*)(w + L.lab3) : labels, (int*)(w + L.lab2)};
-    int* prev0 = (int*)(w + L.prev);
-    int* perm = (int*)(w + L.perm); int* inv = (int*)(w + L.inv); double* box = (double*)(w + L.box);
-    KmFlags* f = (KmFlags*)(w + L.flags);
-    const KmGeom geo = km_geometry(n);
-    CREG_REQUIRE(!pruned || (km_rows(n) >= n + 64 * (int64_t)(geo.RW - 1) && geo.RW <= 64 * geo.PT && km_rows(n) < (1ll << 31)),
-                 "creg_kmeans_lloyd_f64: internal: geometry of the sorted copy (%d workgroups x 4 x %d rows)", geo.G, geo.RW);
-    const int ni = (int)n, nrow = pruned ? (int)km_rows(n) : (int)n;
-    CREG_HIP(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4 * k, s));
-
-    hipLaunchKernelGGL(k_km_stats, dim3(1), dim3(1024), 0, s, X, ni, tol_rel, f);
-    if (pruned) {
-        const int bits = km_cell_bits(n), ncell = 1 << (3 * bits);
-        int* key = (int*)(w + L.key); int* cell = (int*)(w + L.cell); int* gtot = cell + ncell;
-        CREG_HIP(hipMemsetAsync(cell, 0, sizeof(int) * ncell, s));
-        hipLaunchKernelGGL(k_km_cell_count, dim3(cdiv(n, 256)), dim3(256), 0, s, X, ni, f, bits, key, cell);
-        hipLaunchKernelGGL(k_km_cell_totals, dim3(64), dim3(256), 0, s, cell, ncell, gtot);
-        hipLaunchKernelGGL(k_km_cell_scan, dim3(64), dim3(256), 0, s, cell, ncell, geo.RW, gtot);
-        CREG_HIP(hipMemsetAsync(Xc, 0xFF, sizeof(double) * 3 * (size_t)nrow, s));       // dummy rows: NaN coordinates (ignored by the boxes' fmin / fmax) ...
-        CREG_HIP(hipMemsetAsync(perm, 0xFF, sizeof(int) * (size_t)nrow, s));            // ... and perm = -1
-        hipLaunchKernelGGL(k_km_cell_scatter, dim3(cdiv(n, 256)), dim3(256), 0, s, ni, key, cell, perm, inv);
-    }
-    hipLaunchKernelGGL(k_km_center, dim3(cdiv(n > k ? n : k, 256)), dim3(256), 0, s, X, ni, init, k, f, Xc, C2, B, prev0, pruned ? inv : nullptr);
-    if (pruned) hipLaunchKernelGGL(k_km_boxes, dim3(geo.G), dim3(256), 0, s, Xc, nrow, 4 * geo.RW, box);
-    CREG_LAUNCH_CHECK();
-    // labels ping-pong between the caller's buffer and lab2 so "previous labels" needs no copy;
-    // iteration `it` writes lab[it & 1] and compares with the buffer written by it - 1.
-    int done = 0, n_done = 0;
-    KmFlags host;
-    const KmTail T{B, C2, Cw, far_d, (double*)(w + L.segv), (int*)(w + L.segi), {lab[0], lab[1]}, prev0, max_iter, pruned ? inv : nullptr,
-                   (double*)(w + L.ring), (unsigned long long*)(w + L.genrep), (unsigned long long*)(w + L.slots), nrow, perm, km_spin_limit(), geo.RW};
-    if (pruned) CREG_HIP(hipMemsetAsync(w + L.genrep, 0, L.slots + sizeof(unsigned long long) * 1024 - L.genrep, s));
-    // Pruned form: ONE ordinary launch (an E-step, or the relocation a persistent launch left pending), then the persistent
-    // kernel, which iterates until convergence / max_iter / the next empty cluster; one host round trip per such pair.
-    const bool persist = allow_persist && pruned && km_persist_enabled() && launch_persist(Xc, ni, B, k, box, f, acc, T, km_pruned_pt(n), s, true) == 0;
-    for (int round = 0; persist && n_done < max_iter && !done; ++round) {
-        // every pair completes at least the ordinary launch's step (an iteration, or a pending relocation)
-        CREG_REQUIRE(round <= 2 * max_iter + 2, "creg_kmeans_lloyd_f64: the Lloyd state machine makes no progress");
-        CREG_REQUIRE(launch_assign_pruned(Xc, ni, B, k, box, nullptr, f, 1, acc, T, s) == 0, "creg_kmeans_lloyd_f64: cannot raise the dynamic LDS limit of the E-step");
-        CREG_REQUIRE(launch_persist(Xc, ni, B, k, box, f, acc, T, km_pruned_pt(n), s, false) == 0, "creg_kmeans_lloyd_f64: the persistent Lloyd kernel does not fit");
-        CREG_LAUNCH_CHECK();
-        CREG_HIP(hipMemcpyAsync(&host, f, sizeof(KmFlags), hipMemcpyDeviceToHost, s));
-        CREG_HIP(hipStreamSynchronize(s));
-        // a workgroup waited ~1 s for the others (the device was kept busy by other streams' kernels, so the grid was not
-        // resident together): nothing of this attempt is used, the call starts over with one launch per iteration
-        if (host.abort) return KM_RETRY_WITHOUT_PERSIST;
-        done = host.done; n_done = host.n_iter;
-    }
-    while (n_done < max_iter && !done) {
-        // 32 launches per host round trip.  A launch runs the E-step of iteration f->n_iter with the exact incremental sums, and
-        // its last workgroup the M-step tail; launches after convergence (or after max_iter iterations) return at once, and a
-        // launch that follows the discovery of an empty cluster runs the deferred tail instead (see km_lloyd_entry).
-        for (int b = 0; b < 32; ++b)
-        {
-            CREG_REQUIRE((pruned ? launch_assign_pruned(Xc, ni, B, k, box, nullptr, f, 1, acc, T, s)
-                                 : launch_assign(Xc, ni, B, k, nullptr, nullptr, f, use_mfma, s, 0, acc, T)) == 0,
-                         "creg_kmeans_lloyd_f64: cannot raise the dynamic LDS limit of the E-step");
-#ifdef CREG_STAMPS
-            hipLaunchKernelGGL(k_km_fold, dim3(1), dim3(1), 0, s);
-#endif
-        }
-        CREG_LAUNCH_CHECK();
-        CREG_HIP(hipMemcpyAsync(&host, f, sizeof(KmFlags), hipMemcpyDeviceToHost, s));
-        CREG_HIP(hipStreamSynchronize(s));
-        done = host.done; n_done = host.n_iter;
-    }
-    // which buffer holds the labels of the last executed iteration
-    int* last = lab[(host.n_iter - 1) & 1];
-    if (!host.strict) {      // rerun the E-step so labels match the final centres (_kmeans.py:736-748)
-        CREG_REQUIRE((pruned ? launch_assign_pruned(Xc, ni, B, k, box, last, f, 0, nullptr, T, s)
-                             : launch_assign(Xc, ni, B, k, last, nullptr, nullptr, use_mfma, s)) == 0, "creg_kmeans_lloyd_f64: E-step launch failed");
-    }
-    if (pruned) hipLaunchKernelGGL(k_km_unsort, dim3(cdiv(nrow, 256)), dim3(256), 0, s, last, perm, nrow, labels);
-    else if (last != labels) CREG_HIP(hipMemcpyAsync(labels, last, sizeof(int) * n, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(k_km_finish, dim3(1), dim3(1024), 0, s, pruned ? X : Xc, ni, labels, k, C2, f, centers, inertia, n_iter, pruned ? 1 : 0);
-    CREG_LAUNCH_CHECK();
-    return CREG_OK;
-}
-
 extern "C" int creg_kmeans_lloyd_f64(const double* X, int64_t n, const double* init, int32_t k,
                                      int32_t max_iter, double tol_rel, int32_t use_mfma, double* centers,
                                      int32_t* labels, double* inertia, int32_t* n_iter, void* workspace,
@@ -1806,59 +1640,43 @@ extern "C" int creg_kmeans_lloyd_f64(const double* X, int64_t n, const double* i
     static std::atomic<int> backoff{0};
     const bool try_persist = backoff.load(std::memory_order_relaxed) <= 0;
     if (!try_persist) backoff.fetch_sub(1, std::memory_order_relaxed);
-    int rc = km_lloyd_run(X, n, init, k, max_iter, tol_rel, use_mfma, centers, labels, inertia, n_iter, workspace, workspace_bytes, stream, try_persist);
-    if (rc == KM_RETRY_WITHOUT_PERSIST) {
+    CREG_REQUIRE(X && init && centers && labels && inertia && n_iter && workspace, "creg_kmeans_lloyd_f64: null pointer");
+    CREG_REQUIRE(n >= 1 && n < (1ll << 31) && k >= 1 && k <= 1024 && max_iter >= 1,
+                 "creg_kmeans_lloyd_f64: need 1 <= n < 2^31, 1 <= k <= 1024, max_iter >= 1");
+    const KmGeom geo = km_geometry(n);
+    const KmLayout L = km_layout(n, k, geo);
+    CREG_REQUIRE(workspace_bytes >= L.total, "creg_kmeans_lloyd_f64: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    const bool pruned = !use_mfma && km_knobs().prune && n < (1ll << 30);
+    CREG_REQUIRE(!pruned || (geo.rows() >= n + 64 * (int64_t)(geo.RW - 1) && geo.RW <= 64 * geo.PT && geo.rows() < (1ll << 31)),
+                 "creg_kmeans_lloyd_f64: internal: geometry of the sorted copy (%d workgroups x 4 x %d rows)", geo.G, geo.RW);
+    KmRun R{X, (int)n, k, max_iter, use_mfma, pruned, geo, KmWorkspace(workspace, L), KmTail{}, (hipStream_t)stream};
+    const KmWorkspace& W = R.W;
+    KmTail& T = R.T;
+    T.B = W.B; T.C2 = W.C2; T.Cw = W.Cw; T.far_d = W.far_d; T.segv = W.segv; T.segi = W.segi;
+    // the labels ping-pong between two buffers so "previous labels" needs no copy: iteration `it` writes lab[it & 1] and compares
+    // with the buffer written by it - 1.  Pruned: both in the workspace, in the sorted order (put back in the caller's order at
+    // the end); full sweep: the caller's buffer is one of them.
+    T.lab[0] = pruned ? W.lab3 : labels; T.lab[1] = W.lab2; T.prev0 = W.prev0; T.max_iter = max_iter;
+    T.inv = pruned ? W.inv : nullptr; T.ring = W.ring; T.genrep = W.genrep; T.slots = W.slots;
+    T.nrow = pruned ? (int)geo.rows() : (int)n; T.perm = W.perm; T.spin_limit = km_knobs().spin_limit; T.rw = geo.RW;
+
+    KmFlags host;
+    for (bool allow_persist = try_persist;; allow_persist = false) {     // (an attempt without the persistent kernel is never abandoned)
+        host = KmFlags{};
+        bool abandoned = false;
+        if (const int rc = km_prepare(R, init, tol_rel)) return rc;
+        if (const int rc = km_iterate(R, allow_persist, &host, &abandoned)) return rc;
+        if (!abandoned) break;
         backoff.store(KM_PERSIST_BACKOFF, std::memory_order_relaxed);
-        rc = km_lloyd_run(X, n, init, k, max_iter, tol_rel, use_mfma, centers, labels, inertia, n_iter, workspace, workspace_bytes, stream, false);
     }
-    return rc;
+    return km_finish(R, host, centers, labels, inertia, n_iter);
 }
 
 extern "C" int creg_kmeans_assign_f64(const double* X, int64_t n, const double* C, int32_t k, int32_t use_mfma,
                                       int32_t* labels, creg_stream_t stream) {
     CREG_REQUIRE(X && C && labels && n >= 1 && n < (1ll << 31) && k >= 1 && k <= 1024, "creg_kmeans_assign_f64: bad argument");
-    // no device scratch: the kernels derive the (-2c, |c|^2) rows from the centres in their prologue
-    CREG_REQUIRE(launch_assign(X, (int)n, C, k, labels, nullptr, nullptr, use_mfma, (hipStream_t)stream, 1) == 0, "creg_kmeans_assign_f64: E-step launch failed");
-    CREG_LAUNCH_CHECK();
-    return CREG_OK;
-}
-
-extern "C" int creg_group_to_local_f64(const double* X, int64_t n, const int32_t* labels, int32_t k,
-                                       const double* M, int32_t m_is_inverse, double* out_local,
-                                       int32_t* seg_offsets, creg_stream_t stream) {
-    CREG_REQUIRE(X && labels && M && out_local && seg_offsets && n >= 1 && n < (1ll << 31) && k >= 1 && k <= 4096,
-                 "creg_group_to_local_f64: bad argument");
-    hipStream_t s = (hipStream_t)stream;
-    GroupBatch G;
-    G.X[0] = X; G.labels[0] = labels; G.M[0] = M; G.out[0] = out_local; G.off[0] = seg_offsets;
-    if (n > 16384) {                                           // large frames: many-workgroup count, workgroup-per-cluster compaction
-        CREG_HIP(hipMemsetAsync(seg_offsets, 0, sizeof(int) * ((size_t)k + 1), s));
-        hipLaunchKernelGGL(k_group_count, dim3(cdiv(n, 4096)), dim3(1024), sizeof(int) * k, s, labels, (int)n, k, seg_offsets);
-        hipLaunchKernelGGL(k_group_excl, dim3(1), dim3(1024), 0, s, seg_offsets, k);
-        hipLaunchKernelGGL(k_group_scatter_big, dim3(k), dim3(1024), 0, s, X, (int)n, labels, seg_offsets, M, out_local, m_is_inverse);
-        CREG_LAUNCH_CHECK();
-        return CREG_OK;
-    }
-    hipLaunchKernelGGL(k_group_offsets, dim3(1, 1), dim3(1024), sizeof(int) * (k + 1), s, G, (int)n, k);
-    hipLaunchKernelGGL(k_group_scatter, dim3(k, 1), dim3(64), 0, s, G, (int)n, m_is_inverse);
-    CREG_LAUNCH_CHECK();
-    return CREG_OK;
-}
-
-extern "C" int creg_group_to_local_batch_f64(const double* const* X, int64_t n, const int32_t* const* labels, int32_t k,
-                                             const double* const* M, int32_t m_is_inverse, int32_t batch,
-                                             double* const* out_local, int32_t* const* seg_offsets, creg_stream_t stream) {
-    CREG_REQUIRE(X && labels && M && out_local && seg_offsets && n >= 1 && n < (1ll << 31) && k >= 1 && k <= 4096,
-                 "creg_group_to_local_batch_f64: bad argument");
-    CREG_REQUIRE(batch >= 1 && batch <= GRP_MAXB, "creg_group_to_local_batch_f64: batch must be in 1..%d", GRP_MAXB);
-    GroupBatch G;
-    for (int b = 0; b < batch; ++b) {
-        CREG_REQUIRE(X[b] && labels[b] && M[b] && out_local[b] && seg_offsets[b], "creg_group_to_local_batch_f64: null pointer in problem %d", b);
-        G.X[b] = X[b]; G.labels[b] = labels[b]; G.M[b] = M[b]; G.out[b] = out_local[b]; G.off[b] = seg_offsets[b];
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_group_offsets, dim3(1, batch), dim3(1024), sizeof(int) * (k + 1), s, G, (int)n, k);
-    hipLaunchKernelGGL(k_group_scatter, dim3(k, batch), dim3(64), 0, s, G, (int)n, m_is_inverse);
+    // no device scratch: the kernels derive the (-2c, |c|^2) rows from the centres in their prologue (raw = 1)
+    CREG_REQUIRE(launch_assign(X, (int)n, C, k, labels, nullptr, 1, nullptr, KmTail{}, use_mfma, (hipStream_t)stream) == 0, "creg_kmeans_assign_f64: E-step launch failed");
     CREG_LAUNCH_CHECK();
     return CREG_OK;
 }

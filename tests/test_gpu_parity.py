@@ -245,6 +245,47 @@ def test_kmeans_persistent_kernel_gives_up_and_the_call_starts_over(dev, tmp_pat
     assert int(o["n_iter"][0]) == n_iter.item()
 
 
+@pytest.fixture(scope="module")
+def km_knob_cases(dev, tmp_path_factory):
+    """The two inputs of test_kmeans_knob_paths_identical_to_default in one file, with the default run of each in this process."""
+    from autourdf_amd import ops
+    rng = np.random.default_rng(29)
+    Xa = rng.normal(size=(300, 3))
+    ia = Xa[rng.choice(300, 40, replace=False)].copy()
+    ia[:10] += 40.0                                  # ten seeds own nothing: the deferred-relocation launches
+    u, v = rng.uniform(-1, 1, 33000), rng.uniform(-1, 1, 33000)
+    Xb = np.stack([u, v, 0.3 * np.sin(3 * u) * np.cos(2 * v) + 0.01 * rng.normal(size=33000)], 1)
+    ib = Xb[rng.choice(33000, 20, replace=False)].copy()
+    path = tmp_path_factory.mktemp("km_knobs") / "in.npz"
+    np.savez(path, Xa=Xa, ia=ia, Xb=Xb, ib=ib)
+    ref = {t: [o.cpu().numpy() for o in ops.kmeans_lloyd(_cuda(X, dev), _cuda(i, dev), max_iter=40)] for t, X, i in (("a", Xa, ia), ("b", Xb, ib))}
+    return path, ref
+
+
+@pytest.mark.parametrize("knob", ["CREG_KM_PRUNE", "CREG_KM_PERSIST"])
+def test_kmeans_knob_paths_identical_to_default(km_knob_cases, tmp_path, knob):
+    """The two host paths of creg_kmeans_lloyd_f64 that only a knob reaches -- the full-sweep VALU E-step inside the Lloyd loop
+    (CREG_KM_PRUNE=0) and the pruned E-step with one launch per iteration (CREG_KM_PERSIST=0) -- in a child process each (the knobs
+    are read once per process): labels, centres, inertia and iteration count EQUAL to the default run of this process.  n = 300,
+    k = 40 with ten seeds that own nothing runs the deferred-relocation launches (a skipped one shows in n_iter and in an empty
+    cluster); n = 33000 lies just above the two-points-per-thread switch of k_km_assign (32768) and the cell-bits switch (16384);
+    a wrong label-buffer parity shows in the labels."""
+    import subprocess
+    import sys
+    path, ref = km_knob_cases
+    code = ("import numpy as np, torch, sys; sys.path.insert(0, %r); from autourdf_amd import ops; g = np.load(%r); out = {}\n"
+            "for t in 'ab':\n"
+            "    o = ops.kmeans_lloyd(torch.as_tensor(g['X' + t], device='cuda'), torch.as_tensor(g['i' + t], device='cuda'), max_iter=40)\n"
+            "    out.update({t + str(j): o[j].cpu().numpy() for j in range(4)})\n"
+            "np.savez(%r, **out)" % (ROOT, str(path), str(tmp_path / "out.npz")))
+    subprocess.run([sys.executable, "-c", code], check=True, env=dict(os.environ, **{knob: "0"}), timeout=120)
+    o = np.load(tmp_path / "out.npz")
+    for t in "ab":
+        for j, what in enumerate(("centres", "labels", "inertia", "n_iter")):
+            np.testing.assert_array_equal(o[t + str(j)], ref[t][j], err_msg=f"{knob}=0, input {t}: {what}")
+    assert len(np.unique(ref["a"][1])) == 40 and 1 < int(ref["a"][3][0]) and 1 < int(ref["b"][3][0]) <= 40
+
+
 def test_resample_group_to_local_vs_reference_golden(dev, golden):
     from autourdf_amd import ops
     g = golden("resample_reference.npz")

@@ -25,6 +25,31 @@ def test_build_produces_library_and_every_declared_symbol_resolves():
     assert lib.creg_version() >= 100
 
 
+def test_kmeans_workspace_sizes_are_pinned_across_the_geometry_switches():
+    """creg_kmeans_workspace_bytes / creg_kmeans_batch_workspace_bytes are pure host arithmetic (the pruned E-step's geometry and
+    the workspace layout): n on both sides of every switch of the geometry (cell bits at 2048 / 16384 / 131072, row slots per lane
+    and workgroup counts above 16384, 49152, 98304), k at both ends and at the 128 of the batched form.  The numbers are those of
+    the library before the host driver was restructured; callers' allocations depend on them."""
+    from autourdf_amd import _lib
+    lib = _lib.load(check_device=False)
+    ks = (1, 128, 1024)
+    expected = {   # n: (workspace bytes per k, batch workspace bytes per k at batch = 3)
+        17: ((153344, 1440512, 10744576), (768, 43776, 344832)),
+        2048: ((346368, 1633536, 10937600), (49920, 92160, 393216)),
+        16384: ((1494528, 2781696, 12085760), (393984, 436224, 737280)),
+        16385: ((1495552, 2782720, 12086784), (393984, 436992, 738048)),
+        49153: ((3340544, 4627712, 13931776), (1180416, 1223424, 1524480)),
+        98305: ((6108160, 7395328, 16699392), (2360064, 2403072, 2704128)),
+        131072: ((8795904, 10083072, 19387136), (3146496, 3188736, 3489792)),
+        262144: ((16249600, 17536768, 26840832), (6292224, 6334464, 6635520)),
+    }
+    for n, (one, batch) in expected.items():
+        assert tuple(lib.creg_kmeans_workspace_bytes(n, k) for k in ks) == one, n
+        assert tuple(lib.creg_kmeans_batch_workspace_bytes(n, k, 3) for k in ks) == batch, n
+    assert lib.creg_kmeans_workspace_bytes(0, 1) == 0 and lib.creg_kmeans_workspace_bytes(17, 0) == 0
+    assert lib.creg_kmeans_batch_workspace_bytes(17, 1, 0) == 0
+
+
 def test_every_environment_variable_the_library_reads_is_documented():
     """Every getenv("CREG_...") of the library's sources has a row of its own in the "Environment" table of INTEGRATION.md."""
     csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
