@@ -494,6 +494,28 @@ def urdf_fk(table, q, base, want_lines: bool = False):
     return (link_T, lines) if want_lines else link_T
 
 
+def _mesh_pair_args(who, tri, tri_start, link_T, pairs):
+    """The argument checks ``mesh_collide`` and ``mesh_clearance`` share -> (tri, tri_start, link_T (P,L,4,4), pairs, F, P, L, M)."""
+    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
+    tri_start, pairs = _need(tri_start, torch.int64, "tri_start"), _need(pairs, torch.int32, "pairs")
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
+            or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise ValueError(f"{who}: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pairs (M,2) expected, got "
+                         f"{tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, {tuple(pairs.shape)}")
+    F, (P, n_links), M = tri.shape[0], link_T.shape[:2], pairs.shape[0]
+    if n_links < 1:
+        raise ValueError(f"{who}: at least one link")
+    ok = (tri_start[0] == 0) & (tri_start[-1] == F) & (tri_start[1:] >= tri_start[:-1]).all()
+    if M:
+        ok = ok & (pairs >= 0).all() & (pairs < n_links).all() & (pairs[:, 0] != pairs[:, 1]).all()
+    if not bool(ok):
+        raise ValueError(f"{who}: tri_start must run from 0 to {F} without decreasing, and every pair must name two "
+                         f"different links in [0, {n_links})")
+    return tri, tri_start, link_T, pairs, F, P, n_links, M
+
+
 def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
     """Self-collision of posed link meshes (creg_mesh_collide_f64; the contract is in include/creg.h): tri (F,3,3) f64
     link-frame triangles, tri_start (L+1) int64 (link l owns rows tri_start[l]:tri_start[l+1]), link_T (P,L,4,4) f64 -- or
@@ -502,23 +524,7 @@ def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
     every posed link when ``want_boxes``.  One call for all P and M.  Raises for a pair outside [0, L) or naming one link twice
     and for a tri_start that does not run 0 .. F without decreasing (both are read back: the one synchronisation)."""
     L = _lib.load()
-    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
-    tri_start, pairs = _need(tri_start, torch.int64, "tri_start"), _need(pairs, torch.int32, "pairs")
-    if link_T.dim() == 3:
-        link_T = link_T[None]
-    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
-            or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"mesh_collide: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pairs (M,2) expected, got "
-                         f"{tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, {tuple(pairs.shape)}")
-    F, (P, n_links), M = tri.shape[0], link_T.shape[:2], pairs.shape[0]
-    if n_links < 1:
-        raise ValueError("mesh_collide: at least one link")
-    ok = (tri_start[0] == 0) & (tri_start[-1] == F) & (tri_start[1:] >= tri_start[:-1]).all()
-    if M:
-        ok = ok & (pairs >= 0).all() & (pairs < n_links).all() & (pairs[:, 0] != pairs[:, 1]).all()
-    if not bool(ok):
-        raise ValueError(f"mesh_collide: tri_start must run from 0 to {F} without decreasing, and every pair must name two "
-                         f"different links in [0, {n_links})")
+    tri, tri_start, link_T, pairs, F, P, n_links, M = _mesh_pair_args("mesh_collide", tri, tri_start, link_T, pairs)
     dev = tri.device
     count = torch.empty(P, M, dtype=torch.int32, device=dev)
     first = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
@@ -529,6 +535,32 @@ def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
                                        _p(count) if M else None, _p(first) if M else None, _p(boxes), _p(ws), ws_bytes, _stream()),
                "creg_mesh_collide_f64")
     return (count, first, boxes) if want_boxes else (count, first)
+
+
+def mesh_clearance(tri, tri_start, link_T, pairs, d_max, want_boxes: bool = False):
+    """Clearance of posed link meshes (creg_mesh_clearance_f64; the contract is in include/creg.h): the inputs of
+    ``mesh_collide`` and a margin ``d_max`` >= 0 (``inf`` allowed) -> dist (P,M) f64, the minimum distance between the two
+    meshes of every link pair at every pose -- 0.0 where they collide by ``mesh_collide``'s predicate, ``+inf`` where they
+    are farther apart than ``d_max`` (no triangle pair within the margin by the box test, or a found minimum above it) --,
+    witness (P,M,2) int32 the triangle pair (rows of tri) that attains the kernel's minimum, (-1,-1) where no triangle pair
+    was within the margin by the box test, and link_box (P,L,6) when ``want_boxes``.  One call for all P and M; the argument
+    checks are ``mesh_collide``'s, plus a ValueError for a negative or NaN ``d_max``."""
+    L = _lib.load()
+    d_max = float(d_max)
+    if not d_max >= 0.0:
+        raise ValueError(f"mesh_clearance: d_max must be >= 0 (inf allowed), got {d_max}")
+    tri, tri_start, link_T, pairs, F, P, n_links, M = _mesh_pair_args("mesh_clearance", tri, tri_start, link_T, pairs)
+    dev = tri.device
+    dist2 = torch.empty(P, M, dtype=torch.float64, device=dev)
+    witness = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
+    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
+    ws_bytes = L.creg_mesh_clearance_workspace_bytes(F, n_links, P, M)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    _lib.check(L.creg_mesh_clearance_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pairs) if M else None, M,
+                                         d_max, _p(dist2) if M else None, _p(witness) if M else None, _p(boxes), _p(ws), ws_bytes,
+                                         _stream()), "creg_mesh_clearance_f64")
+    dist = torch.where(dist2 > d_max * d_max, torch.full_like(dist2, float("inf")), torch.sqrt(dist2))
+    return (dist, witness, boxes) if want_boxes else (dist, witness)
 
 
 MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")

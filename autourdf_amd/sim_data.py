@@ -24,7 +24,10 @@ project's own contract: the posed ``<visual>`` triangles of every non-adjacent l
 a sequence in one launch (``ops.mesh_collide`` / ``SimEnv.collisions``; include/creg.h states the contract).  PyBullet's
 check -- convex hulls of the ``<collision>`` geometry with Bullet's margins after a physics step -- cannot be pinned without
 PyBullet and is not imitated.  ``data_collection(..., check_collision=True)`` stops a sequence at its first colliding step,
-``collect(..., reject_collisions=True)`` / ``--reject_collisions`` skips colliding seeds.
+``collect(..., reject_collisions=True)`` / ``--reject_collisions`` skips colliding seeds.  A collision margin
+(``collision_margin`` / ``--collision_margin``, ``SimEnv.collisions(margin=...)``) also rejects poses whose links pass closer
+than the margin without touching: the minimum mesh distance of every tested link pair comes from ``ops.mesh_clearance`` /
+``SimEnv.clearance``, again one launch for a sequence.  With no margin the check is the one above, unchanged.
 """
 import os
 import struct
@@ -444,6 +447,18 @@ def ground_mesh(size, cells):
     return np.stack([np.stack([a, b, c], 1), np.stack([a, c, d], 1)], 1).reshape(-1, 3, 3)
 
 
+def _checked_margin(margin):
+    margin = float(margin)
+    if not margin >= 0.0:
+        raise ValueError(f"collision margin must be >= 0 (inf allowed), got {margin}")
+    return margin
+
+
+def _margin_kw(margin):
+    """The keyword a positive margin travels in; none at 0.0, so that the call without margins is today's call."""
+    return {"margin": margin} if _checked_margin(margin) > 0.0 else {}
+
+
 class SimEnv:
     """The part of the reference's SimEnv (sim_data.py:15-64) that describes the robot: revolute joints in URDF
     order with their limits (:66-82), the first ``dof`` of them driven, the rest parked at mid range (:131-157)."""
@@ -561,20 +576,33 @@ class SimEnv:
         u = torch.as_tensor(rng.random((n, 3)), device=tri.device)
         return ops.sample_mesh(tri, cum, own, T, u)
 
-    def collisions(self, link_T, use_excluded=False):
-        """Self and floor contacts of P poses in one launch (creg_mesh_collide_f64): link_T (P,L,4,4) -- or (L,4,4) -- device
-        poses (ops.urdf_fk).  Returns one (self_contact, floor_contact) per pose: self_contact lists (link_a, link_b, count,
-        tri_a, tri_b) for every tested link pair with colliding triangles -- their number and the smallest colliding pair as
-        rows of ``robot.tri``; the tested pairs are ``robot.collision_pairs()``, minus the env's ``excluded_pairs`` when
-        ``use_excluded``.  floor_contact lists the non-root links whose posed box reaches below z = 0, and is empty unless the
-        env was built with ``ground_flag=True`` (the root stands on the ground)."""
+    def _collide_inputs(self, use_excluded):
+        """(host pairs, device pairs, device tri_start) of the tested link pairs, uploaded once per env and choice."""
         tri = self._device_mesh()[0]
         r = self.robot
         key = bool(use_excluded)
         if key not in self._dev_collide:
             host = r.collision_pairs(self.excluded_pairs if key else ())
             self._dev_collide[key] = (host, torch.as_tensor(host, device=tri.device), torch.as_tensor(r.tri_start, device=tri.device))
-        host, pairs, tri_start = self._dev_collide[key]
+        return self._dev_collide[key]
+
+    def collisions(self, link_T, use_excluded=False, margin=0.0):
+        """Self and floor contacts of P poses in one launch (creg_mesh_collide_f64): link_T (P,L,4,4) -- or (L,4,4) -- device
+        poses (ops.urdf_fk).  Returns one (self_contact, floor_contact) per pose: self_contact lists (link_a, link_b, count,
+        tri_a, tri_b) for every tested link pair with colliding triangles -- their number and the smallest colliding pair as
+        rows of ``robot.tri``; the tested pairs are ``robot.collision_pairs()``, minus the env's ``excluded_pairs`` when
+        ``use_excluded``.  floor_contact lists the non-root links whose posed box reaches below z = 0, and is empty unless the
+        env was built with ``ground_flag=True`` (the root stands on the ground).
+        ``margin > 0`` counts a pair closer than ``margin`` as a contact, and a link whose box reaches below z = ``margin`` as a
+        floor contact: the result is ``clearance(link_T, margin, use_excluded)``, whose entries hold the pair's DISTANCE in
+        place of the count (0.0 for a piercing pair) and the closest triangle pair.  ``margin=0.0`` is the check without
+        margins, unchanged."""
+        margin = _checked_margin(margin)
+        if margin > 0.0:
+            return self.clearance(link_T, margin, use_excluded)
+        tri = self._device_mesh()[0]
+        r = self.robot
+        host, pairs, tri_start = self._collide_inputs(use_excluded)
         count, first, box = ops.mesh_collide(tri, tri_start, link_T, pairs, want_boxes=True)
         count, first, low = count.cpu().numpy(), first.cpu().numpy(), box[:, :, 2].cpu().numpy()
         root = r.link_index[r.root]
@@ -586,12 +614,34 @@ class SimEnv:
             out.append((self_c, floor_c))
         return out
 
-    def self_collision_check(self, joint_positions, link_T=None, use_excluded=False):
+    def clearance(self, link_T, margin, use_excluded=False):
+        """How far apart the links are at P poses, in one launch (creg_mesh_clearance_f64 with d_max = ``margin``): link_T as
+        ``collisions`` takes it.  Returns one (near, floor_near) per pose: near lists (link_a, link_b, distance, tri_a, tri_b)
+        for every tested link pair with distance < ``margin`` -- for all tested pairs with ``margin=inf`` --, the minimum
+        distance between the two posed meshes (0.0 where an edge pierces a face) and the triangle pair that attains it as rows
+        of ``robot.tri``.  floor_near lists the non-root links whose posed box reaches below z = ``margin``, on a ground only.
+        A mesh wholly inside another has a positive distance (include/creg.h)."""
+        margin = _checked_margin(margin)
+        tri = self._device_mesh()[0]
+        r = self.robot
+        host, pairs, tri_start = self._collide_inputs(use_excluded)
+        dist, wit, box = ops.mesh_clearance(tri, tri_start, link_T, pairs, margin, want_boxes=True)
+        dist, wit, low = dist.cpu().numpy(), wit.cpu().numpy(), box[:, :, 2].cpu().numpy()
+        root = r.link_index[r.root]
+        out = []
+        for p in range(dist.shape[0]):
+            near = [(r.links[host[m, 0]], r.links[host[m, 1]], float(dist[p, m]), int(wit[p, m, 0]), int(wit[p, m, 1]))
+                    for m in range(dist.shape[1]) if dist[p, m] < margin or margin == np.inf]
+            floor_c = [r.links[l] for l in np.flatnonzero(low[p] < margin) if l != root] if self.ground_tri is not None else []
+            out.append((near, floor_c))
+        return out
+
+    def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
         `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""
         if link_T is None:
             link_T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=self._device_mesh()[0].device)
-        return self.collisions(link_T, use_excluded)[0]
+        return self.collisions(link_T, use_excluded, **_margin_kw(margin))[0]
 
     def reset(self):
         self._dev = None
@@ -617,7 +667,7 @@ def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list)
 
 def data_collection(env, data_path=None, width=800, height=800, visualize=False, angle_list=None, ground_flag=False,
                     noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None,
-                    source="surface", check_collision=False):
+                    source="surface", check_collision=False, collision_margin=0.0):
     """One sequence: for every row of ``angle_list`` pose the robot, sample surface points, keep those that at least one
     camera of the ring sees (``occlusion``: depth buffers of ``width`` x ``height`` like the reference's rendered images,
     sim_data.py:286-306; more samples are drawn until ``oversample * num_points`` visible ones exist), add the
@@ -635,6 +685,8 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     ``excluded_pairs``, as in the reference.  At the first colliding step s it prints ``collision detected`` with the pairs,
     generates and saves only the steps before s, writes no ``noise.txt`` and returns (True, record): the reference breaks at
     that step (sim_data.py:276-281).  With no colliding row the clouds and files are those of ``check_collision=False``.
+    ``collision_margin`` > 0 also stops at a row whose links pass closer than the margin (``SimEnv.collisions(margin=...)``);
+    at 0.0 the check is the one without margins.
     Returns (collision, list of PointCloud) like the reference; collision is False when nothing was checked."""
     if visualize:
         raise NotImplementedError("visualize=True needs Open3D's viewer (out of scope)")
@@ -648,7 +700,8 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
         if poses is None:
             qs = [env.set_joint_positions(cmd) for cmd in np.asarray(angle_list)]
             poses = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
-        for step, (self_c, floor_c) in enumerate(env.collisions(poses[:len(angle_list)], use_excluded=collision_flag)):
+        for step, (self_c, floor_c) in enumerate(env.collisions(poses[:len(angle_list)], use_excluded=collision_flag,
+                                                               **_margin_kw(collision_margin))):
             if len(self_c) + len(floor_c) > 0:
                 print('collision detected', self_c, floor_c)
                 stop = step
@@ -694,25 +747,32 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     return False, record
 
 
-def sequence_collides(env, a_list, use_excluded=False):
+def sequence_collides(env, a_list, use_excluded=False, margin=0.0, closest=None):
     """The link pairs that collide somewhere in the sequence ``a_list`` (num_step, dof): a list of (link_a, link_b) names, a
     floor contact as ('ground', link); empty when every step is free.  One ``ops.urdf_fk`` and one ``SimEnv.collisions`` launch
-    for the whole sequence."""
+    for the whole sequence.  ``margin > 0`` also lists the pairs that pass closer than the margin; a list given as ``closest``
+    then receives (distance, step, link_a, link_b) of the closest such pair."""
     qs = [env.set_joint_positions(cmd) for cmd in np.asarray(a_list)]
     if not qs:
         return []
     link_T = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
-    found = []
-    for self_c, floor_c in env.collisions(link_T, use_excluded):
+    found, best = [], None
+    for step, (self_c, floor_c) in enumerate(env.collisions(link_T, use_excluded, **_margin_kw(margin))):
         for pr in [(c[0], c[1]) for c in self_c] + [("ground", l) for l in floor_c]:
             if pr not in found:
                 found.append(pr)
+        if margin > 0.0:
+            for c in self_c:
+                if best is None or c[2] < best[0]:
+                    best = (c[2], step, c[0], c[1])
+    if closest is not None and best is not None:
+        closest.append(best)
     return found
 
 
 def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, noise=True, num_points=5000,
             num_cameras=20, root=".", source="surface", ground=False, pix=800,
-            reject_collisions=False, max_seeds=100):
+            reject_collisions=False, max_seeds=100, collision_margin=0.0):
     """`epochs` sequences of `num_step` frames under data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/
     -- the directory layout of the reference's collect() (sim_data.py:465-531), which match() globs
     (mlp_reg.py:424).  robot_params needs the reference's keys 'gt' (URDF path), 'dof' and optionally 'sim_ori'.
@@ -721,10 +781,15 @@ def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, 
     robot_params' 'excluded_pairs' applied when its 'collision_exclusion' is true), a colliding seed is skipped with a printed
     line naming its pairs and writes nothing, and the loop stops at `epochs` kept seeds.  After ``max_seeds`` seeds it raises,
     naming the pair that collided most often: the one to put into 'excluded_pairs'.
+    ``collision_margin`` > 0 (with ``reject_collisions``) also skips a seed whose links pass closer than the margin anywhere in
+    its sequence; the printed line then names the closest pair and its distance.
     ``source="depth"`` collects depth-camera frames of ``pix`` x ``pix`` images, ``ground`` stands the robot on the ground
     plane and removes it per camera (the reference's --pix / --ground); the ground needs the depth source."""
     if ground and source != "depth":
         raise ValueError("collect: ground=True needs source='depth' (the surface sampler has no ground to remove)")
+    collision_margin = _checked_margin(collision_margin)
+    if collision_margin > 0.0 and not reject_collisions:
+        raise ValueError("collect: collision_margin needs reject_collisions=True")
     paths, tally, seed = [], {}, 0
     use_excluded = bool(robot_params.get("collision_exclusion", False))
     while len(paths) < epochs:
@@ -738,8 +803,15 @@ def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, 
                      dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras, ground_flag=ground,
                      excluded_pairs=robot_params.get("excluded_pairs", []))
         a_list = angle_list(num_step, step_size, robot_params["dof"], env.joint_limits, np.array([scale] * robot_params["dof"]), seed)
-        hit = sequence_collides(env, a_list, use_excluded) if reject_collisions else []
-        if hit:
+        closest = []
+        if collision_margin > 0.0:
+            hit = sequence_collides(env, a_list, use_excluded, margin=collision_margin, closest=closest)
+        else:
+            hit = sequence_collides(env, a_list, use_excluded) if reject_collisions else []
+        if hit and closest:
+            d, step, la, lb = closest[0]
+            print(f"seed {seed}: within the collision margin {collision_margin:g}: {hit}, closest {la} - {lb} at {d:.6g} (step {step}), skipped")
+        elif hit:
             print(f"seed {seed}: collision detected {hit}, skipped")
             for pr in hit:
                 tally[pr] = tally.get(pr, 0) + 1
@@ -769,12 +841,17 @@ def _parser():
     ap.add_argument('--num_points', type=int, default=5000)
     ap.add_argument('--num_cameras', type=int, default=20)
     ap.add_argument('--reject_collisions', action='store_true', help="skip seeds whose sequence self-collides (or touches the ground), like the reference's collect()")
+    ap.add_argument('--collision_margin', type=float, default=None, help="with --reject_collisions: also skip seeds whose links pass closer than this distance (default: the robot's 'collision_margin' in parameters.json, else 0)")
     return ap
 
 
 def parse_args(argv=None):
     ap = _parser()
     args = ap.parse_args(argv)
+    if args.collision_margin is not None and not args.reject_collisions:
+        ap.error("--collision_margin needs --reject_collisions: the margin belongs to the collision check")
+    if args.collision_margin is not None and not args.collision_margin >= 0:
+        ap.error("--collision_margin must be >= 0")
     if args.ground and not args.depth:
         ap.error("--ground needs --depth: only the depth-camera frames have a ground to remove")
     return args
@@ -782,16 +859,21 @@ def parse_args(argv=None):
 
 def main(argv=None):
     """python -m autourdf_amd.sim_data --robot wx200_5 [...]: the reference's flags (sim_data.py:537-551) minus --gui / --vis,
-    plus --depth and --reject_collisions; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json."""
+    plus --depth, --reject_collisions and --collision_margin; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json,
+    and its 'collision_margin' when the option is not given."""
     import json
     args = parse_args(argv)
     with open('parameters.json') as f:
         params = json.load(f)[args.robot]
     if 'gt' not in params:
         raise SystemExit(f"parameters.json has no 'gt' URDF path for {args.robot!r} (use the reference's parameters.json)")
+    margin = {}
+    if args.reject_collisions:                                    # the option wins over the robot's entry
+        m = args.collision_margin if args.collision_margin is not None else float(params.get("collision_margin", 0.0))
+        margin = {"collision_margin": m} if m > 0 else {}
     for p in collect(args.robot, params, args.num_step, args.step_size, args.epoch, args.scale, not args.no_noise,
                      args.num_points, args.num_cameras, source="depth" if args.depth else "surface", ground=args.ground, pix=args.pix,
-                     reject_collisions=args.reject_collisions):
+                     reject_collisions=args.reject_collisions, **margin):
         print(p)
 
 

@@ -547,6 +547,67 @@ int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start, int64_t n
                           double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Link clearance: for every listed link pair of every pose, in one call, the minimum squared distance between the two posed
+ * triangle meshes and the triangle pair that attains it.  The collision margin of the frame generator rests on it (the reference
+ * rejects near-touching poses through Bullet's margins, which are not imitated; this contract is the project's own).
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T, n_links, n_poses, pairs, n_pairs and link_box are exactly those
+ *              of creg_mesh_collide_f64: the same posed vertices w_i, the same exact min / max boxes.  d_max >= 0 may be +inf.
+ *   max, min   below, max(x, y) and min(x, y) are taken of operands that are never NaN for finite vertices; lo - hi of an empty
+ *              box (+inf | -inf) is +inf.
+ *   box gap    gap2(a, b) = (g_x*g_x + g_y*g_y) + g_z*g_z,  g_k = max(0, max(lo_a[k] - hi_b[k], lo_b[k] - hi_a[k])).
+ *   contributes   triangle pair (a, b) contributes iff gap2(box_a, box_b) <= d_max*d_max (boxes of the three posed vertices).
+ *              This test is part of the contract.  Floating-point subtraction, max, the square of a non-negative and a sum in
+ *              a fixed order are all monotone, so in floating point the gap between two enclosing boxes never exceeds the gap
+ *              between the boxes they enclose: culling by link box, 256-triangle chunk box and tile union box with the same
+ *              formula changes no output.
+ *   d2(a, b)   0.0 when the pair collides by the mesh-collide predicate above (boxes meet, closed comparisons, AND an edge
+ *              properly pierces); otherwise the minimum of 15 terms: pt_tri2(a_i; b_0,b_1,b_2) and pt_tri2(b_i; a_0,a_1,a_2)
+ *              for i = 0,1,2, and seg_seg2(a_i, a_i'; b_j, b_j') for i, j = 0,1,2 with i' = (i+1) mod 3.  Squared distances; no
+ *              square root anywhere.  dot(u,v) = (u_x*v_x + u_y*v_y) + u_z*v_z; clamp01(x) = 0 if x < 0, else 1 if x > 1, else x.
+ *   pt_tri2(p; a,b,c)   ab = b-a, ac = c-a, ap = p-a, bp = p-b, cp = p-c; d1 = dot(ab,ap), d2 = dot(ac,ap), d3 = dot(ab,bp),
+ *              d4 = dot(ac,bp), d5 = dot(ab,cp), d6 = dot(ac,cp).  The first of these that holds decides:
+ *                1  d1 <= 0 && d2 <= 0                          -> dot(ap,ap)                       (vertex a)
+ *                2  d3 >= 0 && d4 <= d3                         -> dot(bp,bp)                       (vertex b)
+ *                3  d6 >= 0 && d5 <= d6                         -> dot(cp,cp)                       (vertex c)
+ *              then with vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4:
+ *                4  vc <= 0 && d1 >= 0 && d3 <= 0               -> den = d1 - d3;  v = d1/den if den > 0 else 0;  w = 0        (edge ab)
+ *                5  vb <= 0 && d2 >= 0 && d6 <= 0               -> den = d2 - d6;  v = 0;  w = d2/den if den > 0 else 0        (edge ac)
+ *                6  va <= 0 && (d4 - d3) >= 0 && (d5 - d6) >= 0 -> den = (d4 - d3) + (d5 - d6);  w = (d4 - d3)/den if den > 0
+ *                                                                  else 0;  v = 1 - w                                          (edge bc)
+ *                7  otherwise                                   -> s = (va + vb) + vc;  v = vb/s, w = vc/s if s > 0 else v = w = 0  (face)
+ *              and for 4..7  q_k = p_k - ((a_k + ab_k*v) + ac_k*w),  result dot(q,q).  (The Voronoi regions of the triangle,
+ *              Ericson's closest point on a triangle, with the vertex tests first.)  Every guard answers with a point of the
+ *              triangle, so a degenerate triangle gives no NaN; its true distance comes from the seg_seg2 terms.
+ *   seg_seg2(p1,q1; p2,q2)   u = q1-p1, v = q2-p2, r = p1-p2; a = dot(u,u), e = dot(v,v), f = dot(v,r), c = dot(u,r),
+ *              b = dot(u,v).  The first that holds:
+ *                1  a <= 0 && e <= 0   -> s = 0, t = 0
+ *                2  a <= 0             -> s = 0, t = clamp01(f/e)
+ *                3  e <= 0             -> t = 0, s = clamp01((0 - c)/a)
+ *                4  otherwise          -> den = a*e - b*b;  s = clamp01((b*f - c*e)/den) if den > 0 else 0;  t = (b*s + f)/e;
+ *                                         if t < 0: t = 0, s = clamp01((0 - c)/a);  else if t > 1: t = 1, s = clamp01((b - c)/a)
+ *              x_k = (p1_k + u_k*s) - (p2_k + v_k*t), result dot(x,x).
+ *   outputs    dist2 (n_poses,n_pairs) fp64: the minimum of d2 over the contributing pairs with a in link pairs[m][0] and b in
+ *              link pairs[m][1]; +inf when none contributes.
+ *              witness (n_poses,n_pairs,2) int32: the lexicographically smallest (a, b), rows of tri, among the contributing
+ *              pairs whose d2 has exactly the bits of the minimum; (-1,-1) when none contributes.
+ *              link_box as in creg_mesh_collide_f64; may be NULL.
+ * A pair that names a link outside [0, n_links), or one link twice, gives +inf and (-1,-1).  n_pairs == 0 fills link_box only.
+ * A value above d_max*d_max can appear: the box gap was small and the triangles farther apart; callers read it as "beyond the
+ * margin".  If the true distance of two links is at most d_max, the pair that attains it contributes, so the result is then the
+ * mesh distance.  As in mesh-collide, a mesh wholly INSIDE another is not detected: it has a positive clearance.
+ * Determinism: nothing is pruned by a running best (computed d2 and computed gap2 are different formulas) and there are no
+ * floating-point atomics -- each block of the pair pass writes one (d2, key = a << 32 | b) partial into its own workspace slot
+ * (pose, pair, block), a finishing pass takes the lexicographic minimum of at most 128 slots.  Two runs give the same bits and
+ * the same witness, and a link pair alone in a call gives the same as among others.
+ * CREG_EINVAL, nothing launched: the argument errors of creg_mesh_collide_f64 (n_poses < 1, n_pairs < 0, n_links < 1 or > 65535,
+ * n_tri < 0 or >= 2^31, a null pointer, null pairs / dist2 / witness with n_pairs > 0, a workspace smaller than
+ * creg_mesh_clearance_workspace_bytes(...): posed vertices, chunk and link boxes, the partials), and a NaN or negative d_max. */
+size_t creg_mesh_clearance_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs);
+int creg_mesh_clearance_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                            int64_t n_poses, const int32_t* pairs, int64_t n_pairs, double d_max, double* dist2, int32_t* witness,
+                            double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Mass properties of closed, outward-oriented link meshes: every link of a call in one set of launches, no host
  * synchronisation.  The reference writes mass 1.0, ixx = iyy = izz = 0.1 and the visual's origin into every <inertial> block
  * ("example values, adjust as needed", PointCloud/compute_joints.py:334-339); this contract is the project's own.
