@@ -563,6 +563,44 @@ def mesh_clearance(tri, tri_start, link_T, pairs, d_max, want_boxes: bool = Fals
     return (dist, witness, boxes) if want_boxes else (dist, witness)
 
 
+MESH_CONTAIN_MAX_POINTS = 16
+
+
+def mesh_contain(tri, tri_start, pts, pt_start, link_T, pairs, want_winding: bool = False, want_boxes: bool = False):
+    """Is a link wholly inside another (creg_mesh_contain_f64; the contract is in include/creg.h): the inputs of
+    ``mesh_collide`` plus pts (N,3) f64 query points in link frames and pt_start (L+1) int64 (link l owns rows
+    pt_start[l]:pt_start[l+1], at most 16 of them; ``UrdfRobot.containment_points``), all on the device -> inside (P,M,2) int32,
+    the number of points of link pairs[m][d] whose generalized winding number in the posed mesh of link pairs[m][1-d] exceeds
+    0.5 in magnitude, first (P,M,2) int32 the smallest such row of pts or -1, then winding (P,M,2,Q) f64 when ``want_winding``
+    (Q the largest point count of a link, at least 1; 0.0 for a point outside the other link's box and for unused slots) and
+    link_box (P,L,6) when ``want_boxes``.  One call for all P, M and both directions; the argument checks are
+    ``mesh_collide``'s, plus a ValueError for a pt_start that does not run 0 .. N without decreasing or gives a link more than
+    16 points."""
+    L = _lib.load()
+    tri, tri_start, link_T, pairs, F, P, n_links, M = _mesh_pair_args("mesh_contain", tri, tri_start, link_T, pairs)
+    pts, pt_start = _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
+    if pts.dim() != 2 or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != n_links + 1:
+        raise ValueError(f"mesh_contain: pts (N,3) / pt_start (L+1) expected, got {tuple(pts.shape)}, {tuple(pt_start.shape)}")
+    N = pts.shape[0]
+    per_link = pt_start[1:] - pt_start[:-1]
+    lo, hi, first_row, last_row = (int(v) for v in torch.stack([per_link.min(), per_link.max(), pt_start[0], pt_start[-1]]).cpu())
+    if first_row != 0 or last_row != N or lo < 0 or hi > MESH_CONTAIN_MAX_POINTS:
+        raise ValueError(f"mesh_contain: pt_start must run from 0 to {N} without decreasing and give a link at most "
+                         f"{MESH_CONTAIN_MAX_POINTS} points")
+    Q = max(hi, 1)
+    dev = tri.device
+    inside = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
+    first = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
+    winding = torch.empty(P, M, 2, Q, dtype=torch.float64, device=dev) if want_winding else None
+    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
+    ws_bytes = L.creg_mesh_contain_workspace_bytes(F, n_links, P, M, Q)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    _lib.check(L.creg_mesh_contain_f64(_p(tri) if F else None, _p(tri_start), F, _p(pts) if N else None, _p(pt_start), N, _p(link_T),
+                                       n_links, P, _p(pairs) if M else None, M, Q, _p(inside) if M else None, _p(first) if M else None,
+                                       _p(winding) if M else None, _p(boxes), _p(ws), ws_bytes, _stream()), "creg_mesh_contain_f64")
+    return (inside, first) + ((winding,) if want_winding else ()) + ((boxes,) if want_boxes else ())
+
+
 MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")
 
 

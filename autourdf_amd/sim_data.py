@@ -28,6 +28,9 @@ PyBullet and is not imitated.  ``data_collection(..., check_collision=True)`` st
 (``collision_margin`` / ``--collision_margin``, ``SimEnv.collisions(margin=...)``) also rejects poses whose links pass closer
 than the margin without touching: the minimum mesh distance of every tested link pair comes from ``ops.mesh_clearance`` /
 ``SimEnv.clearance``, again one launch for a sequence.  With no margin the check is the one above, unchanged.
+Neither check sees a link wholly inside another (no edge pierces a face, and the clearance is positive):
+``containment=True`` / ``--containment`` adds a point-in-mesh query (``ops.mesh_contain`` / ``SimEnv.containment``: winding
+numbers of the posed meshes at ``UrdfRobot.containment_points``), one more launch for a sequence.  Without it nothing changes.
 """
 import os
 import struct
@@ -369,6 +372,32 @@ class UrdfRobot:
         pairs = [(i, j) for i in range(n) for j in range(i + 1, n) if owns[i] and owns[j] and frozenset((i, j)) not in skip]
         return np.asarray(pairs, np.int32).reshape(-1, 2)
 
+    def containment_points(self, max_per_link=16):
+        """(pts (N,3) float64, pt_start (L+1) int64): the query points ``ops.mesh_contain`` poses with each link, in link frames.
+        Per link the vertices are welded by exact equality and the triangle mesh split into connected components; each
+        component gives one point, the first vertex of its first triangle.  Components go by descending triangle count, then by
+        first row, and at most ``max_per_link`` (<= 16) are kept.  One vertex per component suffices: when no edge pierces a
+        face, a connected piece of surface lies wholly on one side of a closed mesh."""
+        from scipy.sparse import coo_matrix
+        from scipy.sparse.csgraph import connected_components
+        if not 1 <= int(max_per_link) <= 16:
+            raise ValueError(f"containment_points: max_per_link must be 1 .. 16, got {max_per_link}")
+        pts, start = [], [0]
+        for l in range(len(self.links)):
+            t = self.tri[self.tri_start[l]:self.tri_start[l + 1]]
+            if len(t):
+                _, vid = np.unique(t.reshape(-1, 3), axis=0, return_inverse=True)
+                vid = vid.reshape(-1, 3)
+                n = int(vid.max()) + 1
+                rows, cols = np.concatenate([vid[:, 0], vid[:, 1]]), np.concatenate([vid[:, 1], vid[:, 2]])
+                _, label = connected_components(coo_matrix((np.ones(len(rows)), (rows, cols)), shape=(n, n)), directed=False)
+                comp = label[vid[:, 0]]                              # a triangle's three vertices share one component
+                ids, first_row, count = np.unique(comp, return_index=True, return_counts=True)
+                order = np.lexsort((first_row, -count))[:int(max_per_link)]
+                pts.extend(t[first_row[order], 0])
+            start.append(len(pts))
+        return np.asarray(pts, np.float64).reshape(-1, 3), np.asarray(start, np.int64)
+
     def fk(self, q_by_joint, base=None):
         """Link poses (L,4,4) float64 for joint positions {name: value} (missing joints at 0)."""
         T = np.tile(np.eye(4), (len(self.links), 1, 1))
@@ -459,6 +488,17 @@ def _margin_kw(margin):
     return {"margin": margin} if _checked_margin(margin) > 0.0 else {}
 
 
+def _containment_kw(containment):
+    """The keyword the containment check travels in; none when it is off, so that the call without it is today's call."""
+    return {"containment": True} if containment else {}
+
+
+def _inside_lines(env, link_T, use_excluded):
+    """['X inside Y (step s)', ...] of a sequence, for the printed lines of the callers below (one more launch)."""
+    return [f"{inner} inside {outer} (step {step})" for step, found in enumerate(env.containment(link_T, use_excluded))
+            for inner, outer, _, _ in found]
+
+
 class SimEnv:
     """The part of the reference's SimEnv (sim_data.py:15-64) that describes the robot: revolute joints in URDF
     order with their limits (:66-82), the first ``dof`` of them driven, the rest parked at mid range (:131-157)."""
@@ -480,6 +520,7 @@ class SimEnv:
         self._dev = None
         self._dev_raster = None
         self._dev_collide = {}
+        self._dev_contain = None
         self.excluded_pairs = [tuple(pr) for pr in excluded_pairs]   # parameters.json's 'excluded_pairs' (link names)
         self._setup_cameras(radius, num_cameras)
         # the ground the reference stands its robot on (ground_flag): seen by the raster passes of depth_cloud only
@@ -586,7 +627,42 @@ class SimEnv:
             self._dev_collide[key] = (host, torch.as_tensor(host, device=tri.device), torch.as_tensor(r.tri_start, device=tri.device))
         return self._dev_collide[key]
 
-    def collisions(self, link_T, use_excluded=False, margin=0.0):
+    def _contain_inputs(self):
+        """(device pts, device pt_start, host pt_start) of ``robot.containment_points()``, uploaded once per env."""
+        if self._dev_contain is None:
+            dev = self._device_mesh()[0].device
+            pts, start = self.robot.containment_points()
+            self._dev_contain = (torch.as_tensor(pts, device=dev), torch.as_tensor(start, device=dev), start)
+        return self._dev_contain
+
+    def _inside(self, link_T, use_excluded):
+        """Per pose a list of (m, inner_link, outer_link, n_inside, winding of the first inside point): one launch
+        (creg_mesh_contain_f64) over the tested pairs in both directions."""
+        tri = self._device_mesh()[0]
+        r = self.robot
+        host, pairs, tri_start = self._collide_inputs(use_excluded)
+        pts, pt_start, h_start = self._contain_inputs()
+        inside, first, wind = ops.mesh_contain(tri, tri_start, pts, pt_start, link_T, pairs, want_winding=True)
+        inside, first, wind = inside.cpu().numpy(), first.cpu().numpy(), wind.cpu().numpy()
+        out = []
+        for p in range(inside.shape[0]):
+            found = []
+            for m, d in zip(*np.nonzero(inside[p])):
+                inner, outer = host[m, d], host[m, 1 - d]
+                found.append((int(m), r.links[inner], r.links[outer], int(inside[p, m, d]),
+                              float(wind[p, m, d, first[p, m, d] - h_start[inner]])))
+            out.append(found)
+        return out
+
+    def containment(self, link_T, use_excluded=False):
+        """Links wholly inside another at P poses, in one launch (creg_mesh_contain_f64): link_T as ``collisions`` takes it.
+        Returns per pose a list of (inner_link, outer_link, n_inside, winding) for every tested pair and direction with an
+        inside point: how many of the inner link's ``robot.containment_points()`` have a winding number above 0.5 in magnitude
+        in the outer link's posed mesh, and the winding number of the first of them.  Not detected: a shell beyond a link's 16
+        largest connected components, and a point on the surface."""
+        return [[f[1:] for f in found] for found in self._inside(link_T, use_excluded)]
+
+    def collisions(self, link_T, use_excluded=False, margin=0.0, containment=False):
         """Self and floor contacts of P poses in one launch (creg_mesh_collide_f64): link_T (P,L,4,4) -- or (L,4,4) -- device
         poses (ops.urdf_fk).  Returns one (self_contact, floor_contact) per pose: self_contact lists (link_a, link_b, count,
         tri_a, tri_b) for every tested link pair with colliding triangles -- their number and the smallest colliding pair as
@@ -596,10 +672,12 @@ class SimEnv:
         ``margin > 0`` counts a pair closer than ``margin`` as a contact, and a link whose box reaches below z = ``margin`` as a
         floor contact: the result is ``clearance(link_T, margin, use_excluded)``, whose entries hold the pair's DISTANCE in
         place of the count (0.0 for a piercing pair) and the closest triangle pair.  ``margin=0.0`` is the check without
-        margins, unchanged."""
+        margins, unchanged.
+        ``containment=True`` also lists a pair with a link wholly inside the other (``containment``: one more launch) that is
+        not listed already, as (link_a, link_b, 0, -1, -1) in the tested pair's order; ``False`` makes no such launch."""
         margin = _checked_margin(margin)
         if margin > 0.0:
-            return self.clearance(link_T, margin, use_excluded)
+            return self.clearance(link_T, margin, use_excluded, **_containment_kw(containment))
         tri = self._device_mesh()[0]
         r = self.robot
         host, pairs, tri_start = self._collide_inputs(use_excluded)
@@ -612,15 +690,24 @@ class SimEnv:
                       for m in np.flatnonzero(count[p])]
             floor_c = [r.links[l] for l in np.flatnonzero(low[p] < 0) if l != root] if self.ground_tri is not None else []
             out.append((self_c, floor_c))
+        if containment:
+            for (self_c, _), found in zip(out, self._inside(link_T, use_excluded)):
+                for m in sorted({f[0] for f in found}):
+                    pr = (r.links[host[m, 0]], r.links[host[m, 1]])
+                    if pr not in [c[:2] for c in self_c]:
+                        self_c.append(pr + (0, -1, -1))
         return out
 
-    def clearance(self, link_T, margin, use_excluded=False):
+    def clearance(self, link_T, margin, use_excluded=False, containment=False):
         """How far apart the links are at P poses, in one launch (creg_mesh_clearance_f64 with d_max = ``margin``): link_T as
         ``collisions`` takes it.  Returns one (near, floor_near) per pose: near lists (link_a, link_b, distance, tri_a, tri_b)
         for every tested link pair with distance < ``margin`` -- for all tested pairs with ``margin=inf`` --, the minimum
         distance between the two posed meshes (0.0 where an edge pierces a face) and the triangle pair that attains it as rows
         of ``robot.tri``.  floor_near lists the non-root links whose posed box reaches below z = ``margin``, on a ground only.
-        A mesh wholly inside another has a positive distance (include/creg.h)."""
+        A mesh wholly inside another has a positive distance (include/creg.h) unless ``containment=True``: then a pair with
+        a link wholly inside the other (``containment``: one more launch) gets distance 0.0 -- a listed entry keeps its
+        witness, an unlisted pair is added with the witness (-1, -1).  Still not detected: a shell beyond a link's 16 largest
+        connected components, and a point on the surface."""
         margin = _checked_margin(margin)
         tri = self._device_mesh()[0]
         r = self.robot
@@ -634,19 +721,29 @@ class SimEnv:
                     for m in range(dist.shape[1]) if dist[p, m] < margin or margin == np.inf]
             floor_c = [r.links[l] for l in np.flatnonzero(low[p] < margin) if l != root] if self.ground_tri is not None else []
             out.append((near, floor_c))
+        if containment:
+            for (near, _), found in zip(out, self._inside(link_T, use_excluded)):
+                for m in sorted({f[0] for f in found}):
+                    pr = (r.links[host[m, 0]], r.links[host[m, 1]])
+                    at = [i for i, c in enumerate(near) if c[:2] == pr]
+                    if at:
+                        near[at[0]] = pr + (0.0,) + near[at[0]][3:]
+                    else:
+                        near.append(pr + (0.0, -1, -1))
         return out
 
-    def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0):
+    def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0, containment=False):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
         `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""
         if link_T is None:
             link_T = torch.as_tensor(self.robot.fk(joint_positions, self.base), device=self._device_mesh()[0].device)
-        return self.collisions(link_T, use_excluded, **_margin_kw(margin))[0]
+        return self.collisions(link_T, use_excluded, **_margin_kw(margin), **_containment_kw(containment))[0]
 
     def reset(self):
         self._dev = None
         self._dev_raster = None
         self._dev_collide = {}
+        self._dev_contain = None
 
 
 def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list):
@@ -667,7 +764,7 @@ def save_step_data(step_id, combined_pcds, joint_positions, data_path, dof_list)
 
 def data_collection(env, data_path=None, width=800, height=800, visualize=False, angle_list=None, ground_flag=False,
                     noise_flag=False, num_points=5000, collision_flag=False, oversample=4, seed=0, occlusion=True, link_T=None,
-                    source="surface", check_collision=False, collision_margin=0.0):
+                    source="surface", check_collision=False, collision_margin=0.0, containment=False):
     """One sequence: for every row of ``angle_list`` pose the robot, sample surface points, keep those that at least one
     camera of the ring sees (``occlusion``: depth buffers of ``width`` x ``height`` like the reference's rendered images,
     sim_data.py:286-306; more samples are drawn until ``oversample * num_points`` visible ones exist), add the
@@ -686,7 +783,8 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     generates and saves only the steps before s, writes no ``noise.txt`` and returns (True, record): the reference breaks at
     that step (sim_data.py:276-281).  With no colliding row the clouds and files are those of ``check_collision=False``.
     ``collision_margin`` > 0 also stops at a row whose links pass closer than the margin (``SimEnv.collisions(margin=...)``);
-    at 0.0 the check is the one without margins.
+    at 0.0 the check is the one without margins.  ``containment=True`` (with ``check_collision``) also stops at a row with a
+    link wholly inside another (``SimEnv.collisions(containment=True)``) and prints ``X inside Y`` for it.
     Returns (collision, list of PointCloud) like the reference; collision is False when nothing was checked."""
     if visualize:
         raise NotImplementedError("visualize=True needs Open3D's viewer (out of scope)")
@@ -701,9 +799,12 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
             qs = [env.set_joint_positions(cmd) for cmd in np.asarray(angle_list)]
             poses = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
         for step, (self_c, floor_c) in enumerate(env.collisions(poses[:len(angle_list)], use_excluded=collision_flag,
-                                                               **_margin_kw(collision_margin))):
+                                                               **_margin_kw(collision_margin), **_containment_kw(containment))):
             if len(self_c) + len(floor_c) > 0:
                 print('collision detected', self_c, floor_c)
+                if containment:
+                    for inner, outer, _, _ in env.containment(poses[step], collision_flag)[0]:
+                        print(f"{inner} inside {outer}")
                 stop = step
                 break
     rng = np.random.default_rng(seed)
@@ -747,17 +848,20 @@ def data_collection(env, data_path=None, width=800, height=800, visualize=False,
     return False, record
 
 
-def sequence_collides(env, a_list, use_excluded=False, margin=0.0, closest=None):
+def sequence_collides(env, a_list, use_excluded=False, margin=0.0, closest=None, containment=False, inside=None):
     """The link pairs that collide somewhere in the sequence ``a_list`` (num_step, dof): a list of (link_a, link_b) names, a
     floor contact as ('ground', link); empty when every step is free.  One ``ops.urdf_fk`` and one ``SimEnv.collisions`` launch
     for the whole sequence.  ``margin > 0`` also lists the pairs that pass closer than the margin; a list given as ``closest``
-    then receives (distance, step, link_a, link_b) of the closest such pair."""
+    then receives (distance, step, link_a, link_b) of the closest such pair.  ``containment=True`` also lists the pairs with a
+    link wholly inside the other; a list given as ``inside`` then receives 'X inside Y (step s)' strings."""
     qs = [env.set_joint_positions(cmd) for cmd in np.asarray(a_list)]
     if not qs:
         return []
     link_T = ops.urdf_fk(env.robot.fk_table(), env.robot.q_rows(qs), env.base)
     found, best = [], None
-    for step, (self_c, floor_c) in enumerate(env.collisions(link_T, use_excluded, **_margin_kw(margin))):
+    if containment and inside is not None:
+        inside.extend(_inside_lines(env, link_T, use_excluded))
+    for step, (self_c, floor_c) in enumerate(env.collisions(link_T, use_excluded, **_margin_kw(margin), **_containment_kw(containment))):
         for pr in [(c[0], c[1]) for c in self_c] + [("ground", l) for l in floor_c]:
             if pr not in found:
                 found.append(pr)
@@ -772,7 +876,7 @@ def sequence_collides(env, a_list, use_excluded=False, margin=0.0, closest=None)
 
 def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, noise=True, num_points=5000,
             num_cameras=20, root=".", source="surface", ground=False, pix=800,
-            reject_collisions=False, max_seeds=100, collision_margin=0.0):
+            reject_collisions=False, max_seeds=100, collision_margin=0.0, containment=False):
     """`epochs` sequences of `num_step` frames under data/raw/{robot}/{step_size}_deg_{num_cameras}_cams/V{seed:04}/
     -- the directory layout of the reference's collect() (sim_data.py:465-531), which match() globs
     (mlp_reg.py:424).  robot_params needs the reference's keys 'gt' (URDF path), 'dof' and optionally 'sim_ori'.
@@ -782,7 +886,9 @@ def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, 
     line naming its pairs and writes nothing, and the loop stops at `epochs` kept seeds.  After ``max_seeds`` seeds it raises,
     naming the pair that collided most often: the one to put into 'excluded_pairs'.
     ``collision_margin`` > 0 (with ``reject_collisions``) also skips a seed whose links pass closer than the margin anywhere in
-    its sequence; the printed line then names the closest pair and its distance.
+    its sequence; the printed line then names the closest pair and its distance.  ``containment=True`` (with
+    ``reject_collisions``) also skips a seed with a link wholly inside another anywhere in its sequence, which neither of the two
+    checks above can see; the printed line then says ``X inside Y``.
     ``source="depth"`` collects depth-camera frames of ``pix`` x ``pix`` images, ``ground`` stands the robot on the ground
     plane and removes it per camera (the reference's --pix / --ground); the ground needs the depth source."""
     if ground and source != "depth":
@@ -790,6 +896,8 @@ def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, 
     collision_margin = _checked_margin(collision_margin)
     if collision_margin > 0.0 and not reject_collisions:
         raise ValueError("collect: collision_margin needs reject_collisions=True")
+    if containment and not reject_collisions:
+        raise ValueError("collect: containment needs reject_collisions=True")
     paths, tally, seed = [], {}, 0
     use_excluded = bool(robot_params.get("collision_exclusion", False))
     while len(paths) < epochs:
@@ -803,12 +911,17 @@ def collect(robot, robot_params, num_step=10, step_size=4, epochs=5, scale=0.9, 
                      dof=robot_params["dof"], radius=robot_params.get("cam_dist", 1.5), num_cameras=num_cameras, ground_flag=ground,
                      excluded_pairs=robot_params.get("excluded_pairs", []))
         a_list = angle_list(num_step, step_size, robot_params["dof"], env.joint_limits, np.array([scale] * robot_params["dof"]), seed)
-        closest = []
+        closest, inside = [], []
+        contain = {"containment": True, "inside": inside} if containment else {}
         if collision_margin > 0.0:
-            hit = sequence_collides(env, a_list, use_excluded, margin=collision_margin, closest=closest)
+            hit = sequence_collides(env, a_list, use_excluded, margin=collision_margin, closest=closest, **contain)
         else:
-            hit = sequence_collides(env, a_list, use_excluded) if reject_collisions else []
-        if hit and closest:
+            hit = sequence_collides(env, a_list, use_excluded, **contain) if reject_collisions else []
+        if hit and inside:
+            print(f"seed {seed}: {', '.join(inside)}: collision detected {hit}, skipped")
+            for pr in hit:
+                tally[pr] = tally.get(pr, 0) + 1
+        elif hit and closest:
             d, step, la, lb = closest[0]
             print(f"seed {seed}: within the collision margin {collision_margin:g}: {hit}, closest {la} - {lb} at {d:.6g} (step {step}), skipped")
         elif hit:
@@ -842,12 +955,15 @@ def _parser():
     ap.add_argument('--num_cameras', type=int, default=20)
     ap.add_argument('--reject_collisions', action='store_true', help="skip seeds whose sequence self-collides (or touches the ground), like the reference's collect()")
     ap.add_argument('--collision_margin', type=float, default=None, help="with --reject_collisions: also skip seeds whose links pass closer than this distance (default: the robot's 'collision_margin' in parameters.json, else 0)")
+    ap.add_argument('--containment', action='store_true', default=None, help="with --reject_collisions: also skip seeds with a link wholly inside another (default: the robot's 'collision_containment' in parameters.json, else off)")
     return ap
 
 
 def parse_args(argv=None):
     ap = _parser()
     args = ap.parse_args(argv)
+    if args.containment and not args.reject_collisions:
+        ap.error("--containment needs --reject_collisions: containment belongs to the collision check")
     if args.collision_margin is not None and not args.reject_collisions:
         ap.error("--collision_margin needs --reject_collisions: the margin belongs to the collision check")
     if args.collision_margin is not None and not args.collision_margin >= 0:
@@ -859,8 +975,8 @@ def parse_args(argv=None):
 
 def main(argv=None):
     """python -m autourdf_amd.sim_data --robot wx200_5 [...]: the reference's flags (sim_data.py:537-551) minus --gui / --vis,
-    plus --depth, --reject_collisions and --collision_margin; reads 'gt' / 'dof' / 'sim_ori' of the robot from ./parameters.json,
-    and its 'collision_margin' when the option is not given."""
+    plus --depth, --reject_collisions, --collision_margin and --containment; reads 'gt' / 'dof' / 'sim_ori' of the robot from
+    ./parameters.json, and its 'collision_margin' / 'collision_containment' when the option is not given."""
     import json
     args = parse_args(argv)
     with open('parameters.json') as f:
@@ -871,6 +987,8 @@ def main(argv=None):
     if args.reject_collisions:                                    # the option wins over the robot's entry
         m = args.collision_margin if args.collision_margin is not None else float(params.get("collision_margin", 0.0))
         margin = {"collision_margin": m} if m > 0 else {}
+        if args.containment or (args.containment is None and bool(params.get("collision_containment", False))):
+            margin["containment"] = True
     for p in collect(args.robot, params, args.num_step, args.step_size, args.epoch, args.scale, not args.no_noise,
                      args.num_points, args.num_cameras, source="depth" if args.depth else "surface", ground=args.ground, pix=args.pix,
                      reject_collisions=args.reject_collisions, **margin):

@@ -526,7 +526,7 @@ int creg_urdf_fk_f64(const int32_t* parent, const int32_t* child, const int32_t*
  *              orient(a,b,c,p) and orient(a,b,c,q) have strictly opposite signs AND orient(p,q,a,b), orient(p,q,b,c),
  *              orient(p,q,c,a) are all > 0 or all < 0.  A zero anywhere is "no": touching, an edge through a vertex or
  *              through an edge, and coplanar overlap are not collisions; links mounted flush do not collide.  A mesh wholly
- *              INSIDE another is not detected (no edge pierces a face).
+ *              INSIDE another is not detected here (no edge pierces a face): creg_mesh_contain_f64 below detects it when asked.
  *   culling    link boxes, boxes of 256-triangle chunks and tile union boxes are exact min / max of the same posed vertices,
  *              so with (1) in the contract they are exactly conservative: culling changes no output.
  * pairs (n_pairs,2) int32 link indices; which pairs to test (adjacent links intersect at every pose and are left out by the
@@ -594,7 +594,8 @@ int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start, int64_t n
  * A pair that names a link outside [0, n_links), or one link twice, gives +inf and (-1,-1).  n_pairs == 0 fills link_box only.
  * A value above d_max*d_max can appear: the box gap was small and the triangles farther apart; callers read it as "beyond the
  * margin".  If the true distance of two links is at most d_max, the pair that attains it contributes, so the result is then the
- * mesh distance.  As in mesh-collide, a mesh wholly INSIDE another is not detected: it has a positive clearance.
+ * mesh distance.  As in mesh-collide, a mesh wholly INSIDE another is not detected here: it has a positive clearance
+ * (creg_mesh_contain_f64 below detects it when asked).
  * Determinism: nothing is pruned by a running best (computed d2 and computed gap2 are different formulas) and there are no
  * floating-point atomics -- each block of the pair pass writes one (d2, key = a << 32 | b) partial into its own workspace slot
  * (pose, pair, block), a finishing pass takes the lexicographic minimum of at most 128 slots.  Two runs give the same bits and
@@ -606,6 +607,56 @@ size_t creg_mesh_clearance_workspace_bytes(int64_t n_tri, int32_t n_links, int64
 int creg_mesh_clearance_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
                             int64_t n_poses, const int32_t* pairs, int64_t n_pairs, double d_max, double* dist2, int32_t* witness,
                             double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Containment: is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
+ * call, the generalized winding number of one link's posed triangle mesh at a few points of the other.  It closes the hole the
+ * two entries above share (no edge pierces a face when a mesh lies wholly inside another); the reference rejects such a pose
+ * because Bullet's hulls overlap.  The winding number is +1 inside a closed outward-oriented mesh, -1 inside an inward-oriented
+ * one, 0 outside a closed mesh, and degrades smoothly on a mesh with holes.  This contract is the project's own.
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T, n_links, n_poses, pairs, n_pairs and link_box are exactly those
+ *              of creg_mesh_collide_f64: the same posed vertices w_i in the same operation order, the same exact min / max link
+ *              boxes.  pts (n_pts,3) fp64: query points in link frames; link l owns rows pt_start[l] .. pt_start[l+1]
+ *              (pt_start (n_links+1) int64, clamped into 0 .. n_pts like tri_start).  A link owns 0 .. 16 points, and q_stride
+ *              (1 .. 16) is at least every link's count.  A point is posed by the vertex formula with its own link's pose.
+ *   direction  for pair m, direction 0 tests the points of link pairs[m][0] against the mesh of link pairs[m][1]; direction 1
+ *              the points of pairs[m][1] against the mesh of pairs[m][0].
+ *   gate       a posed point x is evaluated against link b iff lo_b[k] <= x[k] <= hi_b[k] on all three axes (closed
+ *              comparisons, the exact link box).  Otherwise its winding is exactly 0.0 and nothing is summed.  The gate is part of
+ *              the contract and the only cull: a chunk box cannot cull a winding sum.
+ *   term       per posed triangle (v0,v1,v2) of link b:  a = v0 - x, b = v1 - x, c = v2 - x;  la = sqrt(dot(a,a)), lb and lc
+ *              likewise;  det = dot(a, cross(b,c));  den = (((la*lb)*lc + dot(a,b)*lc) + dot(b,c)*la) + dot(c,a)*lb;
+ *              omega = 2*atan2(det, den)  -- dot and cross as defined above, in exactly this order, no contraction; atan2 and
+ *              sqrt are the device library's.  Finite inputs give no NaN; a triangle with two equal vertices gives exactly 0, a
+ *              collinear one a value at rounding level.  A point ON the surface gives a finite value, but which one is outside
+ *              what this contract promises.
+ *   sum        per point, S = the terms of link b's triangles added in the fixed tree of creg_mesh_inertia_f64 (leaves in
+ *              order, padded with zeros to a multiple of 256; per 256 leaves four 64-lane butterflies, then ((w0+w1)+w2)+w3; the
+ *              chunk results are the leaves of the next level; at least one such level runs).  The tree depends on link b's
+ *              triangle count alone.  w = S / (4*pi), and the point is inside iff fabs(w) > 0.5.
+ *   outputs    inside (n_poses,n_pairs,2) int32: the number of inside points per direction.
+ *              first (n_poses,n_pairs,2) int32: the smallest inside row of pts, or -1.
+ *              winding (n_poses,n_pairs,2,q_stride) fp64, may be NULL: w of the link's points in their order; a slot beyond the
+ *              link's count and a gated-out point hold 0.0.
+ *              link_box as in creg_mesh_collide_f64; may be NULL.
+ * A pair that names a link outside [0, n_links), or one link twice, gives 0, -1 and zeros.  n_pairs == 0 fills link_box only.
+ * Every output element is written by every successful call.
+ * Determinism: no floating-point atomics -- each block of the pair pass stores one partial per (pose, pair, direction, point,
+ * chunk) into its own workspace slot, a finishing pass runs the upper tree levels.  Two runs give the same bits, and a pair alone
+ * in a call gives the same bits as among others.
+ * pt_start is read back by the host before anything is launched (the one stream synchronisation of this entry).
+ * CREG_EINVAL, nothing launched: the argument errors of creg_mesh_collide_f64 (n_poses < 1, n_pairs < 0, n_links < 1 or > 65535,
+ * n_tri < 0 or >= 2^31, a null pointer, null pairs / inside / first with n_pairs > 0), n_pts < 0 or >= 2^31, a null pts (with
+ * n_pts > 0) or pt_start, q_stride outside 1 .. 16, a link that owns more points than q_stride (so more than 16), a workspace
+ * smaller than creg_mesh_contain_workspace_bytes(...): posed vertices, chunk and link boxes and
+ * n_poses * n_pairs * 2 * q_stride * max(1, ceil(n_tri/256)) partials.
+ * Not detected: a shell of a link beyond the 16 points the caller chose (UrdfRobot.containment_points takes one point per
+ * connected component, the largest first), and a point on the surface. */
+size_t creg_mesh_contain_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs, int32_t q_stride);
+int creg_mesh_contain_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* pts, const int64_t* pt_start,
+                          int64_t n_pts, const double* link_T, int32_t n_links, int64_t n_poses, const int32_t* pairs,
+                          int64_t n_pairs, int32_t q_stride, int32_t* inside, int32_t* first, double* winding, double* link_box,
+                          void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Mass properties of closed, outward-oriented link meshes: every link of a call in one set of launches, no host
