@@ -242,3 +242,105 @@ def set_inertials(urdf_file, inertials):
         inertial.find("inertia").attrib.update(ixx=str(I[0, 0]), ixy=str(I[0, 1]), ixz=str(I[0, 2]), iyy=str(I[1, 1]),
                                                iyz=str(I[1, 2]), izz=str(I[2, 2]))
     tree.write(urdf_file, encoding="utf-8", xml_declaration=True)
+
+
+def estimate_joint_motion(links, joint_data, cm_list, start_step=0, num_steps=500, time_step=0):
+    """Where every joint of ``joint_data`` stood at every step of every sequence, and how well "one revolute axis through one
+    point" explains the two links' relative motion (this project's own; ``ops.link_poses`` and ``ops.joint_positions``, three
+    launches in all).  The position is zero at sequence 0, step ``time_step``: the pose ``create_urdf`` writes as the URDF's
+    zero.  One dict per joint, in ``joint_data``'s order: parent_link, child_link, positions (S,num_steps) rad unwrapped along
+    each sequence, lower, upper (the observed range), lower_at, upper_at ((sequence, step) of each, None without a usable
+    sample), tilt_rms, tilt_max (rad: the rotation the axis does not explain), slip_rms, slip_max (how far the joint point
+    moves in the child's frame) and n_used (samples with finite figures).  No figure is turned into a verdict.  IndexError
+    for steps past T, as numpy indexing would raise."""
+    by_id = {l["id"]: i for i, l in enumerate(links)}
+    pairs = [(by_id[j["parent_link"]], by_id[j["child_link"]]) for j in joint_data]
+    link_T = ops.link_poses(_coords(cm_list), [list(l["cluster_idx"]) for l in links])
+    out = ops.joint_positions(link_T, pairs, np.array([j["local_axis"] for j in joint_data], np.float64).reshape(-1, 3),
+                              np.array([np.asarray(j["local_pos"], np.float64)[:3] for j in joint_data]).reshape(-1, 3),
+                              0, time_step, start_step, num_steps)
+    res = {k: v.cpu().numpy() for k, v in out.items()}
+    motion = []
+    for j, jd in enumerate(joint_data):
+        used = int(res["n_used"][j])
+        at = lambda a: (int(a[0]), int(start_step + a[1])) if used else None
+        m = {"parent_link": jd["parent_link"], "child_link": jd["child_link"], "positions": res["q"][j],
+             "lower_at": at(res["lower_at"][j]), "upper_at": at(res["upper_at"][j]), "n_used": used}
+        m.update({k: float(res[k][j]) for k in ("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")})
+        motion.append(m)
+    return motion
+
+
+def set_joint_limits(urdf_file, motion, pad=0.0):
+    """Rewrite the <limit> of every joint ``motion`` names (``estimate_joint_motion``'s list; joint ``joint_{child_link}``) with
+    its observed range: lower = min(lower - pad, 0), upper = max(upper + pad, 0) in rad, written with ``str()``, so the file's
+    zero pose stays inside the limits.  A joint whose padded span reaches 2 pi becomes type="continuous" and loses lower and
+    upper.  Effort, velocity, every other element, the indentation and the XML declaration stay as ``create_urdf`` wrote them.
+    KeyError for a joint the file does not have, ValueError for one without a <limit>, with n_used = 0 or a negative pad;
+    nothing is written in either case."""
+    pad = float(pad)
+    if not pad >= 0.0:
+        raise ValueError(f"set_joint_limits: pad must be >= 0 rad, got {pad}")
+    tree = ET.parse(urdf_file)
+    by_name = {j.get("name"): j for j in tree.getroot().findall("joint")}
+    todo = []
+    for m in motion:
+        name = f"joint_{m['child_link']}"
+        joint = by_name[name]
+        limit = joint.find("limit")
+        if limit is None:
+            raise ValueError(f"{urdf_file}: joint {name} has no <limit> to rewrite")
+        if m["n_used"] == 0 or not (np.isfinite(m["lower"]) and np.isfinite(m["upper"])):
+            raise ValueError(f"{urdf_file}: joint {name} has no usable sample, its range is undefined")
+        todo.append((joint, limit, min(float(m["lower"]) - pad, 0.0), max(float(m["upper"]) + pad, 0.0)))
+    for joint, limit, lower, upper in todo:
+        if upper - lower >= 2.0 * np.pi:
+            joint.set("type", "continuous")
+            for k in ("lower", "upper"):
+                limit.attrib.pop(k, None)
+        else:
+            limit.attrib.update(lower=str(lower), upper=str(upper))
+    tree.write(urdf_file, encoding="utf-8", xml_declaration=True)
+
+
+def replay_urdf(urdf_file, links, motion, cm_list, start_step, num_steps, time_step=0):
+    """Check the written URDF without a ground truth: pose it at every recovered joint position (and at zero) in one
+    ``ops.urdf_fk`` call and compare how each link moved from the zero pose with how the registration saw it move from
+    sequence 0, step ``time_step`` (``ops.link_poses``, ``ops.motion_error``; the compared point is the registered link
+    position at that step).  The file's meshes are not read.  One dict per link, in ``links``' order: link (id), rot_rms,
+    rot_max (rad), pos_rms, pos_max (the clouds' unit), rot_max_at, pos_max_at ((sequence, step), None when no sample is
+    finite) and n_used."""
+    from .sim_data import UrdfRobot
+    robot = UrdfRobot(urdf_file, load_meshes=False)
+    coords = _coords(cm_list)
+    reg = ops.link_poses(coords, [list(l["cluster_idx"]) for l in links])      # (S,T,L,4,4)
+    S, n, n_links = reg.shape[0], int(num_steps), len(links)
+    if start_step < 0 or n < 1 or start_step + n > reg.shape[1]:
+        raise IndexError(f"steps [{start_step}, {start_step + n}) are out of bounds for axis 0 with size {reg.shape[1]}")
+    q_by_name = {f"joint_{m['child_link']}": np.asarray(m["positions"], np.float64).reshape(S, n) for m in motion}
+    names = robot.fk_table()["names"]
+    q = np.zeros((S * n + 1, len(names)))                                      # the last row is the zero pose
+    for col, name in enumerate(names):
+        if name in q_by_name:
+            q[:-1, col] = q_by_name[name].reshape(-1)
+    fk = ops.urdf_fk(robot.fk_table(), q, np.eye(4))                           # (S*n+1, L_urdf, 4, 4)
+    order = torch.as_tensor([robot.link_index[f"link_{l['id']}"] for l in links], device=fk.device)
+    fk = fk[:, order]
+    B = reg[:, start_step:start_step + n].reshape(S * n, n_links, 4, 4)
+    B0 = reg[0, time_step].contiguous()
+    rot, pos = ops.motion_error(fk[:-1].contiguous(), fk[-1].contiguous(), B.contiguous(), B0, B0[:, :3, 3].contiguous())
+    rot, pos = rot.cpu().numpy().reshape(S, n, n_links), pos.cpu().numpy().reshape(S, n, n_links)
+    report = []
+    for i, l in enumerate(links):
+        ok = np.isfinite(rot[:, :, i]) & np.isfinite(pos[:, :, i])
+        r = {"link": l["id"], "n_used": int(ok.sum())}
+        for key, e in (("rot", rot[:, :, i]), ("pos", pos[:, :, i])):
+            if ok.any():
+                e = np.where(ok, e, -np.inf)
+                s, k = np.unravel_index(np.argmax(e), e.shape)
+                r.update({f"{key}_rms": float(np.sqrt((e[ok] ** 2).sum() / ok.sum())), f"{key}_max": float(e[s, k]),
+                          f"{key}_max_at": (int(s), int(start_step + k))})
+            else:
+                r.update({f"{key}_rms": float("nan"), f"{key}_max": float("nan"), f"{key}_max_at": None})
+        report.append(r)
+    return report

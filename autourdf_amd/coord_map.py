@@ -385,11 +385,44 @@ def _parser():
 
 def _cli_parser():
     """The reference's flags plus this project's own: --voxel_size meshes the links and --density (kg/m^3) fills the URDF's
-    inertial blocks from those meshes (each overrides parameters.json's key of the same name)."""
+    inertial blocks from those meshes (each overrides parameters.json's key of the same name); --joint_limits estimates
+    every joint's positions, writes the observed range as its limits and replays the sequences on the URDF, --limit_pad
+    (degrees, default 0) widens that range.  --limit_pad without --joint_limits is a usage error."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
+    parser.add_argument('--joint_limits', action='store_true')
+    parser.add_argument('--limit_pad', type=float, default=None)
+    parse = parser.parse_args
+
+    def parse_args(args=None, namespace=None):
+        ns = parse(args, namespace)
+        if ns.limit_pad is not None and not ns.joint_limits:
+            parser.error("--limit_pad needs --joint_limits")
+        return ns
+    parser.parse_args = parse_args
     return parser
+
+
+def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
+    """Write <name>.joint_motion.json (per-joint and per-link figures) and <name>.joint_positions.npy (J,S,steps) next to
+    the URDF and print one line per joint plus the worst replayed link."""
+    import json
+    stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
+    np.save(stem + '.joint_positions.npy', np.array([m["positions"] for m in motion], np.float64))
+    joints = [{k: v for k, v in m.items() if k != "positions"} for m in motion]
+    with open(stem + '.joint_motion.json', 'w') as f:
+        json.dump({"urdf": urdf_path, "limit_pad_deg": pad_deg, "start_step": start_step, "unit": "rad",
+                   "joints": joints, "links": replay}, f, indent=1,
+                  default=lambda o: o.item() if hasattr(o, "item") else str(o))     # numpy scalars (link ids)
+    for m in motion:
+        print(f"joint_{m['child_link']} ({m['parent_link']} -> {m['child_link']}): {np.degrees(m['lower']):.2f} .. "
+              f"{np.degrees(m['upper']):.2f} deg, tilt_rms {m['tilt_rms']:.3g} rad, slip_rms {m['slip_rms']:.3g}")
+    seen = [r for r in replay if r["n_used"]]
+    if seen:
+        w = max(seen, key=lambda r: r["rot_max"])
+        print(f"replay: worst link {w['link']}: rot_max {w['rot_max']:.3g} rad at {w['rot_max_at']}, "
+              f"pos_max {w['pos_max']:.3g} at {w['pos_max_at']}")
 
 
 def main(argv=None):
@@ -399,13 +432,18 @@ def main(argv=None):
     meshed (``{i:04}.ply`` and ``{i:04}.stl`` in the link directory, the files the URDF names) when the robot's entry has a
     ``voxel_size`` or ``--voxel_size`` is given; the option wins.  With a ``density`` (the key or ``--density``, kg/m^3; the
     option wins) the meshes' mass properties replace the placeholder ``<inertial>`` blocks (``link_inertia``,
-    ``set_inertials``); a density without a voxel size is a ValueError before anything is written."""
+    ``set_inertials``); a density without a voxel size is a ValueError before anything is written.  With ``--joint_limits``
+    (or a ``joint_limits`` key; ``--limit_pad`` / ``limit_pad`` in degrees, the option wins) every joint's positions over
+    all loaded sequences are estimated, the observed range replaces the placeholder limits, the sequences are replayed on
+    the written URDF, and ``<name>.joint_motion.json`` and ``<name>.joint_positions.npy`` are written next to it; a pad
+    without joint limits is a ValueError before anything is written."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import create_urdf, estimate_joint_axes_from_tree, set_inertials
+    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion, replay_urdf, set_inertials,
+                                 set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -416,6 +454,13 @@ def main(argv=None):
     density = args.density if args.density is not None else robot_params.get('density')
     if density is not None and voxel_size is None:
         raise ValueError("a density needs the link meshes: give --voxel_size (or a voxel_size key in parameters.json) with it")
+    joint_limits = bool(args.joint_limits or robot_params.get('joint_limits'))
+    limit_pad = args.limit_pad if args.limit_pad is not None else robot_params.get('limit_pad')
+    if limit_pad is not None and not joint_limits:
+        raise ValueError("a limit_pad needs the joint limits: give --joint_limits (or a joint_limits key in parameters.json) with it")
+    limit_pad = 0.0 if limit_pad is None else float(limit_pad)
+    if not limit_pad >= 0.0:
+        raise ValueError(f"limit_pad must be >= 0 degrees, got {limit_pad}")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -475,6 +520,11 @@ def main(argv=None):
     create_urdf(links, joint_data, cm_list[0], urdf_path, sub_link_path[0])
     if density is not None:
         set_inertials(urdf_path, inertials[0])
+    if joint_limits:
+        motion = estimate_joint_motion(links, joint_data, cm_list, START, END - START)
+        set_joint_limits(urdf_path, motion, float(np.radians(limit_pad)))
+        replay = replay_urdf(urdf_path, links, motion, cm_list, START, END - START)
+        _joint_motion_report(urdf_path, motion, replay, limit_pad, START)
     return urdf_path
 
 

@@ -850,6 +850,109 @@ def link_clouds_prepare(coords: torch.Tensor, matrices: torch.Tensor, link_clust
     return launch, (lm, mm, wf[:n_out], lf[:n_out], oo)
 
 
+# ------------------------------------------------------------------------------ joint motion: positions, limits, replay
+def link_poses(coords: torch.Tensor, link_clusters):
+    """Every link's mean pose at every step in one launch of creg_link_poses_f64: coords (S,T,K,7) f64 [xyz, wxyz],
+    link_clusters one cluster list per link (set order) -> link_T (S,T,L,4,4) f64, the pose creg_joint_axes_f64 works with
+    (mean xyz, eigen-averaged quaternion), unrounded.  ValueError for K > 256, an empty link or a cluster outside [0, K)."""
+    L_ = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    if coords.dim() != 4 or coords.shape[3] != 7 or 0 in coords.shape[:3]:
+        raise ValueError(f"link_poses: coords must be (S,T,K,7) with S, T, K >= 1, got {tuple(coords.shape)}")
+    S, T, K = coords.shape[:3]
+    if K > LINK_SWEEP_MAX_K:
+        raise ValueError(f"link_poses supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+    flat, off = _link_table(link_clusters, K, "link_poses")
+    L = len(off) - 1
+    if L < 1 or S * T * L >= 2 ** 31:
+        raise ValueError(f"link_poses: need 1 <= S*T*L < 2^31 (S={S}, T={T}, L={L})")
+    dev = coords.device
+    cl = torch.tensor(flat, dtype=torch.int32, device=dev)
+    lo = torch.tensor(off, dtype=torch.int32, device=dev)
+    link_T = torch.empty(S, T, L, 4, 4, dtype=torch.float64, device=dev)
+    _lib.check(L_.creg_link_poses_f64(_p(coords), S, T, K, _p(cl), _p(lo), len(flat), L, _p(link_T), _stream()), "creg_link_poses_f64")
+    return link_T
+
+
+def joint_positions(link_T: torch.Tensor, joints, local_axis, local_pos, ref_seq: int = 0, ref_step: int = 0,
+                    start_step: int = 0, num_steps=None):
+    """Every joint's position at every step, its residuals against "one revolute axis through one point" and their
+    per-joint summary (creg_joint_positions_f64).  link_T (S,T,L,4,4) f64 from ``link_poses``; joints (parent link, child
+    link) pairs; local_axis (J,3) and local_pos (J,3 or 4) as ``joint_axes`` returns them (host arrays or f64 device
+    tensors); the steps used are start_step .. start_step + num_steps - 1 (to the end when num_steps is None) and the
+    position is zero at (ref_seq, ref_step).  Returns a dict of device tensors: q, tilt, slip (J,S,num_steps) f64; lower,
+    upper, tilt_rms, tilt_max, slip_rms, slip_max (J) f64; n_used (J) int32; lower_at, upper_at (J,2) int32 = (sequence,
+    step - start_step), -1 where n_used is 0.  IndexError for steps or a reference pose outside link_T, ValueError for
+    shapes and link indices, all before any launch."""
+    L_ = _lib.load()
+    link_T = _need(link_T, torch.float64, "link_T")
+    if link_T.dim() != 5 or tuple(link_T.shape[3:]) != (4, 4) or 0 in link_T.shape[:3]:
+        raise ValueError(f"joint_positions: link_T must be (S,T,L,4,4) with S, T, L >= 1, got {tuple(link_T.shape)}")
+    S, T, L = link_T.shape[:3]
+    dev = link_T.device
+    jt = [(int(p), int(c)) for p, c in joints]
+    J = len(jt)
+    for p, c in jt:
+        if not (0 <= p < L and 0 <= c < L):
+            raise ValueError(f"joint_positions: joint ({p}, {c}) names a link outside [0, {L})")
+    ax = _need(torch.as_tensor(local_axis, dtype=torch.float64, device=dev).reshape(-1, 3), torch.float64, "local_axis")
+    lp = torch.as_tensor(local_pos, dtype=torch.float64, device=dev)
+    if lp.numel() == 0:
+        lp = lp.reshape(0, 4)
+    if ax.shape[0] != J or lp.dim() != 2 or lp.shape[0] != J or (J and lp.shape[1] not in (3, 4)):
+        raise ValueError(f"joint_positions: local_axis must be ({J},3) and local_pos ({J},3) or ({J},4), got "
+                         f"{tuple(ax.shape)} and {tuple(lp.shape)}")
+    if J and lp.shape[1] == 3:
+        lp = torch.cat([lp, torch.ones(J, 1, dtype=torch.float64, device=dev)], dim=1)
+    lp = lp.contiguous()
+    start_step, ref_seq, ref_step = int(start_step), int(ref_seq), int(ref_step)
+    num_steps = T - start_step if num_steps is None else int(num_steps)
+    if start_step < 0 or num_steps < 1:
+        raise ValueError(f"joint_positions: need start_step >= 0 and num_steps >= 1 (got {start_step}, {num_steps})")
+    if start_step + num_steps > T:
+        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 1 with size {T}")
+    if not 0 <= ref_seq < S:
+        raise IndexError(f"index {ref_seq} is out of bounds for axis 0 with size {S}")
+    if not 0 <= ref_step < T:
+        raise IndexError(f"index {ref_step} is out of bounds for axis 1 with size {T}")
+    if S > 65535 or S * num_steps >= 2 ** 31:
+        raise ValueError(f"joint_positions: at most 65535 sequences and 2^31 samples per joint (S={S}, num_steps={num_steps})")
+    f64 = dict(dtype=torch.float64, device=dev)
+    q, tilt, slip = (torch.empty(J, S, num_steps, **f64) for _ in range(3))
+    summary = torch.empty(J, 6, **f64)
+    where = torch.empty(J, 5, dtype=torch.int32, device=dev)
+    if J:
+        jn = torch.tensor(jt, dtype=torch.int32, device=dev).reshape(-1, 2)
+        _lib.check(L_.creg_joint_positions_f64(_p(link_T), S, T, L, _p(jn), J, _p(ax), _p(lp), ref_seq, ref_step, start_step,
+                                               num_steps, _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()),
+                   "creg_joint_positions_f64")
+    out = {"q": q, "tilt": tilt, "slip": slip}
+    for i, k in enumerate(("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")):
+        out[k] = summary[:, i]
+    out.update(n_used=where[:, 0], lower_at=where[:, 1:3], upper_at=where[:, 3:5])
+    return out
+
+
+def motion_error(A, A0, B, B0, point):
+    """How differently every link moved from its reference pose under two descriptions (creg_motion_error_f64): A, B (P,L,4,4),
+    A0, B0 (L,4,4), point (L,3), f64 device tensors -> (rot_err (P,L) rad, pos_err (P,L)): the angle between A A0^-1 and
+    B B0^-1 and the distance between the images of point[l] under the two.  ValueError for shapes before any launch."""
+    L_ = _lib.load()
+    A, A0, B, B0, point = (_need(t, torch.float64, n) for t, n in ((A, "A"), (A0, "A0"), (B, "B"), (B0, "B0"), (point, "point")))
+    if A.dim() != 4 or tuple(A.shape[2:]) != (4, 4) or A.shape != B.shape or 0 in A.shape[:2] \
+            or tuple(A0.shape) != tuple(A.shape[1:]) or A0.shape != B0.shape or tuple(point.shape) != (A.shape[1], 3):
+        raise ValueError(f"motion_error: A, B (P,L,4,4), A0, B0 (L,4,4) and point (L,3) with P, L >= 1 expected, got "
+                         f"{tuple(A.shape)}, {tuple(A0.shape)}, {tuple(B.shape)}, {tuple(B0.shape)}, {tuple(point.shape)}")
+    P, L = A.shape[:2]
+    if P * L >= 2 ** 31:
+        raise ValueError(f"motion_error: P*L must stay below 2^31 (P={P}, L={L})")
+    rot = torch.empty(P, L, dtype=torch.float64, device=A.device)
+    pos = torch.empty(P, L, dtype=torch.float64, device=A.device)
+    _lib.check(L_.creg_motion_error_f64(_p(A), _p(A0), _p(B), _p(B0), _p(point), P, L, _p(rot), _p(pos), _stream()),
+               "creg_motion_error_f64")
+    return rot, pos
+
+
 # ------------------------------------------------------------------------------ N4 link meshing
 MESH_MAX_NEIGHBORS = 32
 

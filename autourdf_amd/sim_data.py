@@ -284,9 +284,10 @@ def _axis_angle(axis, q):
 class UrdfRobot:
     """Kinematic tree + visual triangles of a URDF.  ``links`` in file order; ``joints`` in file order (PyBullet
     numbers joints the same way); ``tri`` (F,3,3) in link frames, ``tri_link`` (F,), ``cum_area`` (F,), ``tri_start`` (L+1,)
-    int64: link l owns rows tri_start[l]:tri_start[l+1] of ``tri``."""
+    int64: link l owns rows tri_start[l]:tri_start[l+1] of ``tri``.  ``load_meshes=False`` keeps the kinematic tree only: no
+    mesh file is resolved or read, ``tri``, ``tri_link`` and ``cum_area`` are empty and ``tri_start`` is all zero."""
 
-    def __init__(self, urdf_path, global_scale=1.0, package_dirs=()):
+    def __init__(self, urdf_path, global_scale=1.0, package_dirs=(), load_meshes=True):
         self.path = os.path.abspath(urdf_path)
         root = ET.parse(self.path).getroot()
         self.links = [l.get("name") for l in root.findall("link")]
@@ -307,6 +308,10 @@ class UrdfRobot:
         if len(roots) != 1:
             raise ValueError(f"{urdf_path}: expected one root link, found {roots}")
         self.root = roots[0]
+        if not load_meshes:
+            self.tri, self.tri_link, self.cum_area = np.zeros((0, 3, 3)), np.zeros(0, np.int32), np.zeros(0)
+            self.tri_start = np.zeros(len(self.links) + 1, np.int64)
+            return
         tris, owner = [], []
         for l in root.findall("link"):
             for vis in l.findall("visual"):

@@ -344,6 +344,59 @@ int creg_link_clouds_f64(const double* coords, const double* matrices, int32_t T
                          double* clouds_lf, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Joint motion: where every joint stood at every step, how well one revolute axis explains it, and how a replayed
+ * URDF compares with the registration (this project's own; the reference writes a placeholder limit).  fp64, no
+ * floating-point atomics: two runs give the same bits, and a joint gives the same bits alone and among others.
+ * R[r][c] below is a rotation's row r, column c; a "rigid inverse" of [R t] is [R^T, -R^T t] with R taken as orthonormal.
+ * For a rotation matrix R:  v(R) = ((R21 - R12)/2, (R02 - R20)/2, (R10 - R01)/2),  c(R) = (((R00 + R11) + R22) - 1)/2,
+ * so that v = sin(angle) axis and c = cos(angle).
+ *
+ * creg_link_poses_f64: one thread per (s, t, l).  coords (S,T,K,7) fp64 = [xyz, wxyz]; links as for creg_joint_axes_f64
+ *   (link_clusters / link_offsets, L links).  link_T (S,T,L,4,4) fp64, row-major: exactly the mean pose
+ *   creg_joint_axes_f64 computes for the link at that step -- the mean xyz summed in list order and divided by the list's
+ *   length, the top eigenvector (cyclic Jacobi) of (1/n) sum q q^T summed in list order, its quaternion_to_matrix --
+ *   written as [R t; 0 0 0 1] without rounding to float32.  A cluster index outside [0, K) is skipped (the host rejects
+ *   it first).  K <= 256, S*T*L < 2^31.
+ *
+ * creg_joint_positions_f64: link_T (S,T,L,4,4) as above.  joints (J,2) int32 = (parent link, child link).  local_axis
+ *   (J,3) and local_pos (J,4) as creg_joint_axes_f64 returns them: in the child's frame, the axis taken as a unit vector,
+ *   only local_pos[0..2] read.  Steps used: t = start_step + i, i in [0, num_steps); start_step + num_steps <= T,
+ *   0 <= ref_seq < S, 0 <= ref_step < T (the host raises IndexError first); S <= 65535.
+ *   Per joint: X(s,t) = P^-1 C (rigid inverse of the parent's link_T times the child's), X0 = X(ref_seq, ref_step),
+ *   D = X0^-1 X(s,t) (rigid inverse again) = [R d].  For a revolute joint D is the rotation by the joint position about
+ *   a = local_axis through p = local_pos.
+ *   Per sample (J,S,num_steps):
+ *     w    = atan2((v0 a0 + v1 a1) + v2 a2, c) with v = v(R), c = c(R): the wrapped position in (-pi, pi].
+ *     q    = the position unwrapped per sequence along i: u(0) = w(0);  u(i) = u(i-1) + (d - 2pi * rint(d / 2pi)) with
+ *            d = w(i) - w(i-1), 2pi the double 6.283185307179586, rint rounding half to even.  One thread runs the
+ *            recurrence in this order.  A non-finite w(i) therefore makes u non-finite from step i to the end of ITS sequence.
+ *     tilt = atan2(|v(E)|, c(E)) >= 0 for E = Rot(a, -w) R, Rot(a, x) = I + sin x [a]x + (1 - cos x) [a]x [a]x: the angle of
+ *            the rotation left once the turn about the axis is taken out.
+ *     slip = |(R p + d) - p|: a point of the axis stays put under a revolute joint.
+ *   Per joint: summary (J,6) = lower = min u, upper = max u, tilt_rms = sqrt(sum tilt^2 / n_used), tilt_max, slip_rms,
+ *   slip_max; where (J,5) int32 = n_used, (s, i) of the minimum, (s, i) of the maximum; ties go to the first sample in
+ *   (s, i) order.  A sample whose u, tilt or slip is not finite is left out of the summary and of n_used; its per-sample
+ *   outputs stay as computed.  The two sums of squares run over 256 threads, thread k taking samples k, k + 256, ... of the
+ *   (s, i) order, then the wave's xor butterfly (offsets 32 .. 1), then the four waves in order: an order (S, num_steps)
+ *   alone decides.  n_used = 0 (a NaN axis, a non-finite reference pose): the six figures are NaN and the four indices -1.
+ *   A joint whose link index is outside [0, L) is skipped: nothing of it is read or written.  J = 0 launches nothing.
+ *   Two launches (samples over (joint, sequence) workgroups, then one workgroup per joint), both latency-bound.
+ *
+ * creg_motion_error_f64: one thread per (pose, link).  A, B (P,L,4,4), A0, B0 (L,4,4), point (L,3), fp64.
+ *   Ma = A A0^-1 and Mb = B B0^-1 (rigid inverses: R = R_X R_X0^T, t = t_X - R t_X0).  rot_err (P,L) = atan2(|v(Rr)|, c(Rr))
+ *   for Rr = R_Ma^T R_Mb; pos_err (P,L) = |Ma x - Mb x| for x = point[l].  The error is free of frames: it compares how a
+ *   link moved from its reference pose under two descriptions, whatever frame each one attaches to the link.  P*L < 2^31. */
+int creg_link_poses_f64(const double* coords, int32_t S, int32_t T, int32_t K, const int32_t* link_clusters,
+                        const int32_t* link_offsets, int32_t n_link_clusters, int32_t L, double* link_T,
+                        creg_stream_t stream);
+int creg_joint_positions_f64(const double* link_T, int32_t S, int32_t T, int32_t L, const int32_t* joints, int32_t J,
+                             const double* local_axis, const double* local_pos, int32_t ref_seq, int32_t ref_step,
+                             int32_t start_step, int32_t num_steps, double* q, double* tilt, double* slip,
+                             double* summary, int32_t* where, creg_stream_t stream);
+int creg_motion_error_f64(const double* A, const double* A0, const double* B, const double* B0, const double* point,
+                          int32_t P, int32_t L, double* rot_err, double* pos_err, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Link meshing (PointCloud/link.py:204-314, link_mesh; DESIGN N4).  The contract is this project's own, NOT pinned to
  * Open3D / PyMCubes / pymeshfix.  Every call takes all L links of one directory: points (n,3) fp64 concatenated with
  * offsets (L+1) int64, per-link outputs concatenated the same way.
