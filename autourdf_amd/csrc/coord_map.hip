@@ -11,6 +11,9 @@
 //   diff = 0 (:283-301), per step i < T:
 //     map[j][k][i] = |t_j - t_k| / (2 bbox) + acos(clamp((tr(R_j^T R_k) - 1) / 2)) / pi
 //   sum_map[j][k] = sum_i |map[j][k][i]|                                                   (:304-305)
+// Non-finite poses propagate as they do in the reference (torch.clamp keeps a NaN): a NaN in R_k gives NaN in row and
+// column k of that step's map (diff = 0), or in the whole map of the two steps that use the pose (diff = 1: every entry
+// sums over all tracks), and in sum_map wherever a step is NaN.  No NaN is ever clamped to a finite angle.
 //
 // One workgroup per step; the two K x K pair matrices live in LDS (K <= 64) or in the workspace.
 // O(T K^3) flops on a few KB: latency-bound by construction, a handful of microseconds per call.
@@ -109,7 +112,8 @@ __global__ __launch_bounds__(CM_NT) void k_coord_dist_map(const double* __restri
             double tr = 0;                                // trace(R_j^T R_k)
 #pragma unroll
             for (int c = 0; c < 3; ++c) tr += (sR[9 * j + c] * sR[9 * k + c] + sR[9 * j + 3 + c] * sR[9 * k + 3 + c]) + sR[9 * j + 6 + c] * sR[9 * k + 6 + c];
-            const double cs = fmin(fmax(0.5 * (tr - 1.0), -1.0), 1.0);
+            const double hc = 0.5 * (tr - 1.0);
+            const double cs = hc != hc ? hc : fmin(fmax(hc, -1.0), 1.0);   // fmax(NaN, -1) is -1: keep the NaN, as torch.clamp does
             drpy = lam_rot * acos(cs);
             d_map[(size_t)p * Tn + i] = dxyz + drpy;
         }

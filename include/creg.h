@@ -252,6 +252,8 @@ int creg_icp_nn_counters(double* out8, int32_t reset, int32_t timing);
  * M (T,K,4,4) fp64 poses.  diff != 0: T-1 maps built from step-to-step motion differences and the
  * row-distance step (:250-281); diff == 0: T maps of pose distances (:283-301).
  * d_map (K,K,T') fp64 laid out like np.stack(..., axis=2); sum_map (K,K) = sum_t |d_map| (:304-305).
+ * A NaN in a rotation block stays NaN (the clamp in front of acos keeps it, like torch.clamp): row and column k
+ * of that step for diff == 0, the two steps that use the pose for diff != 0, and sum_map wherever a step is NaN.
  * bounding_box = CoordMap.bounding_box (diagonal of the raw clouds' AABB, :153-173).
  * coords (n,7) = [x, y, z, qw, qx, qy, qz] with pytorch3d's matrix_to_quaternion in fp64. */
 size_t creg_coord_dist_map_workspace_bytes(int32_t T, int32_t K);

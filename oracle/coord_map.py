@@ -14,6 +14,9 @@ Restates, in numpy fp64:
   ``(trace(R1^T R2) - 1) / 2``).  The wheel is absent from this image and from /root/reference
   -- parity UNPINNED for this third-party arithmetic; cross-checked against
   ``scipy.spatial.transform.Rotation`` (tests/test_oracle_golden.py).
+
+tests/_coord_map_ref.py states the same contract in numpy.longdouble, from the input matrices up and without this
+module; tests/test_coord_map_cpu.py measures this oracle against it (and it against 50-digit mpmath).
 """
 import math
 
