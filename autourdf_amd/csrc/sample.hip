@@ -93,10 +93,12 @@ __global__ __launch_bounds__(256) void k_raster_depth(const double* __restrict__
     if (area == 0.0) return;
     const double xmin = fmin(X[0], fmin(X[1], X[2])), xmax = fmax(X[0], fmax(X[1], X[2]));
     const double ymin = fmin(Y[0], fmin(Y[1], Y[2])), ymax = fmax(Y[0], fmax(Y[1], Y[2]));
-    // pixel bounds clamped BEFORE the integer conversion (a huge projected coordinate would overflow the cast)
+    // off screen / NaN FIRST: past this line xmin - 0.5 <= W and xmax >= -1 (and the same in y), so with the clamps below every
+    // value converted to int lies in [-1, W] / [-1, H] however large the projected coordinates are (the conversion of a double
+    // outside the range of int is undefined)
+    if (!(xmin - 0.5 <= (double)c.W) || !(ymin - 0.5 <= (double)c.H) || !(xmax >= -1.0) || !(ymax >= -1.0)) return;
     const int x0 = (int)fmax(0.0, floor(xmin - 0.5)), x1 = (int)fmin((double)(c.W - 1), ceil(xmax - 0.5));
     const int y0 = (int)fmax(0.0, floor(ymin - 0.5)), y1 = (int)fmin((double)(c.H - 1), ceil(ymax - 0.5));
-    if (!(xmin - 0.5 <= (double)c.W) || !(ymin - 0.5 <= (double)c.H) || !(xmax >= -1.0) || !(ymax >= -1.0)) return;   // off screen / NaN
     const double ia = 1.0 / area, i0 = 1.0 / D[0], i1 = 1.0 / D[1], i2 = 1.0 / D[2];
     unsigned long long* z = zbuf + (size_t)cam_id * c.W * c.H;
     for (int y = y0; y <= y1; ++y)
@@ -123,8 +125,9 @@ __global__ __launch_bounds__(256) void k_visible(const double* __restrict__ pts,
         cam_project(cams + 12 * k, p, xc, yc, d);
         if (!(d >= c.near_v && d <= c.far_v)) continue;
         cam_pixel(c, xc, yc, d, px, py);
-        const int x = (int)floor(px), y = (int)floor(py);
-        if (x < 0 || x >= c.W || y < 0 || y >= c.H) continue;
+        const double fx = floor(px), fy = floor(py);                   // tested as doubles: a huge px would overflow the conversion
+        if (!(fx >= 0.0 && fx < (double)c.W && fy >= 0.0 && fy < (double)c.H)) continue;
+        const int x = (int)fx, y = (int)fy;
         const double zb = __longlong_as_double((long long)zbuf[((size_t)k * c.H + y) * c.W + x]);
         if (d <= zb + eps) seen = 1;
     }

@@ -341,6 +341,26 @@ def icp_p2p(src, src_offsets, tgt, tgt_offsets, init, th: float = 1.0, max_itera
 
 
 # ------------------------------------------------------------------------------ N4 mesh surface sampling
+def _mesh_shapes(who, tri, tri_link, link_T, cum_area=None, cams=None, rows=None, rows_name="", width=1, height=1):
+    """The kernels index these arrays by the sizes of OTHER arrays (tri_link[f] for f < F, cams + 12 c, rows + 3 i): a shape that
+    disagrees is read out of bounds, so it is refused here, before any launch."""
+    F = tri.shape[0]
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or F < 1:
+        raise ValueError(f"{who}: tri (F,3,3) with F >= 1 expected, got {tuple(tri.shape)}")
+    if tuple(tri_link.shape) != (F,):
+        raise ValueError(f"{who}: tri_link ({F}) expected, got {tuple(tri_link.shape)}")
+    if cum_area is not None and tuple(cum_area.shape) != (F,):
+        raise ValueError(f"{who}: cum_area ({F}) expected, got {tuple(cum_area.shape)}")
+    if link_T.dim() != 3 or tuple(link_T.shape[1:]) != (4, 4) or link_T.shape[0] < 1:
+        raise ValueError(f"{who}: link_T (L,4,4) with L >= 1 expected, got {tuple(link_T.shape)}")
+    if cams is not None and (cams.dim() != 2 or cams.shape[1] != 12 or cams.shape[0] < 1):
+        raise ValueError(f"{who}: cams (C,12) with C >= 1 expected, got {tuple(cams.shape)}")
+    if rows is not None and (rows.dim() != 2 or rows.shape[1] != 3 or rows.shape[0] < 1):
+        raise ValueError(f"{who}: {rows_name} (n,3) with n >= 1 expected, got {tuple(rows.shape)}")
+    if int(width) < 1 or int(height) < 1:
+        raise ValueError(f"{who}: width and height >= 1 expected, got {width} x {height}")
+
+
 def sample_mesh(tri, cum_area, tri_link, link_T, u, with_links: bool = False):
     """Area-weighted points on an articulated triangle mesh (creg_sample_mesh_f64): tri (F,3,3) f64 in link
     frames, cum_area (F) f64, tri_link (F) i32, link_T (L,4,4) f64, u (n,3) f64 uniforms -> (n,3) f64 world points
@@ -348,9 +368,8 @@ def sample_mesh(tri, cum_area, tri_link, link_T, u, with_links: bool = False):
     L = _lib.load()
     tri, cum_area, link_T, u = (_need(t, torch.float64, nm) for t, nm in ((tri, "tri"), (cum_area, "cum_area"), (link_T, "link_T"), (u, "u")))
     tri_link = _need(tri_link, torch.int32, "tri_link")
+    _mesh_shapes("sample_mesh", tri, tri_link, link_T, cum_area=cum_area, rows=u, rows_name="u")
     n, F = u.shape[0], tri.shape[0]
-    if cum_area.shape[0] != F or tri_link.shape[0] != F:
-        raise ValueError("sample_mesh: tri / cum_area / tri_link disagree on the number of triangles")
     out = torch.empty(n, 3, dtype=torch.float64, device=u.device)
     links = torch.empty(n, dtype=torch.int32, device=u.device) if with_links else None
     _lib.check(L.creg_sample_mesh_f64(_p(tri), _p(cum_area), _p(tri_link), F, _p(link_T), link_T.shape[0], _p(u), n, _p(out),
@@ -366,8 +385,9 @@ def visibility(tri, tri_link, link_T, cams, pts, fov_deg=60.0, aspect=1.0, near=
     L = _lib.load()
     tri, link_T, cams, pts = (_need(t, torch.float64, nm) for t, nm in ((tri, "tri"), (link_T, "link_T"), (cams, "cams"), (pts, "pts")))
     tri_link = _need(tri_link, torch.int32, "tri_link")
+    _mesh_shapes("visibility", tri, tri_link, link_T, cams=cams, rows=pts, rows_name="pts", width=width, height=height)
     C, n = cams.shape[0], pts.shape[0]
-    ws_bytes = L.creg_visibility_workspace_bytes(C, width, height)
+    ws_bytes = L.creg_visibility_workspace_bytes(C, int(width), int(height))
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=pts.device)
     vis = torch.empty(n, dtype=torch.uint8, device=pts.device)
     _lib.check(L.creg_visibility_f64(_p(tri), _p(tri_link), tri.shape[0], _p(link_T), link_T.shape[0], _p(cams), C, float(fov_deg),
@@ -381,8 +401,7 @@ def raster_depth(tri, tri_link, link_T, cams, fov_deg=60.0, aspect=1.0, near=0.1
     L = _lib.load()
     tri, link_T, cams = (_need(t, torch.float64, nm) for t, nm in ((tri, "tri"), (link_T, "link_T"), (cams, "cams")))
     tri_link = _need(tri_link, torch.int32, "tri_link")
-    if tri.shape[0] != tri_link.shape[0] or cams.dim() != 2 or cams.shape[1] != 12:
-        raise ValueError("raster_depth: tri (F,3,3) / tri_link (F) / cams (C,12) expected")
+    _mesh_shapes("raster_depth", tri, tri_link, link_T, cams=cams, width=width, height=height)
     C = cams.shape[0]
     depth = torch.empty(C, int(height), int(width), dtype=torch.float64, device=tri.device)
     _lib.check(L.creg_raster_depth_f64(_p(tri), _p(tri_link), tri.shape[0], _p(link_T), link_T.shape[0], _p(cams), C, float(fov_deg),

@@ -18,11 +18,12 @@ def sample_mesh(tri, cum_area, tri_link, link_T, u):
     b0, b1, b2 = 1.0 - s, s * (1.0 - u[:, 2]), s * u[:, 2]
     t = tri[f]
     p = (b0[:, None] * t[:, 0] + b1[:, None] * t[:, 1]) + b2[:, None] * t[:, 2]
-    T = link_T[np.asarray(tri_link)[f]]
+    link = np.clip(np.asarray(tri_link)[f], 0, len(link_T) - 1)      # the kernel clamps a link index outside [0, L)
+    T = link_T[link]
     out = np.empty_like(p)
     for d in range(3):
         out[:, d] = ((T[:, d, 0] * p[:, 0] + T[:, d, 1] * p[:, 1]) + T[:, d, 2] * p[:, 2]) + T[:, d, 3]
-    return out, np.asarray(tri_link)[f]
+    return out, link
 
 
 def fk(links, joints, q, root, base=None):
@@ -82,7 +83,7 @@ def visibility(tri, tri_link, link_T, cams, pts, fov_deg=60.0, aspect=1.0, near=
     """numpy restatement of creg_visibility_f64 (same operation order): returns (visible (n) bool, depth (C,H,W))."""
     tri, link_T, cams, pts = (np.asarray(a, np.float64) for a in (tri, link_T, cams, pts))
     tan_half = np.tan(fov_deg * 3.14159265358979323846 / 360.0)
-    T = link_T[np.asarray(tri_link)]
+    T = link_T[np.clip(np.asarray(tri_link), 0, len(link_T) - 1)]    # clamped as in k_raster_depth
     world = np.empty_like(tri)
     for a in range(3):
         world[:, :, a] = ((T[:, None, a, 0] * tri[:, :, 0] + T[:, None, a, 1] * tri[:, :, 1]) + T[:, None, a, 2] * tri[:, :, 2]) + T[:, None, a, 3]
@@ -96,6 +97,8 @@ def visibility(tri, tri_link, link_T, cams, pts, fov_deg=60.0, aspect=1.0, near=
             area = (x[1] - x[0]) * (y[2] - y[0]) - (x[2] - x[0]) * (y[1] - y[0])
             if area == 0.0:
                 continue
+            if not (x.min() - 0.5 <= width) or not (y.min() - 0.5 <= height) or not (x.max() >= -1.0) or not (y.max() >= -1.0):
+                continue                                             # off screen / NaN: before any integer conversion, as the kernel
             x0, x1 = max(0, int(np.floor(x.min() - 0.5))), min(width - 1, int(np.ceil(x.max() - 0.5)))
             y0, y1 = max(0, int(np.floor(y.min() - 0.5))), min(height - 1, int(np.ceil(y.max() - 0.5)))
             if x1 < x0 or y1 < y0:
