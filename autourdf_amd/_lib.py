@@ -118,6 +118,9 @@ SIGNATURES = {
     "creg_mc_emit_i32": (ctypes.c_int, [vp, vp, i32, i64, vp, i64, i64, vp, vp, vp, sz, vp]),
     "creg_mesh_finish_workspace_bytes": (sz, [i64]),
     "creg_mesh_finish_f64": (ctypes.c_int, [vp, i64, vp, i64, vp, vp, i32, vp, f64, i32, vp, vp, vp, sz, vp]),
+    "creg_lattice_hull_workspace_bytes": (sz, [i64, i32]),
+    "creg_lattice_hull_i32": (ctypes.c_int, [vp, i64, vp, vp, i32, i64, vp, vp, vp, sz, vp]),
+    "creg_lattice_hull_emit_i32": (ctypes.c_int, [vp, i64, vp, i32, vp, i64, vp, f64, vp, vp, vp, sz, vp]),
     "creg_train_workspace_bytes": (sz, [ctypes.POINTER(TrainShape)]),
     "creg_train_plan_create": (ctypes.c_int, [ctypes.POINTER(TrainShape), vp, sz, ctypes.POINTER(vp)]),
     "creg_train_plan_run": (ctypes.c_int, [vp, ctypes.POINTER(TrainArgs), vp]),

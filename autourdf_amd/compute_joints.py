@@ -244,6 +244,22 @@ def set_inertials(urdf_file, inertials):
     tree.write(urdf_file, encoding="utf-8", xml_declaration=True)
 
 
+def set_collision_meshes(urdf_file, suffix="_hull"):
+    """Point every link's <collision><geometry><mesh> at the file ``link.link_mesh(..., hull=True)`` wrote (this project's own):
+    the ``filename`` X.stl becomes X<suffix>.stl.  Nothing else changes: every other element and attribute, the indentation
+    and the XML declaration stay as ``create_urdf`` wrote them.  Every link must hold the block ``create_urdf`` writes -- a
+    <collision> with a <geometry><mesh> whose filename ends in .stl -- ValueError naming the link otherwise, and nothing is
+    written in that case."""
+    tree = ET.parse(urdf_file)
+    for link in tree.getroot().findall("link"):
+        mesh = link.find("collision/geometry/mesh")
+        name = mesh.get("filename") if mesh is not None else None
+        if name is None or not name.endswith(".stl"):
+            raise ValueError(f"{urdf_file}: link {link.get('name')} has no <collision><geometry><mesh> with an .stl filename to rewrite")
+        mesh.set("filename", name[:-len(".stl")] + suffix + ".stl")
+    tree.write(urdf_file, encoding="utf-8", xml_declaration=True)
+
+
 def estimate_joint_motion(links, joint_data, cm_list, start_step=0, num_steps=500, time_step=0):
     """Where every joint of ``joint_data`` stood at every step of every sequence, and how well "one revolute axis through one
     point" explains the two links' relative motion (this project's own; ``ops.link_poses`` and ``ops.joint_positions``, three

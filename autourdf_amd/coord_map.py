@@ -387,12 +387,14 @@ def _cli_parser():
     """The reference's flags plus this project's own: --voxel_size meshes the links and --density (kg/m^3) fills the URDF's
     inertial blocks from those meshes (each overrides parameters.json's key of the same name); --joint_limits estimates
     every joint's positions, writes the observed range as its limits and replays the sequences on the URDF, --limit_pad
-    (degrees, default 0) widens that range.  --limit_pad without --joint_limits is a usage error."""
+    (degrees, default 0) widens that range.  --limit_pad without --joint_limits is a usage error.  --collision_hull writes
+    every link's convex hull next to its mesh and names it in the URDF's <collision> blocks."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
     parser.add_argument('--joint_limits', action='store_true')
     parser.add_argument('--limit_pad', type=float, default=None)
+    parser.add_argument('--collision_hull', action='store_true')
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -436,14 +438,18 @@ def main(argv=None):
     (or a ``joint_limits`` key; ``--limit_pad`` / ``limit_pad`` in degrees, the option wins) every joint's positions over
     all loaded sequences are estimated, the observed range replaces the placeholder limits, the sequences are replayed on
     the written URDF, and ``<name>.joint_motion.json`` and ``<name>.joint_positions.npy`` are written next to it; a pad
-    without joint limits is a ValueError before anything is written."""
+    without joint limits is a ValueError before anything is written.  With ``--collision_hull`` (or a boolean
+    ``collision_hull`` key; the option wins) every link's exact convex hull is written as ``{i:04}_hull.stl`` and the URDF's
+    ``<collision>`` blocks name it (``link_mesh(..., hull=True)``, ``set_collision_meshes``), one line per link is printed --
+    triangles of the visual mesh -> triangles of the hull -- and the inertials stay computed from the visual meshes; without a
+    voxel size it is a ValueError before anything is written."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion, replay_urdf, set_inertials,
-                                 set_joint_limits)
+    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion, replay_urdf,
+                                 set_collision_meshes, set_inertials, set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -454,6 +460,10 @@ def main(argv=None):
     density = args.density if args.density is not None else robot_params.get('density')
     if density is not None and voxel_size is None:
         raise ValueError("a density needs the link meshes: give --voxel_size (or a voxel_size key in parameters.json) with it")
+    collision_hull = bool(args.collision_hull or robot_params.get('collision_hull'))
+    if collision_hull and voxel_size is None:
+        raise ValueError("collision hulls need the link meshes: give --voxel_size (or a voxel_size key in parameters.json) with "
+                         "--collision_hull")
     joint_limits = bool(args.joint_limits or robot_params.get('joint_limits'))
     limit_pad = args.limit_pad if args.limit_pad is not None else robot_params.get('limit_pad')
     if limit_pad is not None and not joint_limits:
@@ -512,7 +522,11 @@ def main(argv=None):
               "visualize_kinematic_tree and visualize_urdf")
     else:
         visualize_links(sub_link_path, START, END, dof, False)
-        link_mesh(sub_link_path, dof, voxel_size, False)
+        if collision_hull:
+            for i, (nv, nh) in enumerate(link_mesh(sub_link_path, dof, voxel_size, False, hull=True)[0]):
+                print(f"link_{i}: {nv} triangles -> hull of {nh} triangles")
+        else:
+            link_mesh(sub_link_path, dof, voxel_size, False)
         inertials = link_inertia(sub_link_path, dof, density) if density is not None else None
         print("skipped (out of scope): the cluster / link viewers and plots, visualize_kinematic_tree and visualize_urdf")
     os.makedirs(f'data/urdf/{ROBOT}_{NUM_SEG}_seg/', exist_ok=True)
@@ -520,6 +534,8 @@ def main(argv=None):
     create_urdf(links, joint_data, cm_list[0], urdf_path, sub_link_path[0])
     if density is not None:
         set_inertials(urdf_path, inertials[0])
+    if collision_hull:
+        set_collision_meshes(urdf_path)
     if joint_limits:
         motion = estimate_joint_motion(links, joint_data, cm_list, START, END - START)
         set_joint_limits(urdf_path, motion, float(np.radians(limit_pad)))

@@ -129,13 +129,19 @@ def visualize_links(path_list, start_steps, end_steps, dof, vis_flow):
             write_ply(link_dir + f'{i:04}_og.ply', np.concatenate([np.asarray(f[i], np.float64).reshape(-1, 3) for f in c]))
 
 
-def link_mesh(path_list, dof, vsize, vis_flow):
+def link_mesh(path_list, dof, vsize, vis_flow, hull=False):
     """link.py:204-314 (same signature): {i:04}.ply -> outlier removal, voxel grid of size vsize, marching cubes, one
-    smoothing pass -> binary {i:04}.stl, all dof + 1 links of a directory through one set of launches."""
+    smoothing pass -> binary {i:04}.stl, all dof + 1 links of a directory through one set of launches.
+
+    hull=True (this project's own; DESIGN N4) also writes {i:04}_hull.stl, the exact convex hull of the link's unsmoothed
+    marching-cubes vertices -- it contains the smoothed mesh, whose vertices are averages of those -- through one
+    ``ops.lattice_hull`` call per directory on the same ``ops.voxel_mesh`` result, and returns, per directory, the list of
+    (triangles of the mesh, triangles of the hull) per link.  ValueError naming the link if one has no hull."""
     from .cluster_icp import read_point_cloud
     if vis_flow:
         raise NotImplementedError("link_mesh: there is no viewer here; call it with vis_flow=False")
     dev = _lib.device()
+    counts = []
     for link_dir in path_list:
         clouds = [np.asarray(read_point_cloud(link_dir + f'{i:04}.ply').points, np.float64).reshape(-1, 3)
                   for i in range(dof + 1)]
@@ -145,6 +151,13 @@ def link_mesh(path_list, dof, vsize, vis_flow):
         meshes = ops.voxel_mesh(pts, off, vsize, smooth=True, keep=keep)
         for i, m in enumerate(meshes):
             write_stl(link_dir + f'{i:04}.stl', m["stl_records"].cpu().numpy())
+        if hull:
+            voff = np.concatenate([[0], np.cumsum([len(m["verts_h"]) for m in meshes])]).astype(np.int64)
+            hulls = ops.lattice_hull(torch.cat([m["verts_h"] for m in meshes]), voff, np.stack([m["origin"] for m in meshes]), vsize)
+            for i, h in enumerate(hulls):
+                write_stl(link_dir + f'{i:04}_hull.stl', h["stl_records"].cpu().numpy())
+            counts.append([(len(m["triangles"]), len(h["triangles"])) for m, h in zip(meshes, hulls)])
+    return counts if hull else None
 
 
 def link_inertia(path_list, dof, density, closure_tol=1e-9):

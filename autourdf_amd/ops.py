@@ -1081,6 +1081,74 @@ def voxel_mesh(points: torch.Tensor, offsets: torch.Tensor, voxel_size: float, s
                  origin=origin_h[l], dims=dims_h[l]) for l in range(L)]
 
 
+HULL_MAX_COORD = 16383
+HULL_STATUS = {0: "ok", 1: "fewer than 4 points", 2: "all points identical", 3: "all points collinear", 4: "all points coplanar",
+               5: f"a coordinate beyond {HULL_MAX_COORD}", 6: "offsets are no range of the points", 7: "face slots exhausted",
+               8: "round bound exhausted", 9: "a horizon that is no closed cycle"}
+
+
+def lattice_hull(verts_h: torch.Tensor, offsets, origin=None, voxel_size=None, strict: bool = True):
+    """Exact convex hull of every link's lattice points in one launch (creg_lattice_hull_i32 / _emit_i32; DESIGN N4).
+    verts_h (n,3) int32 concatenated (``voxel_mesh``'s verts_h: half-voxel units, |v| <= 16383), offsets (L+1) int64 (tensor
+    or array).  With origin (L,3) f64 and voxel_size the emitting launch also writes STL records of
+    origin + (voxel_size / 2) * v.  Returns one dict per link: triangles (F,3) int32 (indices local to the link, outward),
+    vertex_ids (sorted unique int64), status (int, 0 = a certified hull; ``HULL_STATUS`` names the others) and stl_records
+    (F,4,3) f32 when asked.  A link of non-zero status has no triangles; strict=True raises ValueError naming the first such
+    link instead.  A coordinate beyond the limit or offsets that do not run from 0 to n without decreasing raise ValueError
+    before anything is launched.  The host waits once, for the face counts."""
+    L_ = _lib.load()
+    verts_h = _need(verts_h, torch.int32, "verts_h")
+    if verts_h.dim() != 2 or verts_h.shape[1] != 3:
+        raise ValueError("lattice_hull: verts_h must be (n,3)")
+    off_h = np.ascontiguousarray(offsets.cpu().numpy() if isinstance(offsets, torch.Tensor) else offsets, np.int64).reshape(-1)
+    n, L = verts_h.shape[0], len(off_h) - 1
+    if L < 1 or off_h[0] != 0 or np.any(np.diff(off_h) < 0) or off_h[-1] != n:
+        raise ValueError("lattice_hull: offsets must be (L+1), L >= 1, non-decreasing from 0 to len(verts_h)")
+    if (origin is None) != (voxel_size is None):
+        raise ValueError("lattice_hull: origin and voxel_size go together")
+    dev = verts_h.device
+    max_abs = int(verts_h.abs().max().item()) if n else 0
+    if max_abs > HULL_MAX_COORD:
+        raise ValueError(f"lattice_hull: a coordinate of magnitude {max_abs} is beyond the limit of {HULL_MAX_COORD}")
+    if origin is not None:
+        origin = torch.as_tensor(origin, dtype=torch.float64).to(dev).contiguous()
+        voxel_size = float(voxel_size)
+        if tuple(origin.shape) != (L, 3):
+            raise ValueError("lattice_hull: origin must be (L,3)")
+        if not (voxel_size > 0 and np.isfinite(voxel_size)):
+            raise ValueError(f"lattice_hull: voxel_size must be positive and finite, got {voxel_size}")
+    st = _stream()
+    off = torch.from_numpy(off_h).to(dev)
+    ws_bytes = int(L_.creg_lattice_hull_workspace_bytes(n, L))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(L, dtype=torch.int32, device=dev)
+    count = torch.empty(L, dtype=torch.int32, device=dev)
+    _check_mesh(L_.creg_lattice_hull_i32(_p(verts_h) if n else None, n, _p(off), off_h.ctypes.data, L, max_abs, _p(status), _p(count),
+                                         _p(ws), ws_bytes, st), "creg_lattice_hull_i32")
+    status_h, count_h = status.cpu().numpy(), count.cpu().numpy()    # the one wait: the face counts size the triangles
+    if strict and status_h.any():
+        l = int(np.nonzero(status_h)[0][0])
+        raise ValueError(f"lattice_hull: link {l} ({off_h[l + 1] - off_h[l]} points) has no hull: "
+                         f"{HULL_STATUS.get(int(status_h[l]), 'status %d' % status_h[l])}")
+    toff_h = np.concatenate([[0], np.cumsum(count_h.astype(np.int64))]).astype(np.int64)
+    F = int(toff_h[-1])
+    toff = torch.from_numpy(toff_h).to(dev)
+    tris = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    rec = torch.empty(F, 4, 3, dtype=torch.float32, device=dev) if origin is not None else None
+    _check_mesh(L_.creg_lattice_hull_emit_i32(_p(verts_h) if n else None, n, _p(off), L, _p(toff), F, _p(origin),
+                                              voxel_size if origin is not None else 0.0, _p(tris) if F else None,
+                                              _p(rec) if (rec is not None and F) else None, _p(ws), ws_bytes, st),
+                "creg_lattice_hull_emit_i32")
+    out = []
+    for l in range(L):
+        t = tris[toff_h[l]:toff_h[l + 1]]
+        d = dict(triangles=t, vertex_ids=torch.unique(t.reshape(-1).to(torch.int64)), status=int(status_h[l]))
+        if rec is not None:
+            d["stl_records"] = rec[toff_h[l]:toff_h[l + 1]]
+        out.append(d)
+    return out
+
+
 # ------------------------------------------------------------------------------ K5 row conversions
 def masked_icp(local: torch.Tensor, world: torch.Tensor, offsets: torch.Tensor, frame: torch.Tensor, M: torch.Tensor,
                scale: float = 1.2, th: float = 1.0, max_iteration: int = 10000, ori: bool = False,

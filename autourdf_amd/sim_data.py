@@ -285,9 +285,14 @@ class UrdfRobot:
     """Kinematic tree + visual triangles of a URDF.  ``links`` in file order; ``joints`` in file order (PyBullet
     numbers joints the same way); ``tri`` (F,3,3) in link frames, ``tri_link`` (F,), ``cum_area`` (F,), ``tri_start`` (L+1,)
     int64: link l owns rows tri_start[l]:tri_start[l+1] of ``tri``.  ``load_meshes=False`` keeps the kinematic tree only: no
-    mesh file is resolved or read, ``tri``, ``tri_link`` and ``cum_area`` are empty and ``tri_start`` is all zero."""
+    mesh file is resolved or read, ``tri``, ``tri_link`` and ``cum_area`` are empty and ``tri_start`` is all zero.
+    ``geometry="collision"`` reads every link's <collision> elements instead of its <visual> ones (their own origins and
+    scales): the hulls of a URDF written with ``--collision_hull``."""
 
-    def __init__(self, urdf_path, global_scale=1.0, package_dirs=(), load_meshes=True):
+    def __init__(self, urdf_path, global_scale=1.0, package_dirs=(), load_meshes=True, geometry="visual"):
+        if geometry not in ("visual", "collision"):
+            raise ValueError(f"geometry must be 'visual' or 'collision', got {geometry!r}")
+        self.geometry = geometry
         self.path = os.path.abspath(urdf_path)
         root = ET.parse(self.path).getroot()
         self.links = [l.get("name") for l in root.findall("link")]
@@ -314,7 +319,7 @@ class UrdfRobot:
             return
         tris, owner = [], []
         for l in root.findall("link"):
-            for vis in l.findall("visual"):
+            for vis in l.findall(geometry):
                 geom = vis.find("geometry")
                 if geom is None or len(geom) == 0:
                     continue
@@ -329,7 +334,7 @@ class UrdfRobot:
                 tris.append(t)
                 owner.append(np.full(len(t), self.link_index[l.get("name")], np.int32))
         if not tris:
-            raise ValueError(f"{urdf_path}: no visual geometry")
+            raise ValueError(f"{urdf_path}: no {geometry} geometry")
         self.tri = np.concatenate(tris)
         self.tri_link = np.concatenate(owner)
         e1, e2 = self.tri[:, 1] - self.tri[:, 0], self.tri[:, 2] - self.tri[:, 0]
@@ -510,11 +515,11 @@ class SimEnv:
 
     def __init__(self, urdf_path, base_position=[0, 0, 0], base_orientation=[0, 0, 0], gui=False, dof=5,
                  ground_flag=False, radius=1.5, num_cameras=3, global_scale=1.0, package_dirs=(), ground_size=None, ground_cells=32,
-                 excluded_pairs=()):
+                 excluded_pairs=(), geometry="visual"):
         if gui:
             raise NotImplementedError("gui=True needs PyBullet's viewer (out of scope)")
         self.dof = dof
-        self.robot = UrdfRobot(urdf_path, global_scale, package_dirs)
+        self.robot = UrdfRobot(urdf_path, global_scale, package_dirs, geometry=geometry)   # "collision": the written hulls
         self.base = np.eye(4)
         self.base[:3, :3] = _rpy_matrix(base_orientation)
         self.base[:3, 3] = base_position

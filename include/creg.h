@@ -444,6 +444,71 @@ int creg_mesh_finish_f64(const int32_t* verts_h, int64_t V, const int32_t* tris,
                          creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Convex collision hulls of the links (DESIGN N4): the exact convex hull of every link's lattice points, all links of a
+ * call in one launch, one workgroup per link.  The contract is this project's own.
+ *   inputs     pts (n,3) int32, the links concatenated (the mesher's verts_h: half-voxel units); offsets (L+1) int64 on the
+ *              device and the same values in offsets_host, which this entry checks before it launches; max_abs: the largest
+ *              |coordinate| if the host knows it, a negative value if it does not.
+ *   build      creg_lattice_hull_i32 writes status (L) int32 and face_count (L) int32 and leaves every link's faces in the
+ *              workspace (creg_lattice_hull_workspace_bytes(n, L): 24 bytes per point, 88 per face slot, 2 n + 4 L slots).
+ *              The host reads face_count -- the one wait, as between creg_mc_count_u8 and creg_mc_emit_i32 -- and sizes
+ *   emit       creg_lattice_hull_emit_i32 on the same workspace: triangles (F,3) int32, indices local to the link's rows of
+ *              pts, link l at rows tri_offsets[l] .. tri_offsets[l+1] (device, (L+1) int64, the prefix sums of face_count),
+ *              in face-slot order.  With stl_records != NULL the same launch writes (F,4,3) float32 records in the format of
+ *              creg_mesh_finish_f64 without smoothing: world = origin[l] + (voxel_size / 2) * v in fp64, rounded to float32;
+ *              the unit normal of the rounded vertices, (0,0,0) if they span no area.  The host only packs bytes.
+ * A link of status CREG_HULL_OK:
+ *   convex     the triangles are a closed, consistently oriented surface of genus 0: every directed edge occurs exactly once
+ *              and so does its reverse, V - E + F = 2, normals point outward, no triangle has zero area, and for every
+ *              face (a,b,c) and every point p of the link det(b-a, c-a, p-a) <= 0, exactly.
+ *   exact      every predicate is an integer determinant in int64; no floating point decides anything and there is no
+ *              tolerance.  |coordinate| <= 16383, so a component of (b-a) x (c-a) is below 2^31 and a determinant below
+ *              6 * 2^45.  max_abs > 16383 is CREG_EINVAL before any launch; a link that holds such a coordinate
+ *              when max_abs < 0 gets CREG_HULL_ERANGE.
+ *   vertices   the vertices used are input points (indices, so trivially) and include every extreme point of the link's
+ *              set.  A point interior to a hull facet or edge is never inserted as an apex (only det > 0 is outside) but may
+ *              be a vertex if it was extreme when inserted; coplanar facets are triangulated as the insertion order left them.
+ *   ties       always to the smallest point index: the seed is the lexicographically smallest point, the farthest from it
+ *              (squared distance), the farthest from that line (squared cross product, in uint64), the farthest from that
+ *              plane (|det|); a round's apex is the point of the lowest face slot that has points above it with the
+ *              largest determinant there; a face is visible from the apex when its determinant is >= 0.
+ *   same bits  no atomics of any kind; every list is kept in a fixed order.  Two runs give the same bits, and a link alone in
+ *              a call gives the same bits as among others.  Nothing outside the outputs and the first
+ *              creg_lattice_hull_workspace_bytes(n, L) bytes of the workspace is written.
+ *   bounded    a round removes its apex from the list of outside points, so a link of n_l points runs at most n_l rounds;
+ *              the live faces never exceed 2 n_l - 4 and a round needs at most 2 fresh slots, so 2 n_l + 4 slots suffice.
+ *              Each bound is checked: CREG_HULL_EBOUND, CREG_HULL_EWORKSPACE, and CREG_HULL_ETOPOLOGY when a horizon is
+ *              not one closed cycle.  None of the three can occur unless the kernel is wrong; no loop waits for another
+ *              thread or workgroup.
+ * Any other status: face_count 0 and no triangle; every other link of the call is unaffected.  CREG_HULL_EFEW: fewer than
+ * 4 points; CREG_HULL_EIDENTICAL / ECOLLINEAR / ECOPLANAR: the points span no volume (duplicated points are otherwise
+ * fine); CREG_HULL_EOFFSETS: offsets[l] .. offsets[l+1] is no range inside 0 .. n (only if the device's offsets differ from
+ * offsets_host).
+ * CREG_EINVAL, nothing launched: n < 0 or > 2^28, L < 1 or > 2^20, a null pointer, offsets_host not non-decreasing from 0 to
+ * n, max_abs > 16383, a workspace that is too small; in emit also n_tri < 0 or > 2 n, and stl_records without an origin or
+ * with a voxel_size that is not positive and finite. */
+enum creg_hull_status {
+    CREG_HULL_OK = 0,
+    CREG_HULL_EFEW = 1,
+    CREG_HULL_EIDENTICAL = 2,
+    CREG_HULL_ECOLLINEAR = 3,
+    CREG_HULL_ECOPLANAR = 4,
+    CREG_HULL_ERANGE = 5,
+    CREG_HULL_EOFFSETS = 6,
+    CREG_HULL_EWORKSPACE = 7,
+    CREG_HULL_EBOUND = 8,
+    CREG_HULL_ETOPOLOGY = 9
+};
+size_t creg_lattice_hull_workspace_bytes(int64_t n, int32_t n_links);
+int creg_lattice_hull_i32(const int32_t* pts, int64_t n, const int64_t* offsets, const int64_t* offsets_host, int32_t n_links,
+                          int64_t max_abs, int32_t* status, int32_t* face_count, void* workspace, size_t workspace_bytes,
+                          creg_stream_t stream);
+int creg_lattice_hull_emit_i32(const int32_t* pts, int64_t n, const int64_t* offsets, int32_t n_links,
+                               const int64_t* tri_offsets, int64_t n_tri, const double* origin, double voxel_size,
+                               int32_t* triangles, float* stl_records, void* workspace, size_t workspace_bytes,
+                               creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * The `--normal` branch (mlp_reg.py:190-203, cluster_icp.py:49-62; CLI flag mlp_reg.py:399): Open3D normal estimation +
  * orientation, then sklearn k_means over [xyz | 0.5 * normal].
  *
