@@ -1,7 +1,7 @@
 // clearance.hip -- link clearance of an articulated triangle mesh, fp64: for every listed link pair of every pose in one call, the
 // minimum squared distance between the two posed triangle meshes and the triangle pair that attains it.  The collision margin of the
 // frame generator is built on it (SimEnv.clearance / collisions(margin=...)); collide.hip answers only yes or no.  The contract is in
-// include/creg.h in full; in short, with the posed vertices and the exact min / max boxes of collide.hip (collide_dev.h):
+// include/creg.h in full; in short, with the posed vertices and the exact min / max boxes of the posing stage (mesh_pose.hip):
 //   gap2(a, b)     = (g_x^2 + g_y^2) + g_z^2,  g_k = max(0, max(lo_a[k] - hi_b[k], lo_b[k] - hi_a[k]))
 //   triangle pair  contributes iff gap2(box_a, box_b) <= d_max * d_max
 //   d2(a, b)       = 0 when the pair collides by the mesh-collide predicate (boxes meet and an edge properly pierces), else the
@@ -14,8 +14,8 @@
 // formula and the same d_max^2 drops no contributing pair, and because "contributes" is part of the contract, culling changes no
 // output.  Nothing is pruned by a running best: the computed d2 and the computed gap2 are different formulas.
 //
-// Passes (CHUNK = 256 triangles; the pose and link-box passes are collide.hip's):
-//   k_collide_pose, k_collide_boxes   posed vertices (P,F,9), chunk boxes and link boxes into the workspace
+// Passes (CHUNK = 256 triangles):
+//   posing stage     mesh_pose.hip: posed vertices (P,F,9), chunk boxes and link boxes into the workspace
 //   k_clear_pairs    grid (tile of link A, pair, pose), 256 threads, the shape of k_collide_pairs with every box_meet turned into
 //                    gap2 <= d_max^2 (except the one inside "collides -> 0"): the tile's triangles within d_max of link B's box are
 //                    ballot-compacted into LDS as SoA and their union box formed; link B is streamed chunk by chunk, chunks beyond
@@ -28,9 +28,7 @@
 //   k_clear_finish   one thread per (pose, pair): the lexicographic minimum over the at most 128 slots -> dist2, witness
 // The minimum over a set does not depend on the order, so the outputs do not depend on scheduling or on the other pairs of a call.
 // fp64 VALU work throughout; nothing here has the shape of a matrix product.
-#include <algorithm>
-#include <cmath>
-#include "collide_dev.h"
+#include "mesh_pair.h"
 
 namespace creg {
 
@@ -296,17 +294,12 @@ __global__ __launch_bounds__(256) void k_clear_finish(const double* __restrict__
     witness[2 * i + 1] = k == CLEAR_NO_KEY ? -1 : (int32_t)(k & 0xffffffffull);
 }
 
-static inline unsigned clear_tiles(int64_t n_tri) {
-    return (unsigned)std::min<int64_t>(std::max<int64_t>((n_tri + COL_CHUNK - 1) / COL_CHUNK, 1), COL_TILES_X);
-}
-struct ClearLayout { size_t posed, chunk_box, link_box, part_d, part_k, total; };
+struct ClearLayout { PoseLayout pose; size_t part_d, part_k, total; };
 static inline ClearLayout clear_layout(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs) {
     ClearLayout w;
-    const size_t slots = (size_t)n_poses * (size_t)n_pairs * clear_tiles(n_tri);
-    w.posed = 0;
-    w.chunk_box = align_up(w.posed + sizeof(double) * 9 * (size_t)n_poses * (size_t)n_tri, 256);
-    w.link_box = align_up(w.chunk_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)collide_slots(n_tri, n_links), 256);
-    w.part_d = align_up(w.link_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)n_links, 256);
+    w.pose = pose_layout(n_tri, n_links, n_poses);
+    const size_t slots = (size_t)n_poses * (size_t)n_pairs * w.pose.tiles;
+    w.part_d = w.pose.end;
     w.part_k = align_up(w.part_d + sizeof(double) * slots, 256);
     w.total = align_up(w.part_k + sizeof(unsigned long long) * slots, 256);
     return w;
@@ -316,7 +309,7 @@ static inline ClearLayout clear_layout(int64_t n_tri, int32_t n_links, int64_t n
 using namespace creg;
 
 extern "C" size_t creg_mesh_clearance_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs) {
-    if (n_tri < 0 || n_tri >= (1ll << 31) || n_links < 1 || n_poses < 1 || n_pairs < 0) return 0;
+    if (!mesh_pair_counts_ok(n_tri, n_links, n_poses, n_pairs)) return 0;
     return clear_layout(n_tri, n_links, n_poses, n_pairs).total;
 }
 
@@ -324,45 +317,30 @@ extern "C" int creg_mesh_clearance_f64(const double* tri, const int64_t* tri_sta
                                        int32_t n_links, int64_t n_poses, const int32_t* pairs, int64_t n_pairs, double d_max,
                                        double* dist2, int32_t* witness, double* link_box, void* workspace, size_t workspace_bytes,
                                        creg_stream_t stream) {
-    CREG_REQUIRE(n_poses >= 1 && n_pairs >= 0 && n_links >= 1 && n_tri >= 0,
-                 "creg_mesh_clearance_f64: bad argument (n_tri %lld, n_links %d, n_poses %lld, n_pairs %lld)", (long long)n_tri,
-                 (int)n_links, (long long)n_poses, (long long)n_pairs);
-    CREG_REQUIRE(n_tri < (1ll << 31) && n_links <= 65535, "creg_mesh_clearance_f64: n_tri < 2^31 and n_links <= 65535 (got %lld, %d)",
-                 (long long)n_tri, (int)n_links);
     CREG_REQUIRE(d_max >= 0.0, "creg_mesh_clearance_f64: d_max must be >= 0 (+inf allowed), got %g", d_max);   // NaN fails too
-    CREG_REQUIRE(tri_start && link_T && workspace && (tri || n_tri == 0), "creg_mesh_clearance_f64: null pointer");
-    CREG_REQUIRE(n_pairs == 0 || (pairs && dist2 && witness), "creg_mesh_clearance_f64: null pairs / dist2 / witness with n_pairs %lld",
-                 (long long)n_pairs);
     const ClearLayout w = clear_layout(n_tri, n_links, n_poses, n_pairs);
-    CREG_REQUIRE(workspace_bytes >= w.total, "creg_mesh_clearance_f64: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
+    if (const int rc = mesh_pair_check("creg_mesh_clearance_f64", tri, tri_start, n_tri, link_T, n_links, n_poses, pairs, n_pairs, dist2,
+                                       witness, "dist2 / witness", workspace, workspace_bytes, w.total))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double* posed = (double*)(ws + w.posed);
-    double* chunk_box = (double*)(ws + w.chunk_box);
-    double* lbox = (double*)(ws + w.link_box);
     double* part_d = (double*)(ws + w.part_d);
     unsigned long long* part_k = (unsigned long long*)(ws + w.part_k);
-    const int64_t n_slots = collide_slots(n_tri, n_links);
-    const unsigned tiles = clear_tiles(n_tri);
     const double dmax2 = d_max * d_max;
     for (int64_t p0 = 0; p0 < n_poses; p0 += 65535) {              // gridDim.y / .z hold at most 65535
         const unsigned np = (unsigned)std::min<int64_t>(n_poses - p0, 65535);
-        hipLaunchKernelGGL(k_collide_pose<0>, dim3(tiles, (unsigned)n_links, np), dim3(256), 0, s, tri, tri_start, n_tri, link_T,
-                           (int)n_links, p0, posed, chunk_box, n_slots);
-        CREG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_collide_boxes<0>, dim3((unsigned)n_links, np), dim3(64), 0, s, tri_start, n_tri, (int)n_links, p0,
-                           chunk_box, n_slots, lbox, link_box);
-        CREG_LAUNCH_CHECK();
+        if (const int rc = mesh_pose_launch(s, tri, tri_start, n_tri, link_T, n_links, p0, np, w.pose, ws, link_box)) return rc;
         for (int64_t m0 = 0; m0 < n_pairs; m0 += 65535) {
             const unsigned nm = (unsigned)std::min<int64_t>(n_pairs - m0, 65535);
-            hipLaunchKernelGGL(k_clear_pairs, dim3(tiles, nm, np), dim3(256), 0, s, tri_start, n_tri, (int)n_links, pairs, n_pairs,
-                               m0, p0, posed, chunk_box, n_slots, lbox, dmax2, part_d, part_k);
+            hipLaunchKernelGGL(k_clear_pairs, dim3(w.pose.tiles, nm, np), dim3(256), 0, s, tri_start, n_tri, (int)n_links, pairs, n_pairs,
+                               m0, p0, (const double*)(ws + w.pose.posed), (const double*)(ws + w.pose.chunk_box), w.pose.n_slots,
+                               (const double*)(ws + w.pose.link_box), dmax2, part_d, part_k);
             CREG_LAUNCH_CHECK();
         }
     }
     if (n_pairs > 0) {
         const int64_t n = n_poses * n_pairs;
-        hipLaunchKernelGGL(k_clear_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part_d, part_k, n, (int)tiles, dist2,
+        hipLaunchKernelGGL(k_clear_finish, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part_d, part_k, n, (int)w.pose.tiles, dist2,
                            witness);
         CREG_LAUNCH_CHECK();
     }

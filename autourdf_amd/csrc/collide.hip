@@ -12,10 +12,8 @@
 // decisions.  Because the box test is part of the contract, every cull below -- link box, chunk box, tile union box, all
 // exact min / max of the same posed vertices -- is exactly conservative: culling changes no output.
 //
-// Passes (CHUNK = 256 triangles, counted from the link's first triangle; the first two and the device helpers are in
-// collide_dev.h, which clearance.hip shares):
-//   k_collide_pose   grid (chunk, link, pose): posed vertices (P,F,9) and one box per chunk into the workspace
-//   k_collide_boxes  one wave per (link, pose): the link box = min / max over its chunk boxes
+// Passes (CHUNK = 256 triangles, counted from the link's first triangle; the device helpers are in mesh_pair.h):
+//   posing stage     mesh_pose.hip: posed vertices (P,F,9), one box per chunk and one per link into the workspace
 //   k_collide_pairs  grid (tile of link A, pair, pose), 256 threads.  Exits when the link boxes, or the tile's chunk box and
 //                    link B's box, are disjoint.  Keeps the tile's triangles whose box meets link B's box, ballot-compacted
 //                    into LDS as SoA (component-major: lane i reads word i, no bank conflict), forms their union box, then
@@ -26,9 +24,7 @@
 //                    something, at the end of the block: the outputs do not depend on scheduling.
 //   k_collide_first  (a << 32 | b) keys -> first (a, b) or (-1, -1)
 // fp64 VALU work throughout; nothing here has the shape of a matrix product.
-#include <algorithm>
-#include <cmath>
-#include "collide_dev.h"
+#include "mesh_pair.h"
 
 namespace creg {
 
@@ -172,13 +168,11 @@ __global__ __launch_bounds__(256) void k_collide_first(const unsigned long long*
     first[2 * i + 1] = k == ~0ull ? -1 : (int32_t)(k & 0xffffffffull);
 }
 
-struct CollideLayout { size_t posed, chunk_box, link_box, keys, total; };
+struct CollideLayout { PoseLayout pose; size_t keys, total; };
 static inline CollideLayout collide_layout(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs) {
     CollideLayout w;
-    w.posed = 0;
-    w.chunk_box = align_up(w.posed + sizeof(double) * 9 * (size_t)n_poses * (size_t)n_tri, 256);
-    w.link_box = align_up(w.chunk_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)collide_slots(n_tri, n_links), 256);
-    w.keys = align_up(w.link_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)n_links, 256);
+    w.pose = pose_layout(n_tri, n_links, n_poses);
+    w.keys = w.pose.end;
     w.total = align_up(w.keys + sizeof(unsigned long long) * (size_t)n_poses * (size_t)n_pairs, 256);
     return w;
 }
@@ -187,7 +181,7 @@ static inline CollideLayout collide_layout(int64_t n_tri, int32_t n_links, int64
 using namespace creg;
 
 extern "C" size_t creg_mesh_collide_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs) {
-    if (n_tri < 0 || n_links < 1 || n_poses < 1 || n_pairs < 0) return 0;
+    if (!mesh_pair_counts_ok(n_tri, n_links, n_poses, n_pairs)) return 0;
     return collide_layout(n_tri, n_links, n_poses, n_pairs).total;
 }
 
@@ -195,40 +189,25 @@ extern "C" int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start
                                      int32_t n_links, int64_t n_poses, const int32_t* pairs, int64_t n_pairs, int32_t* count,
                                      int32_t* first, double* link_box, void* workspace, size_t workspace_bytes,
                                      creg_stream_t stream) {
-    CREG_REQUIRE(n_poses >= 1 && n_pairs >= 0 && n_links >= 1 && n_tri >= 0,
-                 "creg_mesh_collide_f64: bad argument (n_tri %lld, n_links %d, n_poses %lld, n_pairs %lld)", (long long)n_tri,
-                 (int)n_links, (long long)n_poses, (long long)n_pairs);
-    CREG_REQUIRE(n_tri < (1ll << 31) && n_links <= 65535, "creg_mesh_collide_f64: n_tri < 2^31 and n_links <= 65535 (got %lld, %d)",
-                 (long long)n_tri, (int)n_links);
-    CREG_REQUIRE(tri_start && link_T && workspace && (tri || n_tri == 0), "creg_mesh_collide_f64: null pointer");
-    CREG_REQUIRE(n_pairs == 0 || (pairs && count && first), "creg_mesh_collide_f64: null pairs / count / first with n_pairs %lld",
-                 (long long)n_pairs);
     const CollideLayout w = collide_layout(n_tri, n_links, n_poses, n_pairs);
-    CREG_REQUIRE(workspace_bytes >= w.total, "creg_mesh_collide_f64: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
+    if (const int rc = mesh_pair_check("creg_mesh_collide_f64", tri, tri_start, n_tri, link_T, n_links, n_poses, pairs, n_pairs, count,
+                                       first, "count / first", workspace, workspace_bytes, w.total))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double* posed = (double*)(ws + w.posed);
-    double* chunk_box = (double*)(ws + w.chunk_box);
-    double* lbox = (double*)(ws + w.link_box);
     unsigned long long* keys = (unsigned long long*)(ws + w.keys);
-    const int64_t n_slots = collide_slots(n_tri, n_links);
-    const unsigned tiles = (unsigned)std::min<int64_t>(std::max<int64_t>((n_tri + COL_CHUNK - 1) / COL_CHUNK, 1), COL_TILES_X);
     if (n_pairs > 0) {
         CREG_HIP(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)n_poses * (size_t)n_pairs, s));
         CREG_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * (size_t)n_poses * (size_t)n_pairs, s));
     }
     for (int64_t p0 = 0; p0 < n_poses; p0 += 65535) {              // gridDim.y / .z hold at most 65535
         const unsigned np = (unsigned)std::min<int64_t>(n_poses - p0, 65535);
-        hipLaunchKernelGGL(k_collide_pose<0>, dim3(tiles, (unsigned)n_links, np), dim3(256), 0, s, tri, tri_start, n_tri, link_T,
-                           (int)n_links, p0, posed, chunk_box, n_slots);
-        CREG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_collide_boxes<0>, dim3((unsigned)n_links, np), dim3(64), 0, s, tri_start, n_tri, (int)n_links, p0,
-                           chunk_box, n_slots, lbox, link_box);
-        CREG_LAUNCH_CHECK();
+        if (const int rc = mesh_pose_launch(s, tri, tri_start, n_tri, link_T, n_links, p0, np, w.pose, ws, link_box)) return rc;
         for (int64_t m0 = 0; m0 < n_pairs; m0 += 65535) {
             const unsigned nm = (unsigned)std::min<int64_t>(n_pairs - m0, 65535);
-            hipLaunchKernelGGL(k_collide_pairs, dim3(tiles, nm, np), dim3(256), 0, s, tri_start, n_tri, (int)n_links, pairs,
-                               n_pairs, m0, p0, posed, chunk_box, n_slots, lbox, count, keys);
+            hipLaunchKernelGGL(k_collide_pairs, dim3(w.pose.tiles, nm, np), dim3(256), 0, s, tri_start, n_tri, (int)n_links, pairs,
+                               n_pairs, m0, p0, (const double*)(ws + w.pose.posed), (const double*)(ws + w.pose.chunk_box),
+                               w.pose.n_slots, (const double*)(ws + w.pose.link_box), count, keys);
             CREG_LAUNCH_CHECK();
         }
     }

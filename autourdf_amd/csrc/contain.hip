@@ -12,7 +12,7 @@
 // Plain IEEE operations in this order (the library is built with -ffp-contract=off); atan2 and sqrt are the library's.
 //
 // Passes (CHUNK = 256 triangles, counted from the link's first triangle):
-//   k_collide_pose, k_collide_boxes   of collide_dev.h: posed vertices and the exact link boxes
+//   posing stage      mesh_pose.hip: posed vertices and the exact link boxes (the chunk boxes are not used here)
 //   k_contain_pairs   grid (chunk stride of the container, pair x direction, pose), 256 threads.  The block poses the <= 16 points
 //                     of its inner link, gates them against the container's box and leaves when none passes -- the common
 //                     case.  Otherwise a thread keeps one posed triangle of the chunk in registers and walks the gated points
@@ -23,10 +23,8 @@
 //                     (groups of 256 partials, in place, until one is left), then the counts, the first inside row and the
 //                     winding numbers.  Every output element is written, whatever the gate said.
 // fp64 VALU work, dominated by atan2 and three square roots per term; nothing here has the shape of a matrix product.
-#include <algorithm>
-#include <cmath>
 #include <vector>
-#include "collide_dev.h"
+#include "mesh_pair.h"
 
 namespace creg {
 
@@ -203,17 +201,12 @@ __global__ __launch_bounds__(256) void k_contain_finish(const int64_t* __restric
     }
 }
 
-static inline unsigned contain_tiles(int64_t n_tri) {
-    return (unsigned)std::min<int64_t>(std::max<int64_t>((n_tri + COL_CHUNK - 1) / COL_CHUNK, 1), COL_TILES_X);
-}
 static inline int64_t contain_chunks(int64_t n_tri) { return std::max<int64_t>((n_tri + COL_CHUNK - 1) / COL_CHUNK, 1); }
-struct ContainLayout { size_t posed, chunk_box, link_box, part, total; };
+struct ContainLayout { PoseLayout pose; size_t part, total; };
 static inline ContainLayout contain_layout(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs, int32_t q_stride) {
     ContainLayout w;
-    w.posed = 0;
-    w.chunk_box = align_up(w.posed + sizeof(double) * 9 * (size_t)n_poses * (size_t)n_tri, 256);
-    w.link_box = align_up(w.chunk_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)collide_slots(n_tri, n_links), 256);
-    w.part = align_up(w.link_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)n_links, 256);
+    w.pose = pose_layout(n_tri, n_links, n_poses);
+    w.part = w.pose.end;
     w.total = align_up(w.part + sizeof(double) * (size_t)n_poses * (size_t)n_pairs * 2 * (size_t)q_stride * (size_t)contain_chunks(n_tri), 256);
     return w;
 }
@@ -222,7 +215,7 @@ static inline ContainLayout contain_layout(int64_t n_tri, int32_t n_links, int64
 using namespace creg;
 
 extern "C" size_t creg_mesh_contain_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs, int32_t q_stride) {
-    if (n_tri < 0 || n_tri >= (1ll << 31) || n_links < 1 || n_poses < 1 || n_pairs < 0 || q_stride < 1 || q_stride > CON_MAX_PTS) return 0;
+    if (!mesh_pair_counts_ok(n_tri, n_links, n_poses, n_pairs) || q_stride < 1 || q_stride > CON_MAX_PTS) return 0;
     return contain_layout(n_tri, n_links, n_poses, n_pairs, q_stride).total;
 }
 
@@ -231,20 +224,14 @@ extern "C" int creg_mesh_contain_f64(const double* tri, const int64_t* tri_start
                                      const int32_t* pairs, int64_t n_pairs, int32_t q_stride, int32_t* inside, int32_t* first,
                                      double* winding, double* link_box, void* workspace, size_t workspace_bytes,
                                      creg_stream_t stream) {
-    CREG_REQUIRE(n_poses >= 1 && n_pairs >= 0 && n_links >= 1 && n_tri >= 0 && n_pts >= 0,
-                 "creg_mesh_contain_f64: bad argument (n_tri %lld, n_pts %lld, n_links %d, n_poses %lld, n_pairs %lld)", (long long)n_tri,
-                 (long long)n_pts, (int)n_links, (long long)n_poses, (long long)n_pairs);
-    CREG_REQUIRE(n_tri < (1ll << 31) && n_pts < (1ll << 31) && n_links <= 65535,
-                 "creg_mesh_contain_f64: n_tri, n_pts < 2^31 and n_links <= 65535 (got %lld, %lld, %d)", (long long)n_tri, (long long)n_pts,
-                 (int)n_links);
+    CREG_REQUIRE(n_pts >= 0 && n_pts < (1ll << 31), "creg_mesh_contain_f64: 0 <= n_pts < 2^31 (got %lld)", (long long)n_pts);
     CREG_REQUIRE(q_stride >= 1 && q_stride <= CON_MAX_PTS, "creg_mesh_contain_f64: q_stride must be 1 .. %d, got %d", CON_MAX_PTS,
                  (int)q_stride);
-    CREG_REQUIRE(tri_start && pt_start && link_T && workspace && (tri || n_tri == 0) && (pts || n_pts == 0),
-                 "creg_mesh_contain_f64: null pointer");
-    CREG_REQUIRE(n_pairs == 0 || (pairs && inside && first), "creg_mesh_contain_f64: null pairs / inside / first with n_pairs %lld",
-                 (long long)n_pairs);
+    CREG_REQUIRE(pt_start && (pts || n_pts == 0), "creg_mesh_contain_f64: null pointer");
     const ContainLayout w = contain_layout(n_tri, n_links, n_poses, n_pairs, q_stride);
-    CREG_REQUIRE(workspace_bytes >= w.total, "creg_mesh_contain_f64: workspace of %zu bytes, %zu needed", workspace_bytes, w.total);
+    if (const int rc = mesh_pair_check("creg_mesh_contain_f64", tri, tri_start, n_tri, link_T, n_links, n_poses, pairs, n_pairs, inside,
+                                       first, "inside / first", workspace, workspace_bytes, w.total))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     // the points per link are read back before anything is launched: the one host synchronisation of this entry
     std::vector<int64_t> h_start((size_t)n_links + 1);
@@ -258,25 +245,17 @@ extern "C" int creg_mesh_contain_f64(const double* tri, const int64_t* tri_start
                      (int)l, (long long)(b - a), (int)q_stride, CON_MAX_PTS);
     }
     char* ws = (char*)workspace;
-    double* posed = (double*)(ws + w.posed);
-    double* chunk_box = (double*)(ws + w.chunk_box);
-    double* lbox = (double*)(ws + w.link_box);
+    const double* posed = (const double*)(ws + w.pose.posed);
+    const double* lbox = (const double*)(ws + w.pose.link_box);
     double* part = (double*)(ws + w.part);
-    const int64_t n_slots = collide_slots(n_tri, n_links);
-    const unsigned tiles = contain_tiles(n_tri);
     const int64_t C = contain_chunks(n_tri);
     for (int64_t p0 = 0; p0 < n_poses; p0 += 65535) {              // gridDim.y / .z hold at most 65535
         const unsigned np = (unsigned)std::min<int64_t>(n_poses - p0, 65535);
-        hipLaunchKernelGGL(k_collide_pose<0>, dim3(tiles, (unsigned)n_links, np), dim3(256), 0, s, tri, tri_start, n_tri, link_T,
-                           (int)n_links, p0, posed, chunk_box, n_slots);
-        CREG_LAUNCH_CHECK();
-        hipLaunchKernelGGL(k_collide_boxes<0>, dim3((unsigned)n_links, np), dim3(64), 0, s, tri_start, n_tri, (int)n_links, p0,
-                           chunk_box, n_slots, lbox, link_box);
-        CREG_LAUNCH_CHECK();
+        if (const int rc = mesh_pose_launch(s, tri, tri_start, n_tri, link_T, n_links, p0, np, w.pose, ws, link_box)) return rc;
         for (int64_t m0 = 0; m0 < n_pairs; m0 += 32767) {          // two directions per pair in gridDim.y
             const unsigned nm = (unsigned)std::min<int64_t>(n_pairs - m0, 32767);
-            hipLaunchKernelGGL(k_contain_pairs, dim3(tiles, 2 * nm, np), dim3(256), 0, s, tri_start, n_tri, pts, pt_start, n_pts, link_T,
-                               (int)n_links, pairs, n_pairs, m0, p0, posed, lbox, (int)q_stride, C, part);
+            hipLaunchKernelGGL(k_contain_pairs, dim3(w.pose.tiles, 2 * nm, np), dim3(256), 0, s, tri_start, n_tri, pts, pt_start, n_pts,
+                               link_T, (int)n_links, pairs, n_pairs, m0, p0, posed, lbox, (int)q_stride, C, part);
             CREG_LAUNCH_CHECK();
             hipLaunchKernelGGL(k_contain_finish, dim3(2 * nm, np), dim3(256), 0, s, tri_start, n_tri, pts, pt_start, n_pts, link_T,
                                (int)n_links, pairs, n_pairs, m0, p0, lbox, (int)q_stride, C, part, inside, first, winding);

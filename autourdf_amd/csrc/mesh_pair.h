@@ -1,7 +1,10 @@
-// collide_dev.h -- device helpers shared by collide.hip (do two posed link meshes intersect) and clearance.hip (how far apart are
-// they): boxes, the link's rows, the chunk-box slots, the bodies of the pose and link-box passes, the block compaction and the
-// piercing predicate.  Both files pose the same vertices in the same order and take the same exact min / max boxes of them.
+// mesh_pair.h -- what the mesh pair queries share: collide.hip (do two posed link meshes intersect), clearance.hip (how far apart
+// are they) and contain.hip (is one wholly inside the other).
+//   posing stage   mesh_pose.hip: the workspace prefix posed | chunk_box | link_box (pose_layout), the argument checks of the three
+//                  entries (mesh_pair_check) and the pose and link-box passes of one pose slice (mesh_pose_launch)
+//   device helpers boxes, the link's rows, the chunk-box slots, the block compaction and the piercing predicate, for the pair kernels
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include "creg_common.h"
 
@@ -76,7 +79,30 @@ __device__ __forceinline__ void link_rows(const int64_t* __restrict__ tri_start,
 // the chunk boxes of link l start at this slot: distinct links never share one (floor(s / 256) + l is strictly increasing by at
 // least the link's chunk count), and the last slot in use is below floor(F / 256) + L + 1
 __device__ __forceinline__ int64_t chunk_slot(int64_t s, int l) { return (s >> 8) + l; }
-static inline int64_t collide_slots(int64_t n_tri, int32_t n_links) { return (n_tri >> 8) + n_links + 1; }
+
+// the workspace prefix of every query (its own buffers start at `end`), the chunk-box slots of a pose, gridDim.x of the passes
+struct PoseLayout { size_t posed, chunk_box, link_box, end; int64_t n_slots; unsigned tiles; };
+static inline PoseLayout pose_layout(int64_t n_tri, int32_t n_links, int64_t n_poses) {
+    PoseLayout w;
+    w.n_slots = (n_tri >> 8) + n_links + 1;
+    w.tiles = (unsigned)std::min<int64_t>(std::max<int64_t>((n_tri + COL_CHUNK - 1) / COL_CHUNK, 1), COL_TILES_X);
+    w.posed = 0;
+    w.chunk_box = align_up(w.posed + sizeof(double) * 9 * (size_t)n_poses * (size_t)n_tri, 256);
+    w.link_box = align_up(w.chunk_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)w.n_slots, 256);
+    w.end = align_up(w.link_box + sizeof(double) * 6 * (size_t)n_poses * (size_t)n_links, 256);
+    return w;
+}
+// the counts for which the *_workspace_bytes calls answer with a size
+static inline bool mesh_pair_counts_ok(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs) {
+    return n_tri >= 0 && n_tri < (1ll << 31) && n_links >= 1 && n_poses >= 1 && n_pairs >= 0;
+}
+// the entries' shared checks, `who` in every message: counts, limits, null pointers (`outs` names the two outputs), workspace size
+int mesh_pair_check(const char* who, const void* tri, const void* tri_start, int64_t n_tri, const void* link_T, int32_t n_links,
+                    int64_t n_poses, const void* pairs, int64_t n_pairs, const void* out_a, const void* out_b, const char* outs,
+                    const void* workspace, size_t workspace_bytes, size_t need);
+// k_collide_pose and k_collide_boxes for the poses [p0, p0 + np), np <= 65535; link_box_out may be null
+int mesh_pose_launch(hipStream_t s, const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                     int64_t p0, unsigned np, const PoseLayout& w, void* workspace, double* link_box_out);
 
 __device__ __forceinline__ double orient(const double* p, const double* q, const double* r, const double* s) {
     const double ux = q[0] - p[0], uy = q[1] - p[1], uz = q[2] - p[2];
@@ -102,75 +128,6 @@ __device__ __forceinline__ bool edges_pierce(const double* E, const double* T) {
         }
     }
     return hit;
-}
-
-// The pose pass, grid (chunk, link, pose): posed vertices (P,F,9) and one box per chunk into the workspace.  A template, like the
-// link-box pass below, only so that both translation units may hold it.
-template <int kUnused = 0>
-__global__ __launch_bounds__(256) void k_collide_pose(const double* __restrict__ tri, const int64_t* __restrict__ tri_start,
-                                                      int64_t F, const double* __restrict__ link_T, int L, int64_t p0,
-                                                      double* __restrict__ posed, double* __restrict__ chunk_box,
-                                                      int64_t n_slots) {
-    __shared__ double s_red[30];
-    const int l = blockIdx.y;
-    const int64_t p = p0 + blockIdx.z;
-    int64_t s, e;
-    link_rows(tri_start, l, F, s, e);
-    const int64_t n_chunks = (e - s + COL_CHUNK - 1) / COL_CHUNK;
-    const double* T = link_T + ((size_t)p * L + l) * 16;
-    for (int64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-        const int64_t f = s + c * COL_CHUNK + threadIdx.x;
-        Box b;
-        box_empty(b);
-        if (f < e) {
-            double v[9], w[9];
-#pragma unroll
-            for (int k = 0; k < 9; ++k) v[k] = tri[(size_t)f * 9 + k];
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    w[3 * j + i] = ((T[4 * i] * v[3 * j] + T[4 * i + 1] * v[3 * j + 1]) + T[4 * i + 2] * v[3 * j + 2]) + T[4 * i + 3];
-            double* dst = posed + ((size_t)p * F + f) * 9;
-#pragma unroll
-            for (int k = 0; k < 9; ++k) dst[k] = w[k];
-            box_of_tri(w, b);
-        }
-        box_block_reduce(b, s_red);
-        const int64_t slot = chunk_slot(s, l) + c;
-        if (threadIdx.x == 0 && slot < n_slots) box_store(chunk_box + ((size_t)p * n_slots + slot) * 6, b);
-        __syncthreads();                                         // s_red is written again in the next trip
-    }
-}
-
-// The link-box pass, one wave per (link, pose): the link box = min / max over its chunk boxes.
-template <int kUnused = 0>
-__global__ __launch_bounds__(64) void k_collide_boxes(const int64_t* __restrict__ tri_start, int64_t F, int L, int64_t p0,
-                                                      const double* __restrict__ chunk_box, int64_t n_slots,
-                                                      double* __restrict__ link_box_ws, double* __restrict__ link_box_out) {
-    const int l = blockIdx.x;
-    const int64_t p = p0 + blockIdx.y;
-    int64_t s, e;
-    link_rows(tri_start, l, F, s, e);
-    const int64_t n_chunks = (e - s + COL_CHUNK - 1) / COL_CHUNK;
-    Box b;
-    box_empty(b);
-    for (int64_t c = threadIdx.x; c < n_chunks; c += 64) {
-        const int64_t slot = chunk_slot(s, l) + c;
-        if (slot < n_slots) {
-            const double* cb = chunk_box + ((size_t)p * n_slots + slot) * 6;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                b.lo[k] = fmin(b.lo[k], cb[k]);
-                b.hi[k] = fmax(b.hi[k], cb[3 + k]);
-            }
-        }
-    }
-    box_wave_reduce(b);
-    if (threadIdx.x == 0) {
-        box_store(link_box_ws + ((size_t)p * L + l) * 6, b);
-        if (link_box_out) box_store(link_box_out + ((size_t)p * L + l) * 6, b);
-    }
 }
 
 // Stable compaction of the block's `keep` flags: the thread's slot among the kept (or -1) and their number.  s_cnt: 4 ints;

@@ -535,6 +535,20 @@ def _mesh_pair_args(who, tri, tri_start, link_T, pairs):
     return tri, tri_start, link_T, pairs, F, P, n_links, M
 
 
+def _mesh_pair_call(L, entry, tri, tri_start, link_T, pairs, outs, want_boxes, points=(), params=(), size_params=()):
+    """The tail the mesh pair queries share: the optional link_box, the workspace ``creg_mesh_<entry>_workspace_bytes`` asks for,
+    null pointers for an empty ``tri`` or ``pairs`` (then for the outputs too) and the call -> link_box or None.  ``points`` go
+    between F and link_T, ``params`` between M and the outputs, ``size_params`` after M in the workspace call."""
+    F, (P, n_links), M, dev = tri.shape[0], link_T.shape[:2], pairs.shape[0], tri.device
+    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
+    ws_bytes = getattr(L, f"creg_mesh_{entry}_workspace_bytes")(F, n_links, P, M, *size_params)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    name = f"creg_mesh_{entry}_f64"
+    _lib.check(getattr(L, name)(_p(tri) if F else None, _p(tri_start), F, *points, _p(link_T), n_links, P, _p(pairs) if M else None, M,
+                                *params, *(_p(o) if M else None for o in outs), _p(boxes), _p(ws), ws_bytes, _stream()), name)
+    return boxes
+
+
 def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
     """Self-collision of posed link meshes (creg_mesh_collide_f64; the contract is in include/creg.h): tri (F,3,3) f64
     link-frame triangles, tri_start (L+1) int64 (link l owns rows tri_start[l]:tri_start[l+1]), link_T (P,L,4,4) f64 -- or
@@ -544,15 +558,9 @@ def mesh_collide(tri, tri_start, link_T, pairs, want_boxes: bool = False):
     and for a tri_start that does not run 0 .. F without decreasing (both are read back: the one synchronisation)."""
     L = _lib.load()
     tri, tri_start, link_T, pairs, F, P, n_links, M = _mesh_pair_args("mesh_collide", tri, tri_start, link_T, pairs)
-    dev = tri.device
-    count = torch.empty(P, M, dtype=torch.int32, device=dev)
-    first = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
-    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
-    ws_bytes = L.creg_mesh_collide_workspace_bytes(F, n_links, P, M)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-    _lib.check(L.creg_mesh_collide_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pairs) if M else None, M,
-                                       _p(count) if M else None, _p(first) if M else None, _p(boxes), _p(ws), ws_bytes, _stream()),
-               "creg_mesh_collide_f64")
+    count = torch.empty(P, M, dtype=torch.int32, device=tri.device)
+    first = torch.empty(P, M, 2, dtype=torch.int32, device=tri.device)
+    boxes = _mesh_pair_call(L, "collide", tri, tri_start, link_T, pairs, (count, first), want_boxes)
     return (count, first, boxes) if want_boxes else (count, first)
 
 
@@ -569,15 +577,9 @@ def mesh_clearance(tri, tri_start, link_T, pairs, d_max, want_boxes: bool = Fals
     if not d_max >= 0.0:
         raise ValueError(f"mesh_clearance: d_max must be >= 0 (inf allowed), got {d_max}")
     tri, tri_start, link_T, pairs, F, P, n_links, M = _mesh_pair_args("mesh_clearance", tri, tri_start, link_T, pairs)
-    dev = tri.device
-    dist2 = torch.empty(P, M, dtype=torch.float64, device=dev)
-    witness = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
-    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
-    ws_bytes = L.creg_mesh_clearance_workspace_bytes(F, n_links, P, M)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-    _lib.check(L.creg_mesh_clearance_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pairs) if M else None, M,
-                                         d_max, _p(dist2) if M else None, _p(witness) if M else None, _p(boxes), _p(ws), ws_bytes,
-                                         _stream()), "creg_mesh_clearance_f64")
+    dist2 = torch.empty(P, M, dtype=torch.float64, device=tri.device)
+    witness = torch.empty(P, M, 2, dtype=torch.int32, device=tri.device)
+    boxes = _mesh_pair_call(L, "clearance", tri, tri_start, link_T, pairs, (dist2, witness), want_boxes, params=(d_max,))
     dist = torch.where(dist2 > d_max * d_max, torch.full_like(dist2, float("inf")), torch.sqrt(dist2))
     return (dist, witness, boxes) if want_boxes else (dist, witness)
 
@@ -611,12 +613,8 @@ def mesh_contain(tri, tri_start, pts, pt_start, link_T, pairs, want_winding: boo
     inside = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
     first = torch.empty(P, M, 2, dtype=torch.int32, device=dev)
     winding = torch.empty(P, M, 2, Q, dtype=torch.float64, device=dev) if want_winding else None
-    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
-    ws_bytes = L.creg_mesh_contain_workspace_bytes(F, n_links, P, M, Q)
-    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-    _lib.check(L.creg_mesh_contain_f64(_p(tri) if F else None, _p(tri_start), F, _p(pts) if N else None, _p(pt_start), N, _p(link_T),
-                                       n_links, P, _p(pairs) if M else None, M, Q, _p(inside) if M else None, _p(first) if M else None,
-                                       _p(winding) if M else None, _p(boxes), _p(ws), ws_bytes, _stream()), "creg_mesh_contain_f64")
+    boxes = _mesh_pair_call(L, "contain", tri, tri_start, link_T, pairs, (inside, first, winding), want_boxes,
+                            points=(_p(pts) if N else None, _p(pt_start), N), params=(Q,), size_params=(Q,))
     return (inside, first) + ((winding,) if want_winding else ()) + ((boxes,) if want_boxes else ())
 
 

@@ -659,7 +659,8 @@ int creg_urdf_fk_f64(const int32_t* parent, const int32_t* child, const int32_t*
  * A pair that names a link outside [0, n_links), or one link twice, gives count 0 and (-1,-1).  n_pairs == 0 is valid and
  * fills link_box only.  Only integer atomics (add, 64-bit min of (a << 32) | b): two runs are identical.
  * CREG_EINVAL, nothing launched: n_poses < 1, n_pairs < 0, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, a workspace smaller
- * than creg_mesh_collide_workspace_bytes(n_tri, n_links, n_poses, n_pairs) (posed vertices, chunk and link boxes, keys).
+ * than creg_mesh_collide_workspace_bytes(n_tri, n_links, n_poses, n_pairs) (posed vertices, chunk and link boxes, keys), which
+ * is 0 for n_tri < 0 or >= 2^31, n_links < 1, n_poses < 1 and n_pairs < 0.
  * Limits: colliding triangle pairs per link pair and pose < 2^31. */
 size_t creg_mesh_collide_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pairs);
 int creg_mesh_collide_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,

@@ -114,6 +114,19 @@ def test_two_runs_are_identical(sizes):
         assert x.tobytes() == y.tobytes()
 
 
+def test_the_three_mesh_queries_return_the_same_link_boxes(sizes):
+    """mesh_collide, mesh_clearance and mesh_contain run one posing stage: their link_box outputs agree byte for byte (P = 2)."""
+    from autourdf_amd import ops
+    tri, start, link_T, pairs, want = sizes
+    d = [dev(x) for x in (tri, start, link_T[:2], pairs)]
+    no_pts, no_rows = torch.zeros(0, 3, dtype=torch.float64, device="cuda"), torch.zeros(len(start), dtype=torch.int64, device="cuda")
+    boxes = [ops.mesh_collide(*d, want_boxes=True)[-1], ops.mesh_clearance(*d, 0.02, want_boxes=True)[-1],
+             ops.mesh_contain(d[0], d[1], no_pts, no_rows, d[2], d[3], want_boxes=True)[-1]]
+    raw = [b.cpu().numpy().tobytes() for b in boxes]
+    assert raw[0] == raw[1] == raw[2]
+    np.testing.assert_array_equal(boxes[0].cpu().numpy(), want[2][:2])
+
+
 def test_wrapper_raises_for_bad_pairs_and_shapes(sizes):
     from autourdf_amd import ops
     tri, start, link_T, pairs, _ = sizes

@@ -50,6 +50,37 @@ def test_kmeans_workspace_sizes_are_pinned_across_the_geometry_switches():
     assert lib.creg_kmeans_batch_workspace_bytes(17, 1, 0) == 0
 
 
+def test_mesh_pair_workspace_sizes_are_pinned_across_the_chunk_and_tile_switches():
+    """creg_mesh_collide / clearance / contain_workspace_bytes are pure host arithmetic: the shared prefix posed | chunk_box |
+    link_box, then each query's own tail.  n_tri on both sides of a 256-triangle chunk and of the 128-wide tile grid (32768),
+    with and without pairs.  The numbers are those of the library before the three entries shared one posing stage; callers'
+    allocations depend on them.  The one difference: creg_mesh_collide_workspace_bytes answered n_tri = 2^31 with a size the
+    entry itself refused; it now returns 0 as the other two always did."""
+    from autourdf_amd import _lib
+    lib = _lib.load(check_device=False)
+    tris = (0, 1, 255, 256, 257, 32768, 32769)
+    expected = {   # (n_links, n_poses, n_pairs): per n_tri (collide, clearance, contain at q_stride 1, contain at 16)
+        (1, 1, 0): ((512, 512, 512, 512), (768, 768, 768, 768), (18944, 18944, 18944, 18944), (18944, 18944, 18944, 18944), (19200, 19200, 19200, 19200), (2365952, 2365952, 2365952, 2365952), (2366208, 2366208, 2366208, 2366208)),
+        (1, 1, 5): ((768, 1024, 768, 1792), (1024, 1280, 1024, 2048), (19200, 19456, 19200, 20224), (19200, 19456, 19200, 20224), (19456, 19712, 19456, 21760), (2366208, 2376192, 2376192, 2529792), (2366464, 2376448, 2376704, 2531328)),
+        (1, 3, 0): ((768, 768, 768, 768), (1024, 1024, 1024, 1024), (56064, 56064, 56064, 56064), (56064, 56064, 56064, 56064), (56320, 56320, 56320, 56320), (7097088, 7097088, 7097088, 7097088), (7097344, 7097344, 7097344, 7097344)),
+        (1, 3, 5): ((1024, 1280, 1024, 4608), (1280, 1536, 1280, 4864), (56320, 56576, 56320, 59904), (56320, 56576, 56320, 59904), (56576, 56832, 56832, 64000), (7097344, 7127808, 7127808, 7588608), (7097600, 7128064, 7128320, 7592704)),
+        (12, 1, 0): ((1536, 1536, 1536, 1536), (1792, 1792, 1792, 1792), (19968, 19968, 19968, 19968), (19968, 19968, 19968, 19968), (20224, 20224, 20224, 20224), (2366976, 2366976, 2366976, 2366976), (2367232, 2367232, 2367232, 2367232)),
+        (12, 1, 5): ((1792, 2048, 1792, 2816), (2048, 2304, 2048, 3072), (20224, 20480, 20224, 21248), (20224, 20480, 20224, 21248), (20480, 20736, 20480, 22784), (2367232, 2377216, 2377216, 2530816), (2367488, 2377472, 2377728, 2532352)),
+        (12, 3, 0): ((3840, 3840, 3840, 3840), (4096, 4096, 4096, 4096), (59136, 59136, 59136, 59136), (59136, 59136, 59136, 59136), (59392, 59392, 59392, 59392), (7100160, 7100160, 7100160, 7100160), (7100416, 7100416, 7100416, 7100416)),
+        (12, 3, 5): ((4096, 4352, 4096, 7680), (4352, 4608, 4352, 7936), (59392, 59648, 59392, 62976), (59392, 59648, 59392, 62976), (59648, 59904, 59904, 67072), (7100416, 7130880, 7130880, 7591680), (7100672, 7131136, 7131392, 7595776)),
+    }
+    for (n_links, n_poses, n_pairs), rows in expected.items():
+        for n_tri, want in zip(tris, rows):
+            args = (n_tri, n_links, n_poses, n_pairs)
+            got = (lib.creg_mesh_collide_workspace_bytes(*args), lib.creg_mesh_clearance_workspace_bytes(*args),
+                   lib.creg_mesh_contain_workspace_bytes(*args, 1), lib.creg_mesh_contain_workspace_bytes(*args, 16))
+            assert got == want, args
+    for bad in ((-1, 1, 1, 0), (1 << 31, 1, 1, 0), (1, 0, 1, 0), (1, 1, 0, 0), (1, 1, 1, -1)):
+        assert lib.creg_mesh_collide_workspace_bytes(*bad) == 0 and lib.creg_mesh_clearance_workspace_bytes(*bad) == 0, bad
+        assert lib.creg_mesh_contain_workspace_bytes(*bad, 1) == 0, bad
+    assert lib.creg_mesh_contain_workspace_bytes(1, 1, 1, 0, 0) == 0 and lib.creg_mesh_contain_workspace_bytes(1, 1, 1, 0, 17) == 0
+
+
 def test_every_environment_variable_the_library_reads_is_documented():
     """Every getenv("CREG_...") of the library's sources has a row of its own in the "Environment" table of INTEGRATION.md."""
     csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
