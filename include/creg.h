@@ -241,7 +241,9 @@ int creg_icp_p2p_f64(const double* src, int64_t n_src, const int32_t* src_offset
  * out8 (HOST, 8 doubles, may be NULL): [0] waves that searched, [1] float32 screen trips (a trip = 8 staged targets x 64 lanes = 512
  * pair evaluations), [2] trips that went on to the fp64 evaluation, [3] source-iterations (live sources summed over launches),
  * [4] tie rescans, [5] summed k_icp_nn launch time in microseconds, [6] launches timed, [7] 0.  reset != 0: zero all of it afterwards.
- * timing: 1 / 0 switches the event bracketing on / off, < 0 leaves it.  Synchronises the device (hipMemcpyFromSymbol). */
+ * timing: 1 / 0 switches the event bracketing on / off, < 0 leaves it.  Synchronises the device (hipMemcpyFromSymbol).
+ * The hook is for ONE host thread and the CURRENT device: the timing switch and its two tallies are plain process-wide host state
+ * (no lock, no atomics), the work counters are those of the device that is current when it is called. */
 int creg_icp_nn_counters(double* out8, int32_t reset, int32_t timing);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Debug build only: where the cycles of one k_masked_icp workgroup go (see CREG_STAMPS in csrc/icp.hip).
+"""Debug build only: where the cycles of one k_masked_icp workgroup go (see CREG_STAMPS in csrc/icp_dev.h and the ICP_STAMP calls of csrc/icp_small.hip).
 
     CREG_EXTRA_FLAGS=-DCREG_STAMPS python -m autourdf_amd.build --force
     python tests/measure/icp_stamps.py > gpurun_out/icp_stamps.log

@@ -176,7 +176,7 @@ def test_icp_point_to_point_in_the_many_workgroup_regime_vs_oracle():
 
 
 def test_icp_point_to_point_large_regime_empty_target_segment_and_far_coordinates():
-    """ADVICE r5 (icp.hip, many-workgroup point-to-point mode): (a) a pair whose TARGET segment is empty used to give a NaN box centre and an
+    """ADVICE r5 (icp_large.hip, many-workgroup point-to-point mode): (a) a pair whose TARGET segment is empty used to give a NaN box centre and an
     infinite screen bound -- it must leave its pose at the initial one, 0 iterations' worth of change, and not disturb its neighbours;
     (b) targets far from the origin relative to their extent (|coordinate| / extent ~ 1e6: the float32 box is a rounding of the fp64
     targets, now widened by one ulp) still match the oracle."""

@@ -3,6 +3,7 @@
 Bar: bit-exact for indices, labels and the integer-order-independent quantities (L1 distances,
 fp64 k-means distances); fp32 poses / losses within the tolerances written at each assert.
 """
+import functools
 import os
 
 import numpy as np
@@ -1878,7 +1879,7 @@ np.savez(OUT, **out)
 
 def test_masked_icp_float32_screen_changes_no_bit(dev, tmp_path):
     """k_icp_nn skips a trip of eight targets when a float32 evaluation proves that none of them can reach the running best
-    (bound derived in csrc/icp.hip), and starts the running best a hair above the previous match: both only ever skip work.
+    (bound derived in csrc/icp_large.hip), and starts the running best a hair above the previous match: both only ever skip work.
     Two frames of a chain32-shaped sequence in the many-workgroup regime (N = 65536, K = 24: clusters of ~2700 points), the second
     from the first's poses so that previous matches exist -- poses, world clouds and iteration counts must be IDENTICAL to a run
     with CREG_ICP_SCREEN=0 in a child process (the knob is read once per process)."""
@@ -2133,3 +2134,117 @@ def test_masked_icp_launch_timing_changes_no_result(dev):
     plain = go()
     assert launches > 0
     assert all(torch.equal(a, b) for a, b in zip(timed, plain)) and int(plain[2][0]) >= 1
+
+
+def _many_workgroup_problem(dev, seed, k, nf, angle):
+    """The smallest masked problem of the many-workgroup regime: k clusters of 1025 points (n / k > 1024) against a frame of nf points."""
+    from autourdf_amd import ops
+    rng = np.random.default_rng(seed)
+    clusters = [rng.normal(size=(1025, 3)) * [0.06, 0.04, 0.03] + [0.5 * c, 0.0, 0.0] for c in range(k)]
+    moved = np.concatenate(clusters) @ _rot_z(angle).T + [0.003, 0.001, -0.002]
+    frame = np.concatenate([moved, rng.uniform(-0.3, 0.8, size=(nf - len(moved), 3))])[rng.permutation(nf)]
+    frame = frame + rng.normal(scale=3e-4, size=frame.shape)
+    assert ops.masked_icp_regime(1025 * k, nf, k) == "many_workgroups"
+    local, off = ops.pack_clusters(clusters, dev, torch.float64)
+    M = _cuda(np.tile(np.eye(4), (k, 1, 1)), dev)
+    world32 = ops.cluster_transform(local.to(torch.float32), off, M.to(torch.float32))
+    return local, world32, off, _cuda(frame, dev), M
+
+
+def test_masked_icp_many_workgroups_two_streams_on_one_thread_equal_the_calls_alone(dev):
+    """The many-workgroup driver keeps one pinned counter ring per host thread and returns with its last copy into it still in
+    flight.  Two calls from this thread on two different non-default streams, back to back -- the second must not reuse the ring
+    before the first call's last copy has landed, whichever stream that was on -- then the same two calls each alone: poses,
+    moved clouds and iteration counts bit-identical.  k = 1 and k = 2, 1025 points per cluster, frames of 3000 and 4000 points."""
+    from autourdf_amd import ops
+    A, B = _many_workgroup_problem(dev, 31, 1, 3000, 0.03), _many_workgroup_problem(dev, 32, 2, 4000, 0.05)
+    sa, sb = torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)
+    for s in (sa, sb):
+        s.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(sa):
+        ra = ops.masked_icp(*A)
+    with torch.cuda.stream(sb):
+        rb = ops.masked_icp(*B)
+    torch.cuda.synchronize(dev)
+    together = [t.cpu() for t in ra + rb]
+    alone = []
+    for prob in (A, B):
+        alone += [t.cpu() for t in ops.masked_icp(*prob)]
+        torch.cuda.synchronize(dev)
+    assert all(torch.equal(a, b) for a, b in zip(together, alone))
+    assert all(int(i) >= 1 for i in alone[2]) and all(int(i) >= 1 for i in alone[5])
+
+
+def test_masked_icp_many_workgroups_on_a_thread_that_ends_equals_the_main_thread(dev):
+    """The driver's pinned ring belongs to the calling host thread and is released when that thread ends (its last copy waited
+    for first).  The same problem from a short-lived thread, joined, and then from this thread: identical results, and the
+    ended thread leaves the process able to go on."""
+    import threading
+    from autourdf_amd import ops
+    prob = _many_workgroup_problem(dev, 33, 1, 3000, 0.04)
+    got = []
+
+    def work():
+        torch.cuda.set_device(dev)
+        got.extend(t.cpu() for t in ops.masked_icp(*prob))
+
+    t = threading.Thread(target=work)
+    t.start()
+    t.join()
+    here = [t.cpu() for t in ops.masked_icp(*prob)]
+    assert len(got) == 3 and all(torch.equal(a, b) for a, b in zip(got, here)) and int(here[2][0]) >= 1
+
+
+def test_masked_icp_many_workgroups_batch_of_two_equals_the_two_singles(dev):
+    """creg_masked_icp_batch_f64 in the many-workgroup regime runs its problems one after the other, each in its own share of the
+    workspace: a batch of two (k = 2, 2050 sources, frames of 3000 points, different motions) gives the results of the two
+    problems run singly, bit for bit."""
+    from autourdf_amd import ops
+    probs = [_many_workgroup_problem(dev, 41, 2, 3000, 0.03), _many_workgroup_problem(dev, 42, 2, 3000, -0.06)]
+    batch = ops.masked_icp_batch(probs)
+    for got, prob in zip(batch, probs):
+        want = ops.masked_icp(*prob)
+        assert all(torch.equal(a, b) for a, b in zip(got, want)) and (want[2] >= 1).all()
+    assert not torch.equal(batch[0][0], batch[1][0])
+
+
+@functools.lru_cache(maxsize=None)
+def _p2p_cap_problem():
+    rng = np.random.default_rng(51)
+    tgt = rng.uniform(-0.2, 0.2, size=(3000, 3)) * [1.0, 0.6, 0.15]
+    src = tgt[rng.permutation(3000)[:1025]] @ _rot_z(0.12).T + [0.02, -0.015, 0.01] + rng.normal(scale=5e-4, size=(1025, 3))
+    return src, tgt
+
+
+@pytest.mark.parametrize("cap", [1, 15, 16, 17])
+def test_icp_p2p_many_workgroups_iteration_caps_around_one_batch_of_launches(dev, cap):
+    """max_iteration on both sides of the host's batch of 16 launches (a cap of c needs c + 1 launches: 2, 16, 17 and 18), point
+    to point, one pair of 1025 sources against 3000 targets that needs more than 17 iterations.  Against the oracle's
+    registration_icp with the same cap: pose and moved source to 1e-8 (the bound of every K4-against-oracle test here: the two
+    sum in different orders, fp64, a few hundred terms per moment and at most 17 iterations -- 1e-13 at worst -- while the
+    callers need 1e-5), iteration count equal; and against the one-workgroup kernel on the same input
+    (CREG_ICP_P2P_ONE_WORKGROUP=1): iteration count equal, pose and moved source to 1e-12 as in
+    test_icp_point_to_point_in_the_many_workgroup_regime_vs_oracle.  The two regimes are NOT bit-identical at any of these caps
+    (measured on the library before icp.hip was split and after, the same figures: max |T - T1| 1.6e-17, 1.7e-17, 6.9e-18,
+    6.9e-18 and max |moved - moved1| 5.6e-17, 5.6e-17, 2.8e-17, 2.8e-17 at caps 1, 15, 16, 17): they sum the moments in different
+    trees, as creg.h says."""
+    from autourdf_amd import ops
+    from oracle import icp as oicp
+    src, tgt = _p2p_cap_problem()
+    args = (_cuda(src, dev), torch.tensor([0, len(src)], dtype=torch.int32, device=dev), _cuda(tgt, dev),
+            torch.tensor([0, len(tgt)], dtype=torch.int32, device=dev), _cuda(np.eye(4)[None], dev))
+    assert ops.masked_icp_regime(len(src), len(tgt), 1) == "many_workgroups"
+    T, moved, n_it = ops.icp_p2p(*args, th=0.1, max_iteration=cap)
+    os.environ["CREG_ICP_P2P_ONE_WORKGROUP"] = "1"
+    try:
+        T1, moved1, n_it1 = ops.icp_p2p(*args, th=0.1, max_iteration=cap)
+    finally:
+        del os.environ["CREG_ICP_P2P_ONE_WORKGROUP"]
+    T_ref, _, _, n_ref = oicp.registration_icp(src, tgt, 0.1, np.eye(4), cap)
+    print(f"cap {cap}: iterations {int(n_it[0])} / {int(n_it1[0])} / {n_ref}, max |T - T1| {(T - T1).abs().max().item():.3e}, "
+          f"max |moved - moved1| {(moved - moved1).abs().max().item():.3e}, max |T - T_ref| {np.abs(T[0].cpu().numpy() - T_ref).max():.3e}")
+    assert int(n_it[0]) == int(n_it1[0]) == n_ref == cap
+    np.testing.assert_allclose(T[0].cpu().numpy(), T_ref, rtol=0, atol=1e-8)
+    np.testing.assert_allclose(moved.cpu().numpy(), src @ T_ref[:3, :3].T + T_ref[:3, 3], rtol=0, atol=1e-8)
+    np.testing.assert_allclose(T.cpu().numpy(), T1.cpu().numpy(), rtol=0, atol=1e-12)
+    np.testing.assert_allclose(moved.cpu().numpy(), moved1.cpu().numpy(), rtol=0, atol=1e-12)

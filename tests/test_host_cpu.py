@@ -81,6 +81,99 @@ def test_mesh_pair_workspace_sizes_are_pinned_across_the_chunk_and_tile_switches
     assert lib.creg_mesh_contain_workspace_bytes(1, 1, 1, 0, 0) == 0 and lib.creg_mesh_contain_workspace_bytes(1, 1, 1, 0, 17) == 0
 
 
+def test_icp_workspace_sizes_are_pinned_across_every_term_of_the_layout():
+    """creg_icp_workspace_bytes / creg_icp_batch_workspace_bytes are pure host arithmetic: the larger of the two regimes'
+    layouts.  n on both sides of a 64-source chunk, n / k on both sides of the regime's 1024, nf on both sides of 65536, k on
+    both sides of the coordinate pool's cap min(4 nf, k nf), one configs[4]-like shape; batch 1 and 3.  The numbers are those
+    of the library before icp.hip was split and the many-workgroup layout became one carve function; callers' allocations
+    depend on them."""
+    from autourdf_amd import _lib
+    lib = _lib.load(check_device=False)
+    expected = {   # (n, nf, k): (workspace bytes, batch workspace bytes at batch = 1, at batch = 3)
+        (63, 100, 1): (28672, 28672, 86016),
+        (64, 100, 1): (28672, 28672, 86016),
+        (65, 100, 1): (29440, 29440, 88320),
+        (1024, 100, 1): (80640, 80640, 241920),
+        (1025, 100, 1): (81408, 81408, 244224),
+        (2048, 500, 2): (192256, 192256, 576768),
+        (2050, 500, 2): (193024, 193024, 579072),
+        (200, 65536, 2): (5815040, 5815040, 17445120),
+        (200, 65537, 2): (5816320, 5816320, 17448960),
+        (1000, 777, 3): (210944, 210944, 632832),
+        (1000, 777, 4): (262400, 262400, 787200),
+        (1000, 777, 5): (282624, 282624, 847872),
+        (120000, 120000, 30): (40620288, 40620288, 121860864),
+    }
+    for shape, want in expected.items():
+        got = (lib.creg_icp_workspace_bytes(*shape), lib.creg_icp_batch_workspace_bytes(*shape, 1), lib.creg_icp_batch_workspace_bytes(*shape, 3))
+        assert got == want, shape
+    for bad in ((0, 100, 1), (100, 0, 1), (100, 100, 0), (-1, 100, 1)):
+        assert lib.creg_icp_workspace_bytes(*bad) == 0 and lib.creg_icp_batch_workspace_bytes(*bad, 1) == 0, bad
+    assert lib.creg_icp_batch_workspace_bytes(100, 100, 1, 0) == 0 and lib.creg_icp_batch_workspace_bytes(100, 100, 1, -1) == 0
+
+
+def test_icp_entries_refuse_bad_arguments_before_any_device_call():
+    """The ICP entries, creg_aabb_mask_f64 and creg_kabsch_f64 answer a bad argument with CREG_EINVAL and their own name in the
+    error text.  There is no device here (a HIP call would give CREG_EHIP) and the pointers are made-up addresses that are never
+    dereferenced.  Shapes of both regimes; the null field inside problem 1 of 2 at a one-workgroup shape (every problem is checked
+    before the first launch)."""
+    from autourdf_amd import _lib
+    lib = _lib.load(check_device=False)
+    EINVAL = -1
+    p, big = ctypes.c_void_p(0x1000), 1 << 40
+
+    def refused(rc, *words):
+        text = lib.creg_last_error().decode()
+        assert rc == EINVAL and all(w in text for w in words), (rc, text, words)
+
+    def problem(**null):
+        fields = {name: (None if name in null else p) for name, _ in _lib.IcpProblem._fields_}
+        fields["tgt_offsets"] = fields["world_offsets"] = None
+        return _lib.IcpProblem(**fields)
+
+    def batch(probs, nbatch=None, n=100, k=2, nf=100, max_it=10, ws=p, ws_bytes=big):
+        arr = (_lib.IcpProblem * max(len(probs), 1))(*probs)
+        return lib.creg_masked_icp_batch_f64(arr if probs else None, len(probs) if nbatch is None else nbatch, n, k, nf, 1.2, 1.0, max_it, 0, ws, ws_bytes, None)
+
+    def single(n=100, k=2, nf=100, max_it=10, local=p, ws=p, ws_bytes=big):
+        return lib.creg_masked_icp_f64(local, p, None, n, p, k, p, nf, p, 1.2, 1.0, max_it, 0, p, p, p, ws, ws_bytes, None)
+
+    def p2p(n=100, k=2, m=100, max_it=10, src=p, toff=p, ws=p, ws_bytes=big):
+        return lib.creg_icp_p2p_f64(src, n, p, p, m, toff, k, p, 1.0, max_it, p, p, p, ws, ws_bytes, None)
+
+    who = "creg_masked_icp_batch_f64"
+    refused(batch([]), who, "null pointer")                                        # a null problem pointer
+    refused(batch([problem()], ws=None), who, "null pointer")
+    refused(batch([problem()], nbatch=0), who, "batch must be in 1..16")
+    refused(batch([problem()] * 17), who, "batch must be in 1..16")
+    refused(batch([problem()], n=0), who, "no source points")
+    refused(batch([problem()], max_it=0), who, "bad size")
+    refused(batch([problem()], k=0), who, "bad size")
+    need = lib.creg_icp_batch_workspace_bytes(100, 100, 2, 2)
+    refused(batch([problem()] * 2, ws_bytes=need - 1), who, "workspace too small", str(need))
+    refused(batch([problem(), problem(M_out=1)]), who, "null pointer in problem 1")
+    refused(batch([problem(frame=1), problem()]), who, "null pointer in problem 0")
+    for n, k, nf in ((100, 2, 100), (2050, 2, 500)):                              # one workgroup per cluster | many workgroups
+        need = lib.creg_icp_workspace_bytes(n, nf, k)
+        who = "creg_masked_icp_f64"
+        refused(single(n=0, k=k, nf=nf), who, "no source points")
+        refused(single(n=n, k=k, nf=nf, max_it=0), who, "bad size")
+        refused(single(n=n, k=k, nf=nf, ws=None), who, "null pointer")
+        refused(single(n=n, k=k, nf=nf, ws_bytes=need - 1), who, "workspace too small", str(need))
+        refused(single(n=n, k=k, nf=nf, local=None), who, "null pointer in problem 0")
+        who = "creg_icp_p2p_f64"
+        refused(p2p(n=0, k=k, m=nf), who, "no source points")
+        refused(p2p(n=n, k=k, m=nf, max_it=0), who, "bad size")
+        refused(p2p(n=n, k=k, m=nf, toff=None), who, "null pointer")
+        refused(p2p(n=n, k=k, m=nf, ws_bytes=need - 1), who, "workspace too small", str(need))
+        refused(p2p(n=n, k=k, m=nf, src=None), who, "null pointer in problem 0")
+    for args in ((None, p, 2, p, 100, 1.2, p, p, p, None), (p, p, 0, p, 100, 1.2, p, p, p, None), (p, p, 2, p, 0, 1.2, p, p, p, None),
+                 (p, p, 2, p, 1 << 31, 1.2, p, p, p, None), (p, p, 2, p, 100, 1.2, None, p, p, None), (p, p, 2, p, 100, 1.2, p, None, p, None)):
+        refused(lib.creg_aabb_mask_f64(*args), "creg_aabb_mask_f64", "bad argument")
+    refused(lib.creg_kabsch_f64(None, p, None, 10, p, 1, p, None), "creg_kabsch_f64", "null pointer")
+    refused(lib.creg_kabsch_f64(p, p, None, 10, p, 0, p, None), "creg_kabsch_f64", "bad size")
+
+
 def test_every_environment_variable_the_library_reads_is_documented():
     """Every getenv("CREG_...") of the library's sources has a row of its own in the "Environment" table of INTEGRATION.md."""
     csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
