@@ -1,4 +1,4 @@
-"""Debug build only (CREG_EXTRA_FLAGS=-DCREG_BD_STAMPS python autourdf_amd/build.py after touching train_engine.hip): where the two
+"""Debug build only (CREG_EXTRA_FLAGS=-DCREG_BD_STAMPS python autourdf_amd/build.py after touching train_backward.hip or train_dev.h, which hold the stamps): where the two
 roles of the train plan's backward launch k_bd spend a launch.  Runs bench.py's roofline leg (200 back-to-back launches of k_bd carrying
 the problems of the larger graph branch) and prints, per role, when its workgroups start and end inside the launch and the mean duration
 of each phase of a workgroup (100 MHz wall clock, thread 0 of every workgroup).  python tests/measure/bd_stamps.py [bench.py arguments]"""

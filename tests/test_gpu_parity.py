@@ -2112,6 +2112,83 @@ def test_train_plan_calls_leave_nothing_behind_for_the_next(dev, graph_branches)
             assert torch.equal(two, one) and torch.equal(one, three)
 
 
+def _three_cluster_problems(dev, batch, epochs):
+    """The shape of test_train_plan_calls_leave_nothing_behind_for_the_next (K = 3, 64 points per cluster, hidden 64, 'q'), every
+    problem with a target and weights of its own.  Returns (K, n, m, pts, off, ys, mk) with mk(b) = fresh copies of problem b's
+    parameters, after checking on the float32 oracle that none of the trains stops before `epochs` (the comparisons below are of
+    full runs)."""
+    from autourdf_amd import ops
+    from oracle import models, registration
+    rng = np.random.default_rng(11)
+    K, per = 3, 64
+    centres = np.array([[0.0, 0.0, 0.0], [0.3, 0.1, 0.0], [0.1, 0.4, 0.2]])
+    cl = [rng.normal(size=(per, 3)) * 0.05 for _ in range(K)]
+    mats = np.tile(np.eye(4), (K, 1, 1))
+    mats[:, :3, 3] = centres
+    world = np.concatenate([c + t for c, t in zip(cl, centres)])
+    clusters = [torch.tensor(c, dtype=torch.float32) for c in cl]
+    m_host = torch.tensor(mats, dtype=torch.float32)
+    ys_host = [torch.tensor(world @ _rot_z(0.02).T + 0.001 * (b + 1), dtype=torch.float32) for b in range(batch)]
+    sds = []
+    for b in range(batch):
+        torch.manual_seed(5 + b)
+        sds.append(models.QRegMLP(True, 64).state_dict())
+        model = models.QRegMLP(True, 64)
+        model.load_state_dict(sds[b])
+        _, _, _, hist = registration.train(m_host, ys_host[b], model, clusters, rot="q", epochs=epochs)
+        assert len(hist["loss"]) == epochs, (b, len(hist["loss"]))
+    pts, off = ops.pack_clusters(clusters, dev)
+    mk = lambda b: [sds[b][kk].clone().to(dev) for kk in ops.Q_PARAM_ORDER]
+    return K, K * per, m_host.to(dev), pts, off, [y.to(dev) for y in ys_host], mk
+
+
+def _assert_batch_equals_single_runs(outs, params, single_runs, epochs):
+    for b, (out, par, (out1, par1)) in enumerate(zip(outs, params, single_runs)):
+        assert int(out[2][1]) == epochs and int(out1[2][1]) == epochs, b            # result[1] = epochs_run: full runs
+        assert len(out) == len(out1) == 5 and len(par) == len(par1) == 10
+        for got, want in zip(list(out) + par, list(out1) + par1):
+            assert torch.equal(got, want), b
+
+
+def test_batch_of_14_flushes_both_copy_tables_and_equals_14_single_plans(dev):
+    """A batch of 14 against 14 single-problem plans, 4 epochs (one graph): every output and every trained parameter bit-identical.
+    The input copy table holds 14 x 11 = 154 ranges and the output table 14 x 15 = 210: both cross COPY_MAX = 150 and flush in
+    the middle of the batch (no other test goes above a batch of 8).  14 problems take three chains."""
+    from autourdf_amd import ops
+    batch, epochs = 14, 4
+    K, n, m, pts, off, ys, mk = _three_cluster_problems(dev, batch, epochs)
+    plan = ops.TrainPlan("q", K, 64, n, n, epochs=epochs, use_graph=True, device=dev, batch=batch)
+    assert plan.info["graph_branches"] == 3
+    params = [mk(b) for b in range(batch)]
+    outs = plan.run_batch([(m, ys[b], pts, off, params[b]) for b in range(batch)])
+    singles = []
+    for b in range(batch):
+        p1 = mk(b)
+        singles.append((ops.TrainPlan("q", K, 64, n, n, epochs=epochs, use_graph=True, device=dev).run(m, ys[b], pts, off, p1), p1))
+    _assert_batch_equals_single_runs(outs, params, singles, epochs)
+    assert not torch.equal(outs[0][0], outs[13][0])
+
+
+@pytest.mark.parametrize("epochs", [1, 2, 3, 51])
+def test_chain_streams_at_every_split_of_graph_and_eager_epochs_equal_eager_single_runs(dev, epochs):
+    """Batch 5 on the default chains (two chain streams) with use_graph against eager single runs, bit-identical: 1 epoch = no graph
+    at all, 2 = exactly one graph, 3 = a graph plus an eager tail on every chain, 51 = the default 50-epoch graph plus one eager
+    epoch."""
+    from autourdf_amd import ops
+    batch = 5
+    K, n, m, pts, off, ys, mk = _three_cluster_problems(dev, batch, epochs)
+    plan = ops.TrainPlan("q", K, 64, n, n, epochs=epochs, use_graph=True, device=dev, batch=batch)
+    assert plan.info["graph_branches"] == 2
+    params = [mk(b) for b in range(batch)]
+    outs = plan.run_batch([(m, ys[b], pts, off, params[b]) for b in range(batch)])
+    eager = ops.TrainPlan("q", K, 64, n, n, epochs=epochs, use_graph=False, device=dev)
+    singles = []
+    for b in range(batch):
+        p1 = mk(b)
+        singles.append((eager.run(m, ys[b], pts, off, p1), p1))
+    _assert_batch_equals_single_runs(outs, params, singles, epochs)
+
+
 def test_masked_icp_launch_timing_changes_no_result(dev):
     """The many-workgroup ICP with its launch-timing hook on (icp_nn_counters(timing=True): two events around every search launch,
     read and released at the end of the call) against the same call with it off: same poses, points and iteration counts, and the

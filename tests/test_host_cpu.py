@@ -174,6 +174,104 @@ def test_icp_entries_refuse_bad_arguments_before_any_device_call():
     refused(lib.creg_kabsch_f64(p, p, None, 10, p, 0, p, None), "creg_kabsch_f64", "bad size")
 
 
+def _train_shape(rot=0, hidden=64, k=20, n_pred=4096, n_tgt=4096, nn_search=0, batch=1):
+    from autourdf_amd import _lib
+    return _lib.TrainShape(rot=rot, k=k, hidden=hidden, epochs=300, n_pred=n_pred, n_tgt=n_tgt, use_graph=1, batch=batch,
+                           graph_branches=0, nn_search=nn_search)
+
+
+def test_train_workspace_sizes_are_pinned_across_the_layout_switches(monkeypatch):
+    """creg_train_workspace_bytes is pure host arithmetic (make_dims + carve): every pose representation at both ends of the hidden
+    widths; k on both sides of the KP rounding (20 | 21, 40) and at 1; n_tgt where the points per lane switch (4096 | 4097), where
+    the sixteen-queries search and the one-chunk sort end (16384 | 16385) and where the pruned search ends (65536 | 65537), under
+    each nn_search; n_pred on both sides of the PS_MAXB block bound (31488 | 31489 at 64-point blocks and k = 20) and of the 16-bit
+    index bound (65534 | 65535); batch 0, 1, 5, 64.  300 epochs.  The numbers are those of the library before train_engine.hip was
+    split; callers' allocations depend on them.  CREG_NN_ROWS changes the layout and is unset here."""
+    from autourdf_amd import _lib
+    monkeypatch.delenv("CREG_NN_ROWS", raising=False)
+    lib = _lib.load(check_device=False)
+    size = lambda **kw: lib.creg_train_workspace_bytes(ctypes.byref(_train_shape(**kw)))
+    by_rot_hidden = {(0, 64): 788992, (0, 512): 7673856, (1, 64): 759296, (1, 512): 5597696, (2, 64): 808704, (2, 512): 7822592,
+                     (3, 64): 779008, (3, 512): 7599360}
+    for (rot, hidden), want in by_rot_hidden.items():
+        assert size(rot=rot, hidden=hidden) == want, (rot, hidden)
+    for k, want in {1: 740864, 20: 788992, 21: 826880, 40: 875008, 256: 1818112}.items():
+        assert size(k=k) == want, k
+    by_n_tgt = {   # n_tgt: bytes at nn_search 0, 1, 2
+        4096: (788992, 554496, 788992), 4097: (793600, 564224, 916480), 16384: (1191424, 761856, 1306624),
+        16385: (1312768, 762368, 1312768), 65536: (2890240, 1554432, 2890240), 65537: (1554944, 1554944, 1554944)}
+    for n_tgt, want in by_n_tgt.items():
+        assert tuple(size(n_tgt=n_tgt, nn_search=s) for s in (0, 1, 2)) == want, n_tgt
+    by_n_pred = {   # (n_pred, n_tgt): bytes at nn_search 0, 2
+        (31488, 4096): (3431424, 3431424), (31489, 4096): (2376960, 2376960), (31488, 16384): (3836928, 3941376),
+        (31489, 16384): (3950848, 3950848), (65534, 16384): (7217152, 7217152), (65535, 16384): (4959744, 4959744)}
+    for (n_pred, n_tgt), want in by_n_pred.items():
+        assert tuple(size(n_pred=n_pred, n_tgt=n_tgt, nn_search=s) for s in (0, 2)) == want, (n_pred, n_tgt)
+    for batch, want in {0: 788992, 1: 788992, 5: 3944960, 64: 50495488}.items():
+        assert size(batch=batch) == want, batch
+    assert size(rot=2, hidden=512, k=193) == 10694144
+    assert lib.creg_train_workspace_bytes(None) == 0
+
+
+def test_train_workspace_is_zero_bytes_for_a_shape_outside_the_plan(monkeypatch):
+    """Shapes creg_train_workspace_bytes must answer with 0: batch 65, k 257, hidden 96, and '6d' at hidden 512 with k 194 --
+    the limit include/creg.h states (k <= 193 there; '6d' <= 227 at the narrower widths: k_bd's feature pieces).  The library
+    before train_engine.hip was split did not hold the first of the two (10696448 bytes at k 194); this one does."""
+    from autourdf_amd import _lib
+    monkeypatch.delenv("CREG_NN_ROWS", raising=False)
+    lib = _lib.load(check_device=False)
+    size = lambda **kw: lib.creg_train_workspace_bytes(ctypes.byref(_train_shape(**kw)))
+    assert size(batch=65) == 0 and size(batch=-1) == 0
+    assert size(k=257) == 0 and size(k=0) == 0
+    assert size(hidden=96) == 0
+    assert size(rot=2, hidden=64, k=228) == 0 and size(rot=2, hidden=256, k=228) == 0 and size(rot=2, hidden=256, k=227) > 0
+    assert size(rot=2, hidden=512, k=194) == 0 and size(rot=2, hidden=512, k=227) == 0 and size(rot=2, hidden=512, k=193) > 0
+    assert size(rot=0, hidden=512, k=194) > 0 and size(rot=1, hidden=512, k=256) > 0          # the other representations: up to 256
+
+
+def test_train_plan_entries_refuse_bad_arguments_before_any_device_call():
+    """creg_train_plan_create answers a bad argument with CREG_EINVAL and its own name; so do run_batch, resume, probe and profile
+    on a null plan.  Without a device a HIP call gives CREG_EHIP: what a create with everything in order then returns, the plan
+    freed again and the caller's pointer left alone.  The workspace is a made-up address that is never dereferenced."""
+    from autourdf_amd import _lib
+    lib = _lib.load(check_device=False)
+    EINVAL, EHIP = -1, -2
+    ws, big = ctypes.c_void_p(0x10000), 1 << 40
+
+    def refused(rc, *words):
+        text = lib.creg_last_error().decode()
+        assert rc == EINVAL and all(w in text for w in words), (rc, text, words)
+
+    def create(shape=None, ws=ws, ws_bytes=big, out=True):
+        plan = ctypes.c_void_p(0)
+        rc = lib.creg_train_plan_create(ctypes.byref(shape or _train_shape()), ws, ws_bytes, ctypes.byref(plan) if out else None)
+        assert (plan.value is None) == (rc != 0)                         # a failed create leaves the caller's pointer alone
+        if plan.value:
+            lib.creg_train_plan_destroy(plan)
+        return rc
+
+    who = "creg_train_plan_create"
+    refused(create(out=False), who, "null pointer")
+    refused(create(ws=None), who, "null pointer")
+    for bad in (_train_shape(hidden=96), _train_shape(k=257), _train_shape(rot=4), _train_shape(n_tgt=0)):
+        refused(create(bad), who, "unsupported shape")
+    refused(create(ws=ctypes.c_void_p(0x10080)), who, "256-byte aligned")
+    for batch in (-1, 65):
+        refused(create(_train_shape(batch=batch)), who, "batch must be in [0, 64]")
+    for shape in (_train_shape(), _train_shape(batch=5, n_tgt=16385)):
+        need = lib.creg_train_workspace_bytes(ctypes.byref(shape))
+        refused(create(shape, ws_bytes=need - 1), who, "workspace too small", str(need))
+        # everything in order: the first device call (k_bd's dynamic-LDS limit) fails without a device; with one the plan is made
+        assert create(shape, ws_bytes=need) == (EHIP if lib.creg_device_check() != 0 else 0)
+    args, state, us = _lib.TrainArgs(), _lib.TrainState(), (ctypes.c_float * 12)()
+    refused(lib.creg_train_plan_run_batch(None, ctypes.byref(args), 1, None), "creg_train_plan_run_batch", "null pointer")
+    refused(lib.creg_train_plan_run(None, ctypes.byref(args), None), "creg_train_plan_run_batch", "null pointer")
+    refused(lib.creg_train_plan_resume(None, ctypes.byref(args), ctypes.byref(state), 1, None, None, None, None), "creg_train_plan_resume", "null pointer")
+    refused(lib.creg_train_plan_probe(None, ctypes.byref(args), None, None, None, None, None), "creg_train_plan_probe", "null pointer")
+    refused(lib.creg_train_plan_profile(None, ctypes.byref(args), 1, us, None), "creg_train_plan_profile", "bad argument")
+    assert lib.creg_train_plan_destroy(None) == 0
+
+
 def test_every_environment_variable_the_library_reads_is_documented():
     """Every getenv("CREG_...") of the library's sources has a row of its own in the "Environment" table of INTEGRATION.md."""
     csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
