@@ -109,6 +109,9 @@ SIGNATURES = {
     "creg_link_poses_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, vp, vp]),
     "creg_joint_positions_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "creg_motion_error_f64": (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]),
+    "creg_joint_types_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, f64, f64, vp, vp, vp, vp, vp,
+                                            vp, vp, vp, vp]),
+    "creg_joint_slides_f64": (ctypes.c_int, [vp, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "creg_statistical_outlier_f64": (ctypes.c_int, [vp, i64, vp, i32, i32, f64, vp, vp, vp, vp]),
     "creg_voxel_bounds_f64": (ctypes.c_int, [vp, i64, vp, i32, vp, f64, vp, vp, vp, vp]),
     "creg_voxel_layout": (ctypes.c_int, [vp, vp, i32, vp]),

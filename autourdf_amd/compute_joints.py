@@ -11,6 +11,10 @@ are the kernel's closed forms restated on the host for a single joint (4x4 produ
 The axis sign follows creg.h's convention: the first usable sample of a joint has a positive angle (the reference's
 sign follows np.linalg.eig, so the two agree up to one sign per joint).  ``visualize_urdf`` (pybullet GUI) is out of
 scope.  No CPU fallback.
+
+This project's own, beyond the reference: ``estimate_typed_joints_from_tree`` also tells prismatic and fixed joints
+(``creg_joint_types_f64``), and ``estimate_joint_motion``, ``set_joint_limits`` and ``replay_urdf`` recover every joint's
+positions, write the observed limits and check the written file against the registration.
 """
 import os
 import xml.etree.ElementTree as ET
@@ -144,6 +148,50 @@ def estimate_joint_axes_from_tree(links, cm_list, start_step=0, num_steps=500, i
     return joint_data
 
 
+JOINT_TYPE_NAMES = {0: "fixed", 1: "revolute", 2: "prismatic"}       # urdf_fk's numbering
+JOINT_UNITS = {"revolute": "rad", "prismatic": "length", "fixed": None}   # "length": the clouds' own unit
+
+
+def estimate_typed_joints_from_tree(links, cm_list, start_step=0, num_steps=500, interval=1, slide_min=None, turn_min=None):
+    """``estimate_joint_axes_from_tree`` for trees whose joints may also slide or not move at all (this project's own): one
+    ``ops.joint_axes`` and one ``ops.joint_types`` launch over the same samples.  A sample turns when the child's relative
+    rotation reaches ``turn_min`` rad (None: ``ops.JOINT_THETA_MIN``), slides when it does not and the relative translation
+    reaches ``slide_min`` (the clouds' unit, required), and stands still otherwise; a joint with a turning sample is revolute,
+    else one with a sliding sample prismatic, else fixed.  Returns the reference's list of dicts plus "type" ("revolute" |
+    "prismatic" | "fixed") and "counts" (still, turn, slide, bad samples).  A revolute joint's other entries are those of
+    ``estimate_joint_axes_from_tree``; a prismatic joint's local_axis is the slide direction in the child's frame, its
+    local_pos (0,0,0,1) -- the joint point is the child's origin -- and global_axis / global_pos the same at sequence 0, step
+    ``start_step``; a fixed joint has the same point and a NaN axis.  ValueError for a joint without a finite sample, or for
+    a revolute one whose axis is undefined (possible only with ``turn_min`` below ``ops.JOINT_THETA_MIN``)."""
+    turn_min = ops.JOINT_THETA_MIN if turn_min is None else turn_min
+    by_id = {l["id"]: i for i, l in enumerate(links)}
+    pairs = [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+    coords, clusters = _coords(cm_list), [list(l["cluster_idx"]) for l in links]
+    kinds = ops.joint_types(coords, clusters, pairs, start_step, num_steps, interval, turn_min, slide_min)
+    axes = ops.joint_axes(coords, clusters, pairs, start_step, num_steps, interval)
+    res = {k: axes[k].cpu().numpy() for k in ("local_axis", "local_pos", "global_pos", "global_axis", "count")}
+    typ = {k: kinds[k].cpu().numpy() for k in ("type", "counts", "slide_axis", "global_axis", "global_pos")}
+    joint_data = []
+    for j, (p, c) in enumerate(pairs):
+        pid, cid = links[p]["id"], links[c]["id"]
+        if typ["type"][j] < 0:
+            raise ValueError(f"joint between parent link {pid} and child link {cid}: no sample with finite poses, its kind is "
+                             f"undefined")
+        name = JOINT_TYPE_NAMES[int(typ["type"][j])]
+        if name == "revolute":
+            if res["count"][j] == 0:
+                raise ValueError(f"joint between parent link {pid} and child link {cid}: no step turns the child by at least "
+                                 f"{ops.JOINT_THETA_MIN} rad relative to the parent, its axis is undefined")
+            jd = {k: res[k][j] for k in ("local_axis", "local_pos", "global_pos", "global_axis")}
+        else:
+            jd = {"local_axis": typ["slide_axis"][j], "local_pos": np.array([0.0, 0.0, 0.0, 1.0]),
+                  "global_pos": typ["global_pos"][j], "global_axis": typ["global_axis"][j]}
+        print(f"Joint between parent link {pid} and child link {cid}: {name}, axis {jd['local_axis']}")
+        joint_data.append({"parent_link": pid, "child_link": cid, **jd, "type": name,
+                           "counts": [int(x) for x in typ["counts"][j]]})
+    return joint_data
+
+
 def link_transforms(links, cm, time_step=0):
     """create_urdf's per-link transform (compute_joints.py:278-287): the float32 mean of the clusters' float32 matrices
     at time_step, from creg_link_clouds_f64 (no points)."""
@@ -160,7 +208,12 @@ def link_transforms(links, cm, time_step=0):
 
 def create_urdf(links, joint_data, cm, output_file="robot.urdf", mesh_dir="", time_step=0):
     """Write the estimated robot as URDF (compute_joints.py:274-388): same elements, names, attributes, mesh paths,
-    layout and XML declaration."""
+    layout and XML declaration.  A joint dict may carry "type" (``estimate_typed_joints_from_tree``; without the key the joint
+    is revolute and every byte the reference's): "prismatic" writes the same origin and axis expressions with
+    <limit ... lower="0.0" upper="0.0"> for ``set_joint_limits`` to fill, "fixed" the origin alone."""
+    for joint in joint_data:
+        if joint.get("type", "revolute") not in JOINT_UNITS:
+            raise ValueError(f"joint_{joint['child_link']}: unknown joint type {joint['type']!r}")
     robot = ET.Element("robot", name="estimated_robot")
     link_transforms_ = link_transforms(links, cm, time_step)
     link_pos_local = {}
@@ -192,20 +245,26 @@ def create_urdf(links, joint_data, cm, output_file="robot.urdf", mesh_dir="", ti
         ET.SubElement(inertial, "mass", value="1.0")
         ET.SubElement(inertial, "inertia", ixx="0.1", ixy="0.0", ixz="0.0", iyy="0.1", iyz="0.0", izz="0.1")
     for joint in joint_data:
-        joint_elem = ET.SubElement(robot, "joint", name=f"joint_{joint['child_link']}", type="revolute")
+        kind = joint.get("type", "revolute")
+        joint_elem = ET.SubElement(robot, "joint", name=f"joint_{joint['child_link']}", type=kind)
         ET.SubElement(joint_elem, "parent", link=f"link_{joint['parent_link']}")
         ET.SubElement(joint_elem, "child", link=f"link_{joint['child_link']}")
         parent_transform = link_transforms_[joint["parent_link"]]
         child_transform = link_transforms_[joint["child_link"]]
         local_pos = np.linalg.inv(parent_transform) @ np.append(joint["global_pos"], 1)
         origin_xyz = " ".join(map(str, local_pos[:3] + link_pos_local[joint["parent_link"]]))
-        local_axis = np.linalg.inv(parent_transform[:3, :3]) @ np.append(joint["global_axis"], 0)[:3]
-        local_axis = local_axis / np.linalg.norm(local_axis)
         relative_rot = np.linalg.inv(parent_transform[:3, :3]) @ child_transform[:3, :3]
         origin_rpy = " ".join(map(str, R.from_matrix(relative_rot).as_euler("xyz")))
         ET.SubElement(joint_elem, "origin", xyz=origin_xyz, rpy=origin_rpy)
+        if kind == "fixed":                                       # no axis, no limit
+            continue
+        local_axis = np.linalg.inv(parent_transform[:3, :3]) @ np.append(joint["global_axis"], 0)[:3]
+        local_axis = local_axis / np.linalg.norm(local_axis)
         ET.SubElement(joint_elem, "axis", xyz=" ".join(map(str, local_axis)))
-        ET.SubElement(joint_elem, "limit", effort="100", velocity="100", lower="-3.14159", upper="3.14159")
+        if kind == "prismatic":                                   # no placeholder range: set_joint_limits writes the observed one
+            ET.SubElement(joint_elem, "limit", effort="100", velocity="100", lower="0.0", upper="0.0")
+        else:
+            ET.SubElement(joint_elem, "limit", effort="100", velocity="100", lower="-3.14159", upper="3.14159")
     tree = ET.ElementTree(robot)
     ET.indent(tree, space="  ", level=0)
     if os.path.dirname(output_file):
@@ -268,21 +327,43 @@ def estimate_joint_motion(links, joint_data, cm_list, start_step=0, num_steps=50
     each sequence, lower, upper (the observed range), lower_at, upper_at ((sequence, step) of each, None without a usable
     sample), tilt_rms, tilt_max (rad: the rotation the axis does not explain), slip_rms, slip_max (how far the joint point
     moves in the child's frame) and n_used (samples with finite figures).  No figure is turned into a verdict.  IndexError
-    for steps past T, as numpy indexing would raise."""
+    for steps past T, as numpy indexing would raise.
+    Typed ``joint_data`` (``estimate_typed_joints_from_tree``): the revolute joints go through ``ops.joint_positions`` and the
+    prismatic and fixed ones through ``ops.joint_slides`` -- a fixed joint with a zero axis -- one call of each kind at most,
+    merged in ``joint_data``'s order.  A prismatic joint's positions, lower and upper are slides in the clouds' unit, its tilt
+    the whole relative rotation and its slip the motion off the axis; a fixed joint's positions are zero.  Every dict then
+    also carries "type" and "unit" ("rad", "length" for the clouds' unit, None for a fixed joint)."""
     by_id = {l["id"]: i for i, l in enumerate(links)}
     pairs = [(by_id[j["parent_link"]], by_id[j["child_link"]]) for j in joint_data]
     link_T = ops.link_poses(_coords(cm_list), [list(l["cluster_idx"]) for l in links])
-    out = ops.joint_positions(link_T, pairs, np.array([j["local_axis"] for j in joint_data], np.float64).reshape(-1, 3),
-                              np.array([np.asarray(j["local_pos"], np.float64)[:3] for j in joint_data]).reshape(-1, 3),
-                              0, time_step, start_step, num_steps)
-    res = {k: v.cpu().numpy() for k, v in out.items()}
+    typed = any("type" in j for j in joint_data)
+    kinds = [j.get("type", "revolute") for j in joint_data]
+    turning = [i for i, k in enumerate(kinds) if k == "revolute"]
+    sliding = [i for i, k in enumerate(kinds) if k != "revolute"]
+    res = [None] * len(joint_data)                                 # per joint: its row of whichever call took it
+    if turning or not sliding:
+        out = ops.joint_positions(link_T, [pairs[i] for i in turning],
+                                  np.array([joint_data[i]["local_axis"] for i in turning], np.float64).reshape(-1, 3),
+                                  np.array([np.asarray(joint_data[i]["local_pos"], np.float64)[:3] for i in turning]).reshape(-1, 3),
+                                  0, time_step, start_step, num_steps)
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        for row, i in enumerate(turning):
+            res[i] = {k: v[row] for k, v in out.items()}
+    if sliding:
+        axes = np.array([joint_data[i]["local_axis"] if kinds[i] == "prismatic" else np.zeros(3) for i in sliding], np.float64)
+        out = ops.joint_slides(link_T, [pairs[i] for i in sliding], axes.reshape(-1, 3), 0, time_step, start_step, num_steps)
+        out = {k: v.cpu().numpy() for k, v in out.items()}
+        for row, i in enumerate(sliding):
+            res[i] = {k: v[row] for k, v in out.items()}
     motion = []
     for j, jd in enumerate(joint_data):
-        used = int(res["n_used"][j])
+        used = int(res[j]["n_used"])
         at = lambda a: (int(a[0]), int(start_step + a[1])) if used else None
-        m = {"parent_link": jd["parent_link"], "child_link": jd["child_link"], "positions": res["q"][j],
-             "lower_at": at(res["lower_at"][j]), "upper_at": at(res["upper_at"][j]), "n_used": used}
-        m.update({k: float(res[k][j]) for k in ("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")})
+        m = {"parent_link": jd["parent_link"], "child_link": jd["child_link"], "positions": res[j]["q"],
+             "lower_at": at(res[j]["lower_at"]), "upper_at": at(res[j]["upper_at"]), "n_used": used}
+        m.update({k: float(res[j][k]) for k in ("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")})
+        if typed:
+            m.update(type=kinds[j], unit=JOINT_UNITS[kinds[j]])
         motion.append(m)
     return motion
 
@@ -293,7 +374,9 @@ def set_joint_limits(urdf_file, motion, pad=0.0):
     zero pose stays inside the limits.  A joint whose padded span reaches 2 pi becomes type="continuous" and loses lower and
     upper.  Effort, velocity, every other element, the indentation and the XML declaration stay as ``create_urdf`` wrote them.
     KeyError for a joint the file does not have, ValueError for one without a <limit>, with n_used = 0 or a negative pad;
-    nothing is written in either case."""
+    nothing is written in either case.  A motion dict may carry "type" (``estimate_joint_motion`` on typed joints): a
+    prismatic joint gets lower = min(lower, 0), upper = max(upper, 0) in the clouds' unit -- ``pad`` is an angle and leaves it
+    alone -- and never becomes continuous; a fixed joint has no limit and is skipped."""
     pad = float(pad)
     if not pad >= 0.0:
         raise ValueError(f"set_joint_limits: pad must be >= 0 rad, got {pad}")
@@ -303,14 +386,18 @@ def set_joint_limits(urdf_file, motion, pad=0.0):
     for m in motion:
         name = f"joint_{m['child_link']}"
         joint = by_name[name]
+        kind = m.get("type", "revolute")
+        if kind == "fixed":
+            continue
         limit = joint.find("limit")
         if limit is None:
             raise ValueError(f"{urdf_file}: joint {name} has no <limit> to rewrite")
         if m["n_used"] == 0 or not (np.isfinite(m["lower"]) and np.isfinite(m["upper"])):
             raise ValueError(f"{urdf_file}: joint {name} has no usable sample, its range is undefined")
-        todo.append((joint, limit, min(float(m["lower"]) - pad, 0.0), max(float(m["upper"]) + pad, 0.0)))
-    for joint, limit, lower, upper in todo:
-        if upper - lower >= 2.0 * np.pi:
+        own_pad = pad if kind == "revolute" else 0.0               # the pad is an angle
+        todo.append((joint, limit, min(float(m["lower"]) - own_pad, 0.0), max(float(m["upper"]) + own_pad, 0.0), kind))
+    for joint, limit, lower, upper, kind in todo:
+        if kind == "revolute" and upper - lower >= 2.0 * np.pi:
             joint.set("type", "continuous")
             for k in ("lower", "upper"):
                 limit.attrib.pop(k, None)

@@ -388,19 +388,28 @@ def _cli_parser():
     inertial blocks from those meshes (each overrides parameters.json's key of the same name); --joint_limits estimates
     every joint's positions, writes the observed range as its limits and replays the sequences on the URDF, --limit_pad
     (degrees, default 0) widens that range.  --limit_pad without --joint_limits is a usage error.  --collision_hull writes
-    every link's convex hull next to its mesh and names it in the URDF's <collision> blocks."""
+    every link's convex hull next to its mesh and names it in the URDF's <collision> blocks.  --joint_types tells revolute,
+    prismatic and fixed joints apart: --slide_min (the clouds' unit, required with it) and --turn_min (rad, default 2e-4)
+    are its two thresholds.  --joint_types without --joint_limits, and a threshold without --joint_types, are usage errors."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
     parser.add_argument('--joint_limits', action='store_true')
     parser.add_argument('--limit_pad', type=float, default=None)
     parser.add_argument('--collision_hull', action='store_true')
+    parser.add_argument('--joint_types', action='store_true')
+    parser.add_argument('--slide_min', type=float, default=None)
+    parser.add_argument('--turn_min', type=float, default=None)
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
         ns = parse(args, namespace)
         if ns.limit_pad is not None and not ns.joint_limits:
             parser.error("--limit_pad needs --joint_limits")
+        if ns.joint_types and not ns.joint_limits:
+            parser.error("--joint_types needs --joint_limits: a prismatic joint has no placeholder range")
+        if (ns.slide_min is not None or ns.turn_min is not None) and not ns.joint_types:
+            parser.error("--slide_min and --turn_min need --joint_types")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -408,7 +417,8 @@ def _cli_parser():
 
 def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
     """Write <name>.joint_motion.json (per-joint and per-link figures) and <name>.joint_positions.npy (J,S,steps) next to
-    the URDF and print one line per joint plus the worst replayed link."""
+    the URDF and print one line per joint plus the worst replayed link.  Typed joints (``--joint_types``) carry their "type"
+    and "unit" into the file, and their lines name the type and give a prismatic joint's range in the clouds' unit."""
     import json
     stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
     np.save(stem + '.joint_positions.npy', np.array([m["positions"] for m in motion], np.float64))
@@ -418,8 +428,14 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
                    "joints": joints, "links": replay}, f, indent=1,
                   default=lambda o: o.item() if hasattr(o, "item") else str(o))     # numpy scalars (link ids)
     for m in motion:
-        print(f"joint_{m['child_link']} ({m['parent_link']} -> {m['child_link']}): {np.degrees(m['lower']):.2f} .. "
-              f"{np.degrees(m['upper']):.2f} deg, tilt_rms {m['tilt_rms']:.3g} rad, slip_rms {m['slip_rms']:.3g}")
+        if "type" not in m:
+            print(f"joint_{m['child_link']} ({m['parent_link']} -> {m['child_link']}): {np.degrees(m['lower']):.2f} .. "
+                  f"{np.degrees(m['upper']):.2f} deg, tilt_rms {m['tilt_rms']:.3g} rad, slip_rms {m['slip_rms']:.3g}")
+            continue
+        span = {"revolute": f"{np.degrees(m['lower']):.2f} .. {np.degrees(m['upper']):.2f} deg",
+                "prismatic": f"{m['lower']:.6g} .. {m['upper']:.6g} length units", "fixed": "no motion"}[m["type"]]
+        print(f"joint_{m['child_link']} ({m['parent_link']} -> {m['child_link']}), {m['type']}: {span}, "
+              f"tilt_rms {m['tilt_rms']:.3g} rad, slip_rms {m['slip_rms']:.3g}")
     seen = [r for r in replay if r["n_used"]]
     if seen:
         w = max(seen, key=lambda r: r["rot_max"])
@@ -442,14 +458,20 @@ def main(argv=None):
     ``collision_hull`` key; the option wins) every link's exact convex hull is written as ``{i:04}_hull.stl`` and the URDF's
     ``<collision>`` blocks name it (``link_mesh(..., hull=True)``, ``set_collision_meshes``), one line per link is printed --
     triangles of the visual mesh -> triangles of the hull -- and the inertials stay computed from the visual meshes; without a
-    voxel size it is a ValueError before anything is written."""
+    voxel size it is a ValueError before anything is written.  With ``--joint_types`` (or a boolean ``joint_types`` key;
+    ``--slide_min`` / ``slide_min`` in the clouds' unit, ``--turn_min`` / ``turn_min`` in rad, the option wins) the joints
+    come from ``estimate_typed_joints_from_tree``: a child that never turns against its parent becomes a prismatic or a fixed
+    joint instead of a ValueError, the report names every joint's type and unit, and a prismatic joint's limits are its
+    observed slide.  It needs the joint limits and a ``slide_min``, and a threshold needs it: ValueError before anything is
+    written otherwise."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion, replay_urdf,
-                                 set_collision_meshes, set_inertials, set_joint_limits)
+    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
+                                 estimate_typed_joints_from_tree, replay_urdf, set_collision_meshes, set_inertials,
+                                 set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -471,6 +493,21 @@ def main(argv=None):
     limit_pad = 0.0 if limit_pad is None else float(limit_pad)
     if not limit_pad >= 0.0:
         raise ValueError(f"limit_pad must be >= 0 degrees, got {limit_pad}")
+    joint_types = bool(args.joint_types or robot_params.get('joint_types'))
+    slide_min = args.slide_min if args.slide_min is not None else robot_params.get('slide_min')
+    turn_min = args.turn_min if args.turn_min is not None else robot_params.get('turn_min')
+    if (slide_min is not None or turn_min is not None) and not joint_types:
+        raise ValueError("slide_min and turn_min are the thresholds of the joint types: give --joint_types (or a joint_types key "
+                         "in parameters.json) with them")
+    if joint_types and not joint_limits:
+        raise ValueError("joint types need the joint limits, a prismatic joint has no placeholder range: give --joint_limits "
+                         "(or a joint_limits key in parameters.json) with --joint_types")
+    if joint_types and slide_min is None:
+        raise ValueError("joint types need a slide_min, a length in the clouds' unit: give --slide_min (or a slide_min key in "
+                         "parameters.json) with --joint_types")
+    for name, value in (("slide_min", slide_min), ("turn_min", turn_min)):
+        if value is not None and not (np.isfinite(float(value)) and float(value) >= 0.0):
+            raise ValueError(f"{name} must be finite and >= 0, got {value}")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -513,7 +550,11 @@ def main(argv=None):
         cluster_idx, g1, _ = coord_clustering(cm_list[0].num_coords, sum_map, num_links=dof + 1)
 
     links = cm_list[0].kinematics_tree(g0, g1)
-    joint_data = estimate_joint_axes_from_tree(links, cm_list, START, END - START, 4)
+    if joint_types:
+        joint_data = estimate_typed_joints_from_tree(links, cm_list, START, END - START, 4, float(slide_min),
+                                                     None if turn_min is None else float(turn_min))
+    else:
+        joint_data = estimate_joint_axes_from_tree(links, cm_list, START, END - START, 4)
     sub_link_path = [link_path + path.split('/')[-2] + '/' for path in sub_part_path][:1]
     save_links(cm_list, cluster_idx, sub_link_path, START, END)
     refine_links_clusters(sub_link_path, START, END, dof)

@@ -1,5 +1,5 @@
 // joint_motion.hip -- what the registration knows about every joint beyond its axis, fp64 (this project's own; the
-// reference writes a placeholder limit and stops).  Three entries, creg.h has their contracts:
+// reference writes a placeholder limit and stops).  Four entries, creg.h has their contracts:
 //
 // Link poses (k_link_poses, one thread per (sequence, step, link)): link_mean_pose of joints_dev.h, the very pose
 // k_joint_axes works with, written as a rigid 4x4 in fp64.
@@ -14,6 +14,9 @@
 // kernel boundary; its sums go per thread in stride order, then the xor butterfly, then the waves in order -- an order
 // (S, num_steps) alone decides.  No atomics anywhere: two runs give the same bits, a joint alone the bits it gives
 // among others.  Both launches are latency-bound (J x S workgroups of a few hundred samples).
+//
+// Joint slides (k_slide_samples, then the same k_joint_summary): the same D read as a prismatic or a fixed joint -- the
+// slide along local_axis (a zero axis for a fixed joint), the whole rotation as tilt, the motion off the axis as slip.
 //
 // Motion error (k_motion_error, one thread per (pose, link)): how differently a link moved from its reference pose under
 // two descriptions, Ma = A A0^-1 against Mb = B B0^-1, as an angle and as the distance between the images of one point.
@@ -131,6 +134,33 @@ __global__ __launch_bounds__(JM_NT) void k_joint_samples(
             }
         }
         __syncthreads();                                          // the tile is free again
+    }
+}
+
+// The prismatic / fixed counterpart of k_joint_samples: the same D = X0^-1 X = [R d], read as a slide along `a`.  No
+// unwrap, so no serial pass: every thread writes its own three figures.
+__global__ __launch_bounds__(JM_NT) void k_slide_samples(
+    const double* __restrict__ link_T, int T, int L, const int32_t* __restrict__ joints, const double* __restrict__ local_axis,
+    int ref_seq, int ref_step, int start, int num_steps, int S, double* __restrict__ q, double* __restrict__ tilt,
+    double* __restrict__ slip) {
+    const int j = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    const int pl = joints[2 * j], cl = joints[2 * j + 1];
+    if (pl < 0 || pl >= L || cl < 0 || cl >= L) return;          // uniform: the joint is skipped, nothing of it is read or written
+    const double a[3] = {local_axis[3 * j], local_axis[3 * j + 1], local_axis[3 * j + 2]};
+    double t0[3], R0[9];
+    joint_pose(link_T + ((size_t)ref_seq * T + ref_step) * L * 16, pl, cl, t0, R0);
+    const size_t row = ((size_t)j * S + s) * num_steps;
+    for (int i = tid; i < num_steps; i += JM_NT) {
+        double tx[3], Rx[9], d[3], R[9];
+        joint_pose(link_T + ((size_t)s * T + (start + i)) * L * 16, pl, cl, tx, Rx);
+        child_in_parent(t0, R0, tx, Rx, d, R);                    // D = X0^-1 X
+        double v[3], c;
+        skew_and_cos(R, v, c);
+        const double u = (d[0] * a[0] + d[1] * a[1]) + d[2] * a[2];
+        const double e[3] = {d[0] - u * a[0], d[1] - u * a[1], d[2] - u * a[2]};
+        q[row + i] = u;
+        tilt[row + i] = atan2(norm3(v), c);                       // the whole rotation is unexplained
+        slip[row + i] = norm3(e);
     }
 }
 
@@ -267,6 +297,27 @@ extern "C" int creg_joint_positions_f64(const double* link_T, int32_t S, int32_t
                  "creg_joint_positions_f64: null pointer");
     hipLaunchKernelGGL(k_joint_samples, dim3(J, S), dim3(JM_NT), 0, (hipStream_t)stream, link_T, T, L, joints, local_axis, local_pos,
                        ref_seq, ref_step, start_step, num_steps, S, q, tilt, slip);
+    CREG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_joint_summary, dim3(J), dim3(JM_NT), 0, (hipStream_t)stream, q, tilt, slip, joints, L, S, num_steps, summary,
+                       where);
+    CREG_LAUNCH_CHECK();
+    return CREG_OK;
+}
+
+extern "C" int creg_joint_slides_f64(const double* link_T, int32_t S, int32_t T, int32_t L, const int32_t* joints, int32_t J,
+                                     const double* local_axis, int32_t ref_seq, int32_t ref_step, int32_t start_step,
+                                     int32_t num_steps, double* q, double* tilt, double* slip, double* summary, int32_t* where,
+                                     creg_stream_t stream) {
+    CREG_REQUIRE(S >= 1 && S <= 65535 && T >= 1 && L >= 1 && J >= 0, "creg_joint_slides_f64: bad size (S=%d, T=%d, L=%d, J=%d; S <= 65535)",
+                 S, T, L, J);
+    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && (int64_t)start_step + num_steps <= T && (int64_t)S * num_steps <= INT_MAX,
+                 "creg_joint_slides_f64: steps [%d, %d + %d) out of range for T=%d", start_step, start_step, num_steps, T);
+    CREG_REQUIRE(ref_seq >= 0 && ref_seq < S && ref_step >= 0 && ref_step < T,
+                 "creg_joint_slides_f64: reference pose (%d, %d) outside (S=%d, T=%d)", ref_seq, ref_step, S, T);
+    if (J == 0) return CREG_OK;
+    CREG_REQUIRE(link_T && joints && local_axis && q && tilt && slip && summary && where, "creg_joint_slides_f64: null pointer");
+    hipLaunchKernelGGL(k_slide_samples, dim3(J, S), dim3(JM_NT), 0, (hipStream_t)stream, link_T, T, L, joints, local_axis, ref_seq,
+                       ref_step, start_step, num_steps, S, q, tilt, slip);
     CREG_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_joint_summary, dim3(J), dim3(JM_NT), 0, (hipStream_t)stream, q, tilt, slip, joints, L, S, num_steps, summary,
                        where);

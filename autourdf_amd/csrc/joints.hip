@@ -113,21 +113,6 @@ __device__ void pose_to_f32_matrix(const double t[3], const double R[9], double 
     M[12] = 0.0; M[13] = 0.0; M[14] = 0.0; M[15] = 1.0;
 }
 
-// Sample r of a sequence -> (step_prev, step): phases a = 0..interval-1, then steps, as the reference's loops.
-__device__ void sample_steps(int r, int start, int num_steps, int interval, int& i0, int& i1) {
-    for (int a = 0; a < interval; ++a) {
-        const int na = a < num_steps ? (num_steps - a + interval - 1) / interval : 0;
-        const int ns = na > 1 ? na - 1 : 0;
-        if (r < ns) {
-            i1 = start + a + (r + 1) * interval;
-            i0 = i1 - interval;
-            return;
-        }
-        r -= ns;
-    }
-    i0 = i1 = start;                                      // unreachable: r < samples per sequence
-}
-
 __global__ __launch_bounds__(JA_NT) void k_joint_axes(
     const double* __restrict__ coords, int S, int T, int K, const int32_t* __restrict__ cl, const int32_t* __restrict__ off,
     int n_cl, const int32_t* __restrict__ joints, int start, int num_steps, int interval, int per_seq, int NS,

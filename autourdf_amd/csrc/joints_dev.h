@@ -1,6 +1,7 @@
-// joints_dev.h -- device helpers of the URDF stage's pose arithmetic, fp64, shared by joints.hip (joint axes, link clouds)
-// and joint_motion.hip (link poses, joint positions): the top eigenvector by cyclic Jacobi, a link's mean pose
-// (get_cluster_pose_mean), the child's pose in the parent's frame and a link's span of the flat cluster list.
+// joints_dev.h -- device helpers of the URDF stage's pose arithmetic, fp64, shared by joints.hip (joint axes, link clouds),
+// joint_types.hip (joint kinds) and joint_motion.hip (link poses, joint positions, slides): the top eigenvector by cyclic Jacobi, a link's mean pose
+// (get_cluster_pose_mean), the child's pose in the parent's frame, a link's span of the flat cluster list and the
+// enumeration of a joint's samples, which joint_types.hip shares with joints.hip.
 // quat_to_matrix is creg_dev.h's, which this header brings in.
 #pragma once
 #include <cstdint>
@@ -114,6 +115,21 @@ __device__ inline LinkSpan link_span(const int32_t* cl, const int32_t* off, int 
     a = a < 0 ? 0 : (a > n_cl ? n_cl : a);
     b = b < a ? a : (b > n_cl ? n_cl : b);
     return {cl + a, b - a};
+}
+
+// Sample r of a sequence -> (step_prev, step): phases a = 0..interval-1, then steps, as the reference's loops.
+__device__ inline void sample_steps(int r, int start, int num_steps, int interval, int& i0, int& i1) {
+    for (int a = 0; a < interval; ++a) {
+        const int na = a < num_steps ? (num_steps - a + interval - 1) / interval : 0;
+        const int ns = na > 1 ? na - 1 : 0;
+        if (r < ns) {
+            i1 = start + a + (r + 1) * interval;
+            i0 = i1 - interval;
+            return;
+        }
+        r -= ns;
+    }
+    i0 = i1 = start;                                      // unreachable: r < samples per sequence
 }
 
 }  // namespace creg

@@ -826,6 +826,62 @@ def joint_axes_prepare(coords: torch.Tensor, link_clusters, joints, start_step: 
     return launch, out
 
 
+def joint_types(coords: torch.Tensor, link_clusters, joints, start_step: int = 0, num_steps: int = 1, interval: int = 1,
+                turn_min: float = JOINT_THETA_MIN, slide_min=None):
+    """Which kind of joint every edge is, over joint_axes' samples, in one launch of creg_joint_types_f64.  coords,
+    link_clusters, joints and the steps as ``joint_axes``; a sample turns when its angle reaches turn_min (rad), slides when
+    it does not and its translation reaches slide_min, and stands still otherwise.  slide_min is a length in the clouds'
+    unit and has no default: None is a ValueError.  Returns a dict of device tensors: sample_angle (J,NS) f64 (the bits of
+    joint_axes'), sample_slide (J,NS,3) f64, sample_kind (J,NS) int32 (-1 bad, 0 still, 1 turn, 2 slide), counts (J,4) int32
+    (still, turn, slide, bad), type (J) int32 in urdf_fk's numbering (0 fixed, 1 revolute, 2 prismatic, -1 no finite sample),
+    slide_axis, global_axis, global_pos (J,3) f64.  The checks and errors are joint_axes', plus ValueError for a threshold
+    that is negative or not finite, all before any launch."""
+    if slide_min is None:
+        raise ValueError("joint_types: slide_min is a length in the clouds' unit and has no default, give one")
+    turn_min, slide_min = float(turn_min), float(slide_min)
+    if not (np.isfinite(turn_min) and turn_min >= 0.0 and np.isfinite(slide_min) and slide_min >= 0.0):
+        raise ValueError(f"joint_types: turn_min and slide_min must be finite and >= 0 (got {turn_min}, {slide_min})")
+    L_ = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    if coords.dim() != 4 or coords.shape[3] != 7:
+        raise ValueError("joint_types: coords must be (S,T,K,7)")
+    S, T, K = coords.shape[:3]
+    if K > LINK_SWEEP_MAX_K:
+        raise ValueError(f"joint_types supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+    start_step, num_steps, interval = int(start_step), int(num_steps), int(interval)
+    if start_step < 0 or num_steps < 1 or interval < 1:
+        raise ValueError(f"joint_types: need start_step >= 0, num_steps >= 1, interval >= 1 "
+                         f"(got {start_step}, {num_steps}, {interval})")
+    if start_step + num_steps > T:
+        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 0 with size {T}")
+    flat, off = _link_table(link_clusters, K, "joint_types")
+    L = len(off) - 1
+    jt = [(int(p), int(c)) for p, c in joints]
+    for p, c in jt:
+        if not (0 <= p < L and 0 <= c < L):
+            raise ValueError(f"joint_types: joint ({p}, {c}) names a link outside [0, {L})")
+    NS = joint_samples(S, num_steps, interval)
+    if NS > JOINT_MAX_SAMPLES:
+        raise ValueError(f"joint_types: {NS} samples per joint, at most {JOINT_MAX_SAMPLES} are supported")
+    dev, J = coords.device, len(jt)
+    i32 = dict(dtype=torch.int32, device=dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    out = {"sample_angle": torch.empty(J, NS, **f64), "sample_slide": torch.empty(J, NS, 3, **f64),
+           "sample_kind": torch.empty(J, NS, **i32), "counts": torch.empty(J, 4, **i32), "type": torch.empty(J, **i32),
+           "slide_axis": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
+           "global_pos": torch.empty(J, 3, **f64)}
+    if J:
+        cl = torch.tensor(flat, **i32)
+        lo = torch.tensor(off, **i32)
+        jn = torch.tensor(jt, **i32).reshape(-1, 2)
+        smp = (_p(out["sample_angle"]), _p(out["sample_slide"]), _p(out["sample_kind"])) if NS else (None, None, None)
+        _lib.check(L_.creg_joint_types_f64(_p(coords), S, T, K, _p(cl), _p(lo), len(flat), L, _p(jn), J, start_step, num_steps,
+                                           interval, turn_min, slide_min, *smp, _p(out["counts"]), _p(out["type"]),
+                                           _p(out["slide_axis"]), _p(out["global_axis"]), _p(out["global_pos"]), _stream()),
+                   "creg_joint_types_f64")
+    return out
+
+
 def link_clouds_bytes(n_points: int, n_out: int, T: int, K: int, L: int) -> int:
     """HBM traffic of one creg_link_clouds_f64 launch: points read, both clouds written, poses and offsets."""
     return 24 * n_points + 48 * n_out + T * K * (7 + 16) * 8 + (T * K + T * L + 2) * 8 + T * L * 2 * 64
@@ -963,6 +1019,54 @@ def joint_positions(link_T: torch.Tensor, joints, local_axis, local_pos, ref_seq
         _lib.check(L_.creg_joint_positions_f64(_p(link_T), S, T, L, _p(jn), J, _p(ax), _p(lp), ref_seq, ref_step, start_step,
                                                num_steps, _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()),
                    "creg_joint_positions_f64")
+    out = {"q": q, "tilt": tilt, "slip": slip}
+    for i, k in enumerate(("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")):
+        out[k] = summary[:, i]
+    out.update(n_used=where[:, 0], lower_at=where[:, 1:3], upper_at=where[:, 3:5])
+    return out
+
+
+def joint_slides(link_T: torch.Tensor, joints, local_axis, ref_seq: int = 0, ref_step: int = 0, start_step: int = 0,
+                 num_steps=None):
+    """``joint_positions`` for prismatic and fixed joints (creg_joint_slides_f64): q is the slide along local_axis (J,3), a
+    unit vector in the child's frame, or zero for a fixed joint; tilt is the whole rotation of the child against the
+    reference pose and slip the motion off the axis.  There is no local_pos and nothing is unwrapped.  Returns the dict
+    ``joint_positions`` returns and raises what it raises."""
+    L_ = _lib.load()
+    link_T = _need(link_T, torch.float64, "link_T")
+    if link_T.dim() != 5 or tuple(link_T.shape[3:]) != (4, 4) or 0 in link_T.shape[:3]:
+        raise ValueError(f"joint_slides: link_T must be (S,T,L,4,4) with S, T, L >= 1, got {tuple(link_T.shape)}")
+    S, T, L = link_T.shape[:3]
+    dev = link_T.device
+    jt = [(int(p), int(c)) for p, c in joints]
+    J = len(jt)
+    for p, c in jt:
+        if not (0 <= p < L and 0 <= c < L):
+            raise ValueError(f"joint_slides: joint ({p}, {c}) names a link outside [0, {L})")
+    ax = _need(torch.as_tensor(local_axis, dtype=torch.float64, device=dev).reshape(-1, 3), torch.float64, "local_axis")
+    if ax.shape[0] != J:
+        raise ValueError(f"joint_slides: local_axis must be ({J},3), got {tuple(ax.shape)}")
+    start_step, ref_seq, ref_step = int(start_step), int(ref_seq), int(ref_step)
+    num_steps = T - start_step if num_steps is None else int(num_steps)
+    if start_step < 0 or num_steps < 1:
+        raise ValueError(f"joint_slides: need start_step >= 0 and num_steps >= 1 (got {start_step}, {num_steps})")
+    if start_step + num_steps > T:
+        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 1 with size {T}")
+    if not 0 <= ref_seq < S:
+        raise IndexError(f"index {ref_seq} is out of bounds for axis 0 with size {S}")
+    if not 0 <= ref_step < T:
+        raise IndexError(f"index {ref_step} is out of bounds for axis 1 with size {T}")
+    if S > 65535 or S * num_steps >= 2 ** 31:
+        raise ValueError(f"joint_slides: at most 65535 sequences and 2^31 samples per joint (S={S}, num_steps={num_steps})")
+    f64 = dict(dtype=torch.float64, device=dev)
+    q, tilt, slip = (torch.empty(J, S, num_steps, **f64) for _ in range(3))
+    summary = torch.empty(J, 6, **f64)
+    where = torch.empty(J, 5, dtype=torch.int32, device=dev)
+    if J:
+        jn = torch.tensor(jt, dtype=torch.int32, device=dev).reshape(-1, 2)
+        _lib.check(L_.creg_joint_slides_f64(_p(link_T), S, T, L, _p(jn), J, _p(ax), ref_seq, ref_step, start_step, num_steps,
+                                            _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()),
+                   "creg_joint_slides_f64")
     out = {"q": q, "tilt": tilt, "slip": slip}
     for i, k in enumerate(("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")):
         out[k] = summary[:, i]

@@ -389,7 +389,55 @@ int creg_link_clouds_f64(const double* coords, const double* matrices, int32_t T
  * creg_motion_error_f64: one thread per (pose, link).  A, B (P,L,4,4), A0, B0 (L,4,4), point (L,3), fp64.
  *   Ma = A A0^-1 and Mb = B B0^-1 (rigid inverses: R = R_X R_X0^T, t = t_X - R t_X0).  rot_err (P,L) = atan2(|v(Rr)|, c(Rr))
  *   for Rr = R_Ma^T R_Mb; pos_err (P,L) = |Ma x - Mb x| for x = point[l].  The error is free of frames: it compares how a
- *   link moved from its reference pose under two descriptions, whatever frame each one attaches to the link.  P*L < 2^31. */
+ *   link moved from its reference pose under two descriptions, whatever frame each one attaches to the link.  P*L < 2^31.
+ *
+ * creg_joint_types_f64: which kind of joint every edge is -- the companion of creg_joint_axes_f64, with its launch shape
+ *   (one workgroup of 256 threads per joint, thread k taking samples k, k + 256, ...) and its samples (sequence-major,
+ *   then phase, then step; NS = creg_joint_axes_samples(S, num_steps, interval) <= 4096, K <= 256).  coords, links and
+ *   joints as there, plus L, the number of links (link_offsets holds L+1 entries).  turn_min (rad) and slide_min (the
+ *   clouds' unit) are finite and >= 0 (the host rejects anything else).
+ *   Per sample: D = X_{i-1}^-1 X_i = [R t] built exactly as creg_joint_axes_f64 builds it (the links' mean poses, X = P^-1 C
+ *   by the rigid inverse, then X_{i-1}^-1 X_i by the rigid inverse), theta = atan2(|v(R)|, c(R)) with
+ *   |v| = sqrt((v0 v0 + v1 v1) + v2 v2): the bits of creg_joint_axes_f64's sample_angle on the same input.  t is the
+ *   translation of D, in the child's frame at step i - interval, and |t| = sqrt((t0 t0 + t1 t1) + t2 t2).
+ *   Per sample (J,NS): sample_angle = theta, sample_slide (3) = t, sample_kind int32:
+ *     -1  theta or a component of t is not finite
+ *      1  (turn)   theta >= turn_min
+ *      2  (slide)  theta < turn_min and |t| >= slide_min
+ *      0  (still)  otherwise
+ *   Per joint: counts (J,4) int32 = n_still, n_turn, n_slide, n_bad;  type (J) int32 in creg_urdf_fk_f64's numbering:
+ *      1 (revolute) if n_turn > 0 -- with turn_min = 2e-4 exactly the joints creg_joint_axes_f64 gives count > 0 for
+ *      (finite outputs granted);  else 2 (prismatic) if n_slide > 0;  else 0 (fixed) if n_still > 0;  else -1 (no finite
+ *      sample, or NS = 0).
+ *   slide_axis (J,3) = the unit top eigenvector (cyclic Jacobi, ties: the first largest diagonal) of sum t t^T over the
+ *   slide samples, signed so that (a0 t0 + a1 t1) + a2 t2 >= 0 for the first slide sample in sample order (the convention
+ *   of local_axis); NaN when n_slide = 0.  The six sums run per thread in stride order, then the wave's xor butterfly
+ *   (offsets 32 .. 1), then the four waves in order.  No atomics on floating-point data: two runs give the same bits, a
+ *   joint alone the bits it gives among others.
+ *   global_axis (J,3) = R_child(sequence 0, step start_step) slide_axis (NaN with it);  global_pos (J,3) = the child's mean
+ *   position at that pose rounded to float32, as creg_joint_axes_f64's first-pose matrix holds it.  The joint point of a
+ *   prismatic or fixed joint is the child's origin: its local_pos is (0,0,0,1) by definition.
+ *   A joint whose link index is outside [0, L) is skipped: nothing of it is read or written.  J = 0 launches nothing.
+ *   With NS = 0 the per-sample outputs may be NULL and are not touched.  One launch, latency-bound.
+ *
+ * creg_joint_slides_f64: the prismatic / fixed counterpart of creg_joint_positions_f64.  link_T, joints, ref_seq, ref_step,
+ *   start_step, num_steps and their bounds as there; local_axis (J,3) in the child's frame, taken as a unit vector or, for
+ *   a fixed joint, as zero; there is no local_pos.  D = X0^-1 X(s,t) = [R d] as there.
+ *   Per sample (J,S,num_steps):
+ *     q    = (d0 a0 + d1 a1) + d2 a2: the slide along the axis; nothing is unwrapped.
+ *     tilt = atan2(|v(R)|, c(R)) >= 0: the whole rotation is unexplained.
+ *     slip = |d - q a|: the motion off the axis.  A fixed joint passes a = 0: q = 0 and slip = |d|.
+ *   Per joint: summary (J,6) and where (J,5) by the second launch of creg_joint_positions_f64, unchanged, in its layout.
+ *   A joint whose link index is outside [0, L) is skipped.  J = 0 launches nothing.  Two launches, both latency-bound. */
+int creg_joint_types_f64(const double* coords, int32_t S, int32_t T, int32_t K, const int32_t* link_clusters,
+                         const int32_t* link_offsets, int32_t n_link_clusters, int32_t L, const int32_t* joints, int32_t J,
+                         int32_t start_step, int32_t num_steps, int32_t interval, double turn_min, double slide_min,
+                         double* sample_angle, double* sample_slide, int32_t* sample_kind, int32_t* counts, int32_t* type,
+                         double* slide_axis, double* global_axis, double* global_pos, creg_stream_t stream);
+int creg_joint_slides_f64(const double* link_T, int32_t S, int32_t T, int32_t L, const int32_t* joints, int32_t J,
+                          const double* local_axis, int32_t ref_seq, int32_t ref_step, int32_t start_step,
+                          int32_t num_steps, double* q, double* tilt, double* slip, double* summary, int32_t* where,
+                          creg_stream_t stream);
 int creg_link_poses_f64(const double* coords, int32_t S, int32_t T, int32_t K, const int32_t* link_clusters,
                         const int32_t* link_offsets, int32_t n_link_clusters, int32_t L, double* link_T,
                         creg_stream_t stream);

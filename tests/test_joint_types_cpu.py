@@ -1,0 +1,237 @@
+"""No GPU: the two joint-type entry points are declared, bound and built; the command line's flags; the numpy restatement
+of their contracts (tests/_joint_types_ref.py) on the typed synthetic tree; create_urdf and set_joint_limits on typed
+joints."""
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+import _joint_motion_ref as M  # noqa: E402
+import _joint_types_ref as JT  # noqa: E402
+
+NAMES = {"creg_joint_types_f64": 24, "creg_joint_slides_f64": 17}
+
+
+@pytest.fixture(scope="module")
+def tree():
+    t = JT.typed_tree(S=2, T=20)
+    t["link_T"] = M.link_poses(t["coords"], t["link_clusters"])
+    t["ref"] = JT.joint_types(t["coords"], t["link_clusters"], t["joints"], 0, 20, 4, JT.TURN_MIN, JT.SLIDE_MIN)
+    return t
+
+
+# ------------------------------------------------------------------------------------------------ plumbing
+def test_symbols_are_declared_bound_and_built():
+    from autourdf_amd import _lib, build
+    header = open(os.path.join(ROOT, "include", "creg.h")).read()
+    assert "joint_types.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "joint_types.hip"))
+    L = ctypes.CDLL(build.build_lib())
+    for name, n_args in NAMES.items():
+        assert re.search(r"\b%s\s*\(" % name, header) and name in _lib.SIGNATURES
+        assert getattr(L, name) is not None
+        assert len(_lib.SIGNATURES[name][1]) == n_args
+        decl = re.search(r"int %s\(([^;]*)\);" % name, header).group(1)
+        assert decl.count(",") + 1 == n_args                                  # the header and the binding agree
+    assert _lib.load(check_device=False).creg_version() >= 1700
+    # the argument counts of the entries that were there stay
+    assert len(_lib.SIGNATURES["creg_joint_axes_f64"][1]) == 23 and len(_lib.SIGNATURES["creg_joint_positions_f64"][1]) == 18
+    # the header states the forms the kernels and the restatement share
+    assert "theta = atan2(|v(R)|, c(R))" in header and "q    = (d0 a0 + d1 a1) + d2 a2" in header
+    assert "slip = |d - q a|" in header and "n_still, n_turn, n_slide, n_bad" in header
+
+
+def test_sample_enumeration_is_shared():
+    hdr = open(os.path.join(ROOT, "autourdf_amd", "csrc", "joints_dev.h")).read()
+    assert re.search(r"__device__ inline void sample_steps\(", hdr)
+    for name in ("joints.hip", "joint_types.hip"):
+        src = open(os.path.join(ROOT, "autourdf_amd", "csrc", name)).read()
+        assert '#include "joints_dev.h"' in src and "sample_steps(" in src
+        assert not re.search(r"__device__ (inline )?void sample_steps\(", src)
+
+
+def test_ops_need_device_tensors_and_a_slide_min():
+    import torch
+    from autourdf_amd import ops
+    c = torch.zeros(1, 2, 2, 7, dtype=torch.float64)
+    with pytest.raises(RuntimeError):
+        ops.joint_types(c, [[0], [1]], [(0, 1)], 0, 2, 1, slide_min=1e-6)
+    with pytest.raises(RuntimeError):
+        ops.joint_slides(torch.zeros(1, 2, 2, 4, 4, dtype=torch.float64), [(0, 1)], np.zeros((1, 3)))
+    with pytest.raises(ValueError, match="slide_min"):
+        ops.joint_types(c, [[0], [1]], [(0, 1)], 0, 2, 1)
+    for bad in (dict(slide_min=-1.0), dict(slide_min=float("nan")), dict(slide_min=1e-6, turn_min=-1e-3),
+                dict(slide_min=1e-6, turn_min=float("inf"))):
+        with pytest.raises(ValueError, match="finite"):
+            ops.joint_types(c, [[0], [1]], [(0, 1)], 0, 2, 1, **bad)
+
+
+def test_command_line_flags():
+    import inspect
+    from autourdf_amd import compute_joints, coord_map
+    parse = coord_map._cli_parser().parse_args
+    args = parse(["--joint_limits", "--joint_types", "--slide_min", "1e-6", "--turn_min", "1e-3"])
+    assert args.joint_types and args.slide_min == 1e-6 and args.turn_min == 1e-3
+    args = parse(["--joint_limits", "--joint_types"])                        # the slide_min may come from parameters.json
+    assert args.joint_types and args.slide_min is None and args.turn_min is None
+    args = parse([])
+    assert args.joint_types is False and args.slide_min is None and args.turn_min is None
+    for bad in (["--joint_types", "--slide_min", "1e-6"], ["--slide_min", "1e-6"], ["--joint_limits", "--turn_min", "1e-3"],
+                ["--joint_limits", "--slide_min", "1e-6"]):
+        with pytest.raises(SystemExit):
+            parse(bad)
+    for flag in (["--joint_types"], ["--slide_min", "1e-6"], ["--turn_min", "1e-3"]):
+        with pytest.raises(SystemExit):
+            coord_map._parser().parse_args(flag)                             # not flags of the reference
+    est = inspect.signature(compute_joints.estimate_typed_joints_from_tree).parameters
+    assert list(est) == ["links", "cm_list", "start_step", "num_steps", "interval", "slide_min", "turn_min"]
+    assert [est[k].default for k in est if k not in ("links", "cm_list")] == [0, 500, 1, None, None]
+    assert list(inspect.signature(compute_joints.estimate_joint_axes_from_tree).parameters) == [
+        "links", "cm_list", "start_step", "num_steps", "interval"]
+    assert list(inspect.signature(compute_joints.create_urdf).parameters) == [
+        "links", "joint_data", "cm", "output_file", "mesh_dir", "time_step"]
+
+
+# ------------------------------------------------------------------------------------------------ the restatement
+def test_restatement_recovers_the_types_and_the_slide_axis(tree):
+    ref = tree["ref"]
+    assert JT.separation(ref)
+    assert [{v: k for k, v in JT.KINDS.items()}[int(x)] for x in ref["type"]] == tree["types"]
+    NS = ref["sample_kind"].shape[1]
+    assert NS == 2 * 16                                                       # 20 steps at interval 4: 4 phases of 4 samples
+    assert ref["counts"].tolist() == [[0, NS, 0, 0], [0, 0, NS, 0], [NS, 0, 0, 0], [0, NS, 0, 0]]
+    # every cluster's orientation is the identity at step 0, so the child's measured frame is the link's own
+    assert np.abs(ref["slide_axis"][JT.PRISMATIC] - tree["axes"][JT.PRISMATIC]).max() <= 1e-9
+    assert np.abs(ref["global_axis"][JT.PRISMATIC] - tree["axes"][JT.PRISMATIC]).max() <= 1e-9
+    assert np.isnan(ref["slide_axis"][[0, JT.FIXED, 3]]).all()
+    assert ref["sample_angle"][JT.PRISMATIC].max() <= 1e-6 and ref["sample_angle"][JT.FIXED].max() <= 1e-6
+    child = tree["link_T"][0, 0, [c for _, c in tree["joints"]], :3, 3]
+    assert np.array_equal(ref["global_pos"], child.astype(np.float32).astype(np.float64))
+    # the per-sample slides of the prismatic joint are the increments of its true positions along the axis
+    q = tree["q_true"][JT.PRISMATIC]
+    want = [q[s, i1] - q[s, i0] for s, i0, i1 in M.JR.sample_steps(2, 20, 4)]
+    np.testing.assert_allclose(ref["sample_slide"][JT.PRISMATIC] @ tree["axes"][JT.PRISMATIC], want, rtol=0, atol=1e-9)
+
+
+def test_restatement_thresholds_and_priority(tree):
+    args = (tree["coords"], tree["link_clusters"], tree["joints"], 0, 20, 4)
+    # a turn_min above every turn: the revolute joints' children also move, so their samples slide
+    high = JT.joint_types(*args, 10.0, JT.SLIDE_MIN)
+    assert high["type"].tolist() == [2, 2, 0, 2]
+    both = JT.joint_types(*args, 10.0, 10.0)
+    assert both["type"].tolist() == [0, 0, 0, 0] and np.isnan(both["slide_axis"]).all()
+    coords = tree["coords"].copy()
+    coords[1, 8, 7, 0] = np.nan                                               # cluster 7 is link 4: joint (2, 4), sequence 1, step 8
+    bad = JT.joint_types(coords, *args[1:], JT.TURN_MIN, JT.SLIDE_MIN)
+    assert bad["counts"][3].tolist() == [0, 30, 0, 2] and bad["counts"][:3].tolist() == tree["ref"]["counts"][:3].tolist()
+    none = JT.joint_types(*args[:3], 0, 1, 1, JT.TURN_MIN, JT.SLIDE_MIN)       # one step: no sample
+    assert none["type"].tolist() == [-1] * 4 and none["counts"].tolist() == [[0] * 4] * 4
+
+
+def test_restated_slides_recover_the_true_positions(tree):
+    axes = np.where(np.array(tree["types"])[:, None] == "prismatic", tree["axes"], 0.0)
+    for ref_step, start, n in ((0, 0, 20), (19, 3, 10), (5, 2, 8)):
+        out = JT.joint_slides(tree["link_T"], tree["joints"][1:3], axes[1:3], 0, ref_step, start, n)
+        want = tree["q_true"][JT.PRISMATIC][:, start:start + n] - tree["q_true"][JT.PRISMATIC][0, ref_step]
+        assert np.abs(out["q"][0] - want).max() <= 1e-9
+        assert np.all(out["q"][1] == 0.0)                                     # the fixed joint: a zero axis
+        assert out["tilt_max"].max() <= 1e-9 and out["slip_max"].max() <= 1e-9
+    # a revolute joint read as a slide: its rotation is left over
+    out = JT.joint_slides(tree["link_T"], tree["joints"][:1], tree["axes"][:1])
+    assert out["tilt_max"][0] >= 0.5
+
+
+# ------------------------------------------------------------------------------------------------ create_urdf, limits
+def _joint_data(tree, typed=True):
+    """Hand-made joint dicts of the tree: the axes and points it was built with (identity orientations at step 0)."""
+    pos = tree["link_T"][0, 0, :, :3, 3]
+    out = []
+    for j, ((p, c), kind) in enumerate(zip(tree["joints"], tree["types"])):
+        jd = {"parent_link": p, "child_link": c, "local_axis": tree["axes"][j], "local_pos": np.array([0.0, 0.0, 0.0, 1.0]),
+              "global_pos": pos[c].astype(np.float32).astype(np.float64), "global_axis": tree["axes"][j]}
+        if typed:
+            jd["type"] = kind
+        out.append(jd)
+    return out
+
+
+@pytest.fixture()
+def no_device(tree, monkeypatch):
+    """create_urdf's only device call is link_transforms: here the float32 mean of the clusters' float32 matrices on the host."""
+    from autourdf_amd import compute_joints
+
+    def link_transforms(links, cm, time_step=0):
+        out = {}
+        for l in links:
+            m = np.zeros((4, 4), np.float32)
+            for k in l["cluster_idx"]:
+                m += M.JR.pose_matrix(cm.coords[time_step, k, :3], cm.coords[time_step, k, 3:]).astype(np.float32)
+            out[l["id"]] = m / np.float32(len(l["cluster_idx"]))
+        return out
+    monkeypatch.setattr(compute_joints, "link_transforms", link_transforms)
+
+
+def test_create_urdf_writes_the_three_kinds(tree, no_device, tmp_path):
+    import types
+    from autourdf_amd import compute_joints
+    from autourdf_amd.sim_data import UrdfRobot
+    path = str(tmp_path / "typed.urdf")
+    compute_joints.create_urdf(tree["links"], _joint_data(tree), types.SimpleNamespace(coords=tree["coords"][0]), path, "mesh/dir")
+    robot = UrdfRobot(path, load_meshes=False)
+    by_name = {j["name"]: j for j in robot.joints}
+    assert [by_name[f"joint_{c}"]["type"] for _, c in tree["joints"]] == tree["types"]
+    text = open(path).read()
+    blocks = {m.group(1): m.group(0) for m in re.finditer(r'<joint name="(joint_\d)".*?</joint>', text, re.S)}
+    assert "<axis" not in blocks["joint_3"] and "<limit" not in blocks["joint_3"] and 'type="fixed"' in blocks["joint_3"]
+    assert '<limit effort="100" velocity="100" lower="0.0" upper="0.0" />' in blocks["joint_2"] and "<axis" in blocks["joint_2"]
+    assert 'lower="-3.14159" upper="3.14159"' in blocks["joint_1"] and 'lower="-3.14159" upper="3.14159"' in blocks["joint_4"]
+    np.testing.assert_allclose(by_name["joint_2"]["axis"], tree["axes"][JT.PRISMATIC], rtol=0, atol=1e-6)
+    with pytest.raises(ValueError, match="helical"):
+        compute_joints.create_urdf(tree["links"], [dict(_joint_data(tree)[0], type="helical")] + _joint_data(tree)[1:],
+                                   types.SimpleNamespace(coords=tree["coords"][0]), str(tmp_path / "no.urdf"))
+    assert not os.path.exists(tmp_path / "no.urdf")
+
+
+def test_create_urdf_without_the_key_writes_the_bytes_of_a_revolute_type(tree, no_device, tmp_path):
+    import types
+    from autourdf_amd import compute_joints
+    cm = types.SimpleNamespace(coords=tree["coords"][0])
+    plain, typed = str(tmp_path / "plain.urdf"), str(tmp_path / "typed.urdf")
+    compute_joints.create_urdf(tree["links"], _joint_data(tree, typed=False), cm, plain, "mesh/dir")
+    compute_joints.create_urdf(tree["links"], [dict(j, type="revolute") for j in _joint_data(tree, typed=False)], cm, typed, "mesh/dir")
+    text = open(plain, "rb").read()
+    assert text == open(typed, "rb").read()
+    assert text.count(b'type="revolute"') == 4 and text.count(b'lower="-3.14159" upper="3.14159"') == 4
+    assert b"prismatic" not in text and b"fixed" not in text
+
+
+def test_set_joint_limits_on_typed_joints(tree, no_device, tmp_path):
+    import types
+    from autourdf_amd import compute_joints
+    from autourdf_amd.sim_data import UrdfRobot
+    path = str(tmp_path / "typed.urdf")
+    compute_joints.create_urdf(tree["links"], _joint_data(tree), types.SimpleNamespace(coords=tree["coords"][0]), path, "mesh/dir")
+    before = open(path, "rb").read().splitlines()
+    motion = [{"parent_link": 0, "child_link": 1, "type": "revolute", "lower": -0.5, "upper": 0.25, "n_used": 5},
+              {"parent_link": 1, "child_link": 2, "type": "prismatic", "lower": 0.01, "upper": 7.5, "n_used": 5},
+              {"parent_link": 1, "child_link": 3, "type": "fixed", "lower": 0.0, "upper": 0.0, "n_used": 5},
+              {"parent_link": 2, "child_link": 4, "type": "revolute", "lower": -3.2, "upper": 3.0, "n_used": 5}]
+    compute_joints.set_joint_limits(path, motion, pad=0.05)
+    by_name = {j["name"]: j for j in UrdfRobot(path, load_meshes=False).joints}
+    assert by_name["joint_1"]["type"] == "revolute" and by_name["joint_1"]["limit"] == [-0.5 - 0.05, 0.25 + 0.05]
+    # a slide of 7.5 is no angle: no pad, zero stays inside, and a span past 2 pi does not make it continuous
+    assert by_name["joint_2"]["type"] == "prismatic" and by_name["joint_2"]["limit"] == [0.0, 7.5]
+    assert by_name["joint_3"]["type"] == "fixed" and by_name["joint_4"]["type"] == "continuous"
+    after = open(path, "rb").read().splitlines()
+    changed = [i for i, (x, y) in enumerate(zip(before, after)) if x != y]
+    assert len(after) == len(before) and len(changed) == 4                   # three limits and one joint's type
+    assert not any(b"joint_3" in after[i] for i in changed)
+    # a fixed joint is skipped even without figures; a prismatic one without them is refused as a revolute one is
+    compute_joints.set_joint_limits(path, [dict(motion[2], n_used=0, lower=float("nan"), upper=float("nan"))])
+    with pytest.raises(ValueError, match="joint_2"):
+        compute_joints.set_joint_limits(path, [dict(motion[1], n_used=0)])
