@@ -14,7 +14,8 @@ scope.  No CPU fallback.
 
 This project's own, beyond the reference: ``estimate_typed_joints_from_tree`` also tells prismatic and fixed joints
 (``creg_joint_types_f64``), and ``estimate_joint_motion``, ``set_joint_limits`` and ``replay_urdf`` recover every joint's
-positions, write the observed limits and check the written file against the registration.
+positions, write the observed limits and check the written file against the registration; ``cloud_fit_poses`` and
+``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``).
 """
 import os
 import xml.etree.ElementTree as ET
@@ -447,3 +448,105 @@ def replay_urdf(urdf_file, links, motion, cm_list, start_step, num_steps, time_s
                 r.update({f"{key}_rms": float("nan"), f"{key}_max": float("nan"), f"{key}_max_at": None})
         report.append(r)
     return report
+
+
+def _fit_figures(dist):
+    """n, mean, rms, p95, max, max_at and unexplained of one set of distances: the statistics cover the finite ones."""
+    dist = np.asarray(dist, np.float64)
+    ok = np.isfinite(dist)
+    out = {"n": int(dist.size), "unexplained": int(dist.size - ok.sum())}
+    if ok.any():
+        d = dist[ok]
+        out.update(mean=float(d.mean()), rms=float(np.sqrt((d * d).sum() / d.size)), p95=float(np.percentile(d, 95)),
+                   max=float(d.max()), max_at=int(np.flatnonzero(ok)[np.argmax(d)]))
+    else:
+        out.update(mean=float("nan"), rms=float("nan"), p95=float("nan"), max=float("nan"), max_at=None)
+    return out
+
+
+def cloud_fit_poses(robot, link_T, clouds, d_max=np.inf):
+    """How well a robot's meshes, posed by ``link_T``, explain one cloud per pose (this project's own): robot a ``UrdfRobot``
+    loaded with its meshes, link_T (P,L,4,4) device poses in ``robot.links``' order (``ops.urdf_fk``), clouds a list of P (n_p,3)
+    arrays of world points.  ONE ``ops.point_mesh_distance`` call for all poses.  Returns a dict:
+    "poses", one dict per pose with n, mean, rms, p95, max, max_at (the point's row in its cloud) and unexplained (points
+    farther than ``d_max`` from every triangle, or NaN; their distance is ``inf``), the statistics over the finite distances;
+    "links", one dict per link with link (name), n (finite points whose nearest triangle is the link's) and rms; "all", the
+    pose figures over every point (max_at a (pose, row) pair); and "dist" / "link", lists of P host arrays with every point's
+    distance and link index (-1 where no triangle was within ``d_max``).  No threshold turns a figure into a verdict.  Not seen
+    from this side: mesh surface that no point lies near, and a wrong link that happens to lie on the right surface."""
+    dev = link_T.device
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if len(clouds) != link_T.shape[0]:
+        raise ValueError(f"cloud_fit_poses: {link_T.shape[0]} poses need as many clouds, got {len(clouds)}")
+    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    cut = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
+    pts = torch.as_tensor(np.concatenate(parts) if parts else np.zeros((0, 3)), device=dev)
+    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
+    dist, _, link = ops.point_mesh_distance(tri, torch.as_tensor(robot.tri_start, device=dev), link_T, pts,
+                                            torch.as_tensor(cut, device=dev), d_max)
+    dist, link = dist.cpu().numpy(), link.cpu().numpy()
+    poses = [_fit_figures(dist[cut[p]:cut[p + 1]]) for p in range(len(parts))]
+    overall = _fit_figures(dist)
+    if overall["max_at"] is not None:
+        p = int(np.searchsorted(cut, overall["max_at"], side="right") - 1)
+        overall["max_at"] = (p, int(overall["max_at"] - cut[p]))
+    ok = np.isfinite(dist)
+    per_link = []
+    for l, name in enumerate(robot.links):
+        d = dist[ok & (link == l)]
+        per_link.append({"link": name, "n": int(d.size), "rms": float(np.sqrt((d * d).sum() / d.size)) if d.size else float("nan")})
+    return {"poses": poses, "links": per_link, "all": overall,
+            "dist": [dist[cut[p]:cut[p + 1]] for p in range(len(parts))], "link": [link[cut[p]:cut[p + 1]] for p in range(len(parts))]}
+
+
+def cloud_fit_link_poses(urdf_file, links, motion, cm_list, start_step, num_steps, time_step=0):
+    """The poses ``cloud_fit`` puts the URDF's meshes at -> (robot, link_T (S*num_steps,L,4,4) device poses in ``robot.links``'
+    order): the file with its meshes (``UrdfRobot(path)``: every visual origin as written), the ``q`` rows of ``replay_urdf``
+    through one ``ops.urdf_fk`` call, and every pose moved by the registered motion of the root link,
+    G = reg[s,t,root] reg[0,time_step,root]^-1 from ``ops.link_poses`` (the raw clouds carry a per-frame translation that the
+    URDF's fixed base does not): link_T = G A(q).  The file is taken at its word.  ``create_urdf`` keeps the reference's origin
+    expressions, which add offsets taken in the world frame to offsets taken in link frames; they hold when the registered link
+    frames of (sequence 0, ``time_step``) are unrotated, which is how the registration defines step 0 (DESIGN N4 has the
+    figures for both cases).  At another ``time_step`` the file's zero pose is off, and this check says so, as the replay does."""
+    from .sim_data import UrdfRobot
+    robot = UrdfRobot(urdf_file)
+    coords = _coords(cm_list)
+    reg = ops.link_poses(coords, [list(l["cluster_idx"]) for l in links])      # (S,T,L,4,4)
+    S, n = reg.shape[0], int(num_steps)
+    if start_step < 0 or n < 1 or start_step + n > reg.shape[1]:
+        raise IndexError(f"steps [{start_step}, {start_step + n}) are out of bounds for axis 0 with size {reg.shape[1]}")
+    q_by_name = {f"joint_{m['child_link']}": np.asarray(m["positions"], np.float64).reshape(S, n) for m in motion}
+    names = robot.fk_table()["names"]
+    q = np.zeros((S * n, len(names)))
+    for col, name in enumerate(names):
+        if name in q_by_name:
+            q[:, col] = q_by_name[name].reshape(-1)
+    fk = ops.urdf_fk(robot.fk_table(), q, np.eye(4))                           # (S*n, L_urdf, 4, 4)
+    (root,) = [i for i, l in enumerate(links) if l["parent_id"] is None]
+    G = reg[:, start_step:start_step + n, root].reshape(S * n, 4, 4) @ torch.linalg.inv(reg[0, time_step, root])
+    return robot, (G[:, None] @ fk).contiguous()
+
+
+def cloud_fit(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf):
+    """Check the written URDF against the raw clouds it was made from (this project's own): the file's meshes, posed by the
+    file's joints at the recovered positions of every step of every sequence (``cloud_fit_link_poses``), against that step's
+    ``robot.ply`` under ``raw_dirs[s]`` (``cluster_icp.read_point_cloud``), in one ``cloud_fit_poses`` call, whose dict is
+    returned with "sequences" added: the pose figures over each sequence's points (max_at a (step, row) pair).  Pose
+    s * num_steps + k is step ``start_step + k`` of sequence s.  Distances are in the clouds' unit."""
+    from .cluster_icp import read_point_cloud
+    robot, link_T = cloud_fit_link_poses(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
+    S, n = len(cm_list), int(num_steps)
+    clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
+              for s in range(S) for k in range(n)]
+    fit = cloud_fit_poses(robot, link_T, clouds, d_max)
+    fit["sequences"] = []
+    for s in range(S):
+        sizes = [len(c) for c in clouds[s * n:(s + 1) * n]]
+        cut = np.concatenate([[0], np.cumsum(sizes)])
+        fig = _fit_figures(np.concatenate(fit["dist"][s * n:(s + 1) * n]) if n else np.zeros(0))
+        if fig["max_at"] is not None:
+            k = int(np.searchsorted(cut, fig["max_at"], side="right") - 1)
+            fig["max_at"] = (int(start_step + k), int(fig["max_at"] - cut[k]))
+        fit["sequences"].append(fig)
+    return fit

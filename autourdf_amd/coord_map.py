@@ -390,7 +390,11 @@ def _cli_parser():
     (degrees, default 0) widens that range.  --limit_pad without --joint_limits is a usage error.  --collision_hull writes
     every link's convex hull next to its mesh and names it in the URDF's <collision> blocks.  --joint_types tells revolute,
     prismatic and fixed joints apart: --slide_min (the clouds' unit, required with it) and --turn_min (rad, default 2e-4)
-    are its two thresholds.  --joint_types without --joint_limits, and a threshold without --joint_types, are usage errors."""
+    are its two thresholds.  --joint_types without --joint_limits, and a threshold without --joint_types, are usage errors.
+    --cloud_fit sets the written URDF's meshes, posed at the recovered joint positions, against the raw clouds and writes
+    <name>.cloud_fit.json; --fit_max (the clouds' unit, default inf) is the distance beyond which a point counts as
+    unexplained.  --cloud_fit without --voxel_size or without --joint_limits, and --fit_max without --cloud_fit, are usage
+    errors."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
@@ -400,6 +404,8 @@ def _cli_parser():
     parser.add_argument('--joint_types', action='store_true')
     parser.add_argument('--slide_min', type=float, default=None)
     parser.add_argument('--turn_min', type=float, default=None)
+    parser.add_argument('--cloud_fit', action='store_true')
+    parser.add_argument('--fit_max', type=float, default=None)
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -410,6 +416,12 @@ def _cli_parser():
             parser.error("--joint_types needs --joint_limits: a prismatic joint has no placeholder range")
         if (ns.slide_min is not None or ns.turn_min is not None) and not ns.joint_types:
             parser.error("--slide_min and --turn_min need --joint_types")
+        if ns.cloud_fit and ns.voxel_size is None:
+            parser.error("--cloud_fit needs --voxel_size: it measures the raw clouds against the link meshes")
+        if ns.cloud_fit and not ns.joint_limits:
+            parser.error("--cloud_fit needs --joint_limits: the meshes are posed at the recovered joint positions")
+        if ns.fit_max is not None and not ns.cloud_fit:
+            parser.error("--fit_max needs --cloud_fit")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -443,6 +455,26 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
               f"pos_max {w['pos_max']:.3g} at {w['pos_max_at']}")
 
 
+def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names):
+    """Write <name>.cloud_fit.json next to the URDF -- the per-frame, per-sequence, per-link and overall figures of
+    ``cloud_fit``, without the per-point arrays -- and print one line per sequence (rms, p95, unexplained share) and the worst
+    frame.  ``fit_max`` is written as null when it is inf."""
+    import json
+    stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
+    clean = lambda d: {k: (None if isinstance(v, float) and not np.isfinite(v) else v) for k, v in d.items()}
+    frames = [dict(clean(f), sequence=i // num_steps, step=start_step + i % num_steps) for i, f in enumerate(fit["poses"])]
+    with open(stem + '.cloud_fit.json', 'w') as f:
+        json.dump({"urdf": urdf_path, "fit_max": None if np.isinf(fit_max) else fit_max, "start_step": start_step,
+                   "unit": "the clouds' unit", "all": clean(fit["all"]), "sequences": [clean(s) for s in fit["sequences"]],
+                   "links": [clean(l) for l in fit["links"]], "frames": frames}, f, indent=1)
+    for name, s in zip(seq_names, fit["sequences"]):
+        print(f"cloud_fit {name}: rms {s['rms']:.3g}, p95 {s['p95']:.3g}, unexplained {s['unexplained'] / max(s['n'], 1):.2%} of {s['n']}")
+    seen = [f for f in frames if f["rms"] is not None]
+    if seen:
+        w = max(seen, key=lambda f: f["rms"])
+        print(f"cloud_fit: worst frame sequence {w['sequence']} step {w['step']}: rms {w['rms']:.3g}, max {w['max']:.3g} at point {w['max_at']}")
+
+
 def main(argv=None):
     """The reference's ``python coord_map.py`` (coord_map.py:641-792) without its viewers and plots: sum maps, MST, link
     discovery, kinematic tree, joint axes, link clouds, their ICP refinement, the link meshes and the URDF file.  Paths
@@ -463,13 +495,17 @@ def main(argv=None):
     come from ``estimate_typed_joints_from_tree``: a child that never turns against its parent becomes a prismatic or a fixed
     joint instead of a ValueError, the report names every joint's type and unit, and a prismatic joint's limits are its
     observed slide.  It needs the joint limits and a ``slide_min``, and a threshold needs it: ValueError before anything is
-    written otherwise."""
+    written otherwise.  With ``--cloud_fit`` (or a boolean ``cloud_fit`` key; ``--fit_max`` / ``fit_max`` in the clouds' unit,
+    default inf, the option wins) the written URDF's meshes, posed by its joints at the recovered positions, are set against
+    every loaded raw cloud after the replay (``cloud_fit``: one ``ops.point_mesh_distance`` call), ``<name>.cloud_fit.json`` is
+    written next to the URDF and one line per sequence and the worst frame are printed.  It needs the link meshes and the joint
+    limits, and a ``fit_max`` needs it: ValueError before anything is written otherwise."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import (create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
+    from .compute_joints import (cloud_fit, create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
                                  estimate_typed_joints_from_tree, replay_urdf, set_collision_meshes, set_inertials,
                                  set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
@@ -508,6 +544,19 @@ def main(argv=None):
     for name, value in (("slide_min", slide_min), ("turn_min", turn_min)):
         if value is not None and not (np.isfinite(float(value)) and float(value) >= 0.0):
             raise ValueError(f"{name} must be finite and >= 0, got {value}")
+    want_fit = bool(args.cloud_fit or robot_params.get('cloud_fit'))
+    fit_max = args.fit_max if args.fit_max is not None else robot_params.get('fit_max')
+    if fit_max is not None and not want_fit:
+        raise ValueError("a fit_max is the cloud fit's distance limit: give --cloud_fit (or a cloud_fit key in parameters.json) with it")
+    if want_fit and voxel_size is None:
+        raise ValueError("the cloud fit needs the link meshes: give --voxel_size (or a voxel_size key in parameters.json) with "
+                         "--cloud_fit")
+    if want_fit and not joint_limits:
+        raise ValueError("the cloud fit poses the meshes at the recovered joint positions: give --joint_limits (or a joint_limits "
+                         "key in parameters.json) with --cloud_fit")
+    fit_max = float("inf") if fit_max is None else float(fit_max)
+    if not fit_max >= 0.0:
+        raise ValueError(f"fit_max must be >= 0 (inf allowed), got {fit_max}")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -582,6 +631,9 @@ def main(argv=None):
         set_joint_limits(urdf_path, motion, float(np.radians(limit_pad)))
         replay = replay_urdf(urdf_path, links, motion, cm_list, START, END - START)
         _joint_motion_report(urdf_path, motion, replay, limit_pad, START)
+        if want_fit:
+            fit = cloud_fit(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START, d_max=fit_max)
+            _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path])
     return urdf_path
 
 

@@ -638,6 +638,73 @@ def mesh_contain(tri, tri_start, pts, pt_start, link_T, pairs, want_winding: boo
     return (inside, first) + ((winding,) if want_winding else ()) + ((boxes,) if want_boxes else ())
 
 
+def _morton_order(pts, pt_start, P):
+    """A permutation of pts' rows that keeps every pose's rows where they are as a set and orders them by a 30-bit Morton key,
+    10 bits per axis over the pose's own bounding box (NaN and infinite coordinates count as 0: any order is a valid one)."""
+    N, dev = pts.shape[0], pts.device
+    pose = torch.repeat_interleave(torch.arange(P, device=dev), pt_start[1:] - pt_start[:-1], output_size=N)
+    x = torch.nan_to_num(pts, nan=0.0, posinf=0.0, neginf=0.0)
+    at = pose[:, None].expand(N, 3)
+    lo = torch.full((P, 3), float("inf"), dtype=pts.dtype, device=dev).scatter_reduce(0, at, x, "amin")
+    hi = torch.full((P, 3), float("-inf"), dtype=pts.dtype, device=dev).scatter_reduce(0, at, x, "amax")
+    ext = (hi - lo)[pose]
+    cell = ((x - lo[pose]) * torch.where(ext > 0, 1023.0 / ext, torch.zeros_like(ext))).clamp_(0, 1023).to(torch.int64)
+    for shift, mask in ((16, 0x030000FF), (8, 0x0300F00F), (4, 0x030C30C3), (2, 0x09249249)):      # spread 10 bits to every third
+        cell = (cell | (cell << shift)) & mask
+    key = (pose << 30) | (cell[:, 0] << 2) | (cell[:, 1] << 1) | cell[:, 2]
+    return torch.argsort(key)
+
+
+def point_mesh_distance(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"), sort: bool = True, want_boxes: bool = False):
+    """Distance from world points to posed link meshes (creg_point_mesh_f64; the contract is in include/creg.h): tri (F,3,3) f64
+    link-frame triangles, tri_start (L+1) int64, link_T (P,L,4,4) f64 -- or (L,4,4) for P = 1 --, pts (N,3) f64 world points and
+    pt_start (P+1) int64 (pose p owns rows pt_start[p]:pt_start[p+1]), all on the device, and ``d_max`` >= 0 (``inf`` allowed)
+    -> dist (N) f64, the distance from every point to its pose's mesh, ``+inf`` where it exceeds ``d_max`` (no triangle within
+    ``d_max`` by the box test, or a found minimum above it; also for a NaN point), tri_idx (N) int32 the row of tri that attains
+    the kernel's minimum or -1 where no triangle was within ``d_max`` by the box test, link (N) int32 the link that owns that row
+    or -1, and link_box (P,L,6) when ``want_boxes``.  One call for all poses.
+    ``sort=True`` hands the kernel every pose's points in Morton order (10 bits per axis over the pose's own bounding box) and
+    scatters the results back, so that a tile of 64 points is compact and the kernel's box culls bite; a point's result does
+    not depend on the order, so no bit of any output changes.
+    ValueError before any launch: a bad shape or dtype, a tri_start that does not run 0 .. F or a pt_start that does not run
+    0 .. N without decreasing (both are read back: the one synchronisation), a negative or NaN ``d_max``."""
+    L = _lib.load()
+    d_max = float(d_max)
+    if not d_max >= 0.0:
+        raise ValueError(f"point_mesh_distance: d_max must be >= 0 (inf allowed), got {d_max}")
+    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
+    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
+            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
+            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1:
+        raise ValueError(f"point_mesh_distance: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) expected, "
+                         f"got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, {tuple(pts.shape)}, "
+                         f"{tuple(pt_start.shape)}")
+    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    ok = (tri_start[0] == 0) & (tri_start[-1] == F) & (tri_start[1:] >= tri_start[:-1]).all() \
+        & (pt_start[0] == 0) & (pt_start[-1] == N) & (pt_start[1:] >= pt_start[:-1]).all()
+    if not bool(ok):
+        raise ValueError(f"point_mesh_distance: tri_start must run from 0 to {F} and pt_start from 0 to {N} without decreasing")
+    order = _morton_order(pts, pt_start, P) if sort and N else None
+    dist2 = torch.empty(N, dtype=torch.float64, device=dev)
+    tri_idx = torch.empty(N, dtype=torch.int32, device=dev)
+    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
+    ws_bytes = L.creg_point_mesh_workspace_bytes(F, n_links, P, N)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    sent = pts if order is None else pts[order].contiguous()
+    _lib.check(L.creg_point_mesh_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(sent) if N else None,
+                                     _p(pt_start), N, d_max, _p(dist2) if N else None, _p(tri_idx) if N else None, _p(boxes), _p(ws),
+                                     ws_bytes, _stream()), "creg_point_mesh_f64")
+    if order is not None:
+        dist2, tri_idx = torch.empty_like(dist2).index_copy_(0, order, dist2), torch.empty_like(tri_idx).index_copy_(0, order, tri_idx)
+    dist = torch.where(dist2 > d_max * d_max, torch.full_like(dist2, float("inf")), torch.sqrt(dist2))
+    owner = (torch.searchsorted(tri_start, tri_idx.to(torch.int64), right=True) - 1).to(torch.int32)
+    link = torch.where(tri_idx >= 0, owner, torch.full_like(owner, -1))
+    return (dist, tri_idx, link) + ((boxes,) if want_boxes else ())
+
+
 MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")
 
 

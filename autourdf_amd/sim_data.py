@@ -742,6 +742,25 @@ class SimEnv:
                         near.append(pr + (0.0, -1, -1))
         return out
 
+    def surface_distance(self, link_T, clouds, d_max=np.inf):
+        """How far the points of P clouds lie from the robot's meshes at P poses, in one launch (creg_point_mesh_f64): link_T
+        (P,L,4,4) -- or (L,4,4) -- device poses (ops.urdf_fk) and ``clouds``, one (n_p,3) array of world points per pose (host
+        arrays or device tensors).  Returns (dist, tri, link), each a list with one host array per pose: the distance of every
+        point from the posed meshes (``inf`` beyond ``d_max``), the row of ``robot.tri`` that attains it and the index in
+        ``robot.links`` of the link that owns that row (-1 where no triangle was within ``d_max``): a part segmentation of the
+        cloud.  The other direction -- mesh surface that no point lies near -- is not measured."""
+        tri = self._device_mesh()[0]
+        if link_T.dim() == 3:
+            link_T = link_T[None]
+        if len(clouds) != link_T.shape[0]:
+            raise ValueError(f"surface_distance: {link_T.shape[0]} poses need as many clouds, got {len(clouds)}")
+        parts = [torch.as_tensor(c, dtype=torch.float64).reshape(-1, 3).to(tri.device) for c in clouds]
+        cut = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+        pts = torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.float64, device=tri.device)
+        tri_start = self._collide_inputs(False)[2]
+        out = ops.point_mesh_distance(tri, tri_start, link_T, pts, torch.as_tensor(cut, device=tri.device), d_max)
+        return tuple([a[cut[p]:cut[p + 1]] for p in range(len(parts))] for a in (o.cpu().numpy() for o in out))
+
     def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0, containment=False):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
         `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""

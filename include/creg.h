@@ -780,6 +780,48 @@ int creg_mesh_clearance_f64(const double* tri, const int64_t* tri_start, int64_t
                             double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point-to-mesh distance: for every point of every pose, in one call, the minimum squared distance to the pose's posed triangle
+ * mesh and the triangle that attains it.  The check of a written URDF against the raw clouds rests on it, and the triangle's link
+ * is a part segmentation of the cloud.  The reference has no such step; this contract is the project's own.
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T, n_links, n_poses and link_box are exactly those of
+ *              creg_mesh_collide_f64: the same posed vertices w_i in the same operation order, the same exact min / max boxes.
+ *              pts (n_pts,3) fp64: WORLD points.  Pose p owns rows pt_start[p] .. pt_start[p+1] (pt_start (n_poses+1) int64,
+ *              non-decreasing, 0 .. n_pts; each pose's two values are clamped into 0 .. n_pts the way tri_start's are, nothing
+ *              outside pts, dist2 and tri_idx is touched).  d_max >= 0 may be +inf.
+ *   live       a point is live iff none of its three coordinates is NaN (x == x on each).  A point that is not live has no
+ *              contributing triangle.  The box of a live point is lo = hi = the point.
+ *   box gap    gap2 of the clearance contract above; for a triangle's box and a point p it reads
+ *              gap2(p, box) = (g_x*g_x + g_y*g_y) + g_z*g_z,  g_k = max(0, max(lo[k] - p[k], p[k] - hi[k])).
+ *   contributes   triangle f of pose p contributes to live point i of pose p iff gap2(p_i, box_f) <= d_max*d_max, box_f the exact
+ *              min / max box of the three posed vertices.  This test is part of the contract.  By the monotonicity stated in the
+ *              clearance contract, culling by link box, by 256-triangle chunk box and by the union box of a tile of live points,
+ *              with the box-box gap2 and the same d_max*d_max, drops no contributing triangle: culling changes no output.
+ *   d2(i, f)   pt_tri2(p_i; a, b, c) of the clearance contract above, (a, b, c) the posed vertices of row f: its seven cases in
+ *              that order, dot(u,v) = (u_x*v_x + u_y*v_y) + u_z*v_z, no contraction, no square root.  A zero-area triangle goes
+ *              through the den > 0 and s > 0 guards like any other; every guard answers with a point of the triangle.
+ *   outputs    per point: best = +inf, idx = -1; then the contributing triangles of its pose in ascending row order, each
+ *              replacing (best, idx) by (d2, row) when d2 < best.  So
+ *              dist2 (n_pts) fp64: the minimum of d2 over the contributing triangles, +inf when there is none;
+ *              tri_idx (n_pts) int32: the smallest row of tri whose d2 has exactly the bits of that minimum, or -1.
+ *              (A d2 that is not below +inf -- a point with an infinite coordinate -- leaves +inf and -1.)
+ *              link_box as in creg_mesh_collide_f64; may be NULL.
+ *              A row of pts that no pose owns is not written.  n_pts == 0 fills link_box only.
+ * A value above d_max*d_max can appear: the box gap was small and the triangle farther away; callers read it as "beyond d_max".
+ * If a point's true distance to the mesh is at most d_max, the triangle that attains it contributes, so the result is then the
+ * distance to the mesh.  Nothing is pruned by a running best (computed d2 and computed gap2 are different formulas, so that could
+ * change a tie): d_max is the cull.
+ * Determinism: no atomics.  A point's two outputs are a function of its coordinates and of its pose's posed mesh alone: they do
+ * not depend on the other points or poses of the call, on the order of pts, or on scheduling.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, n_pts < 0 or >= 2^31,
+ * (n_pts >> 6) + n_poses >= 2^31, a null tri (with n_tri > 0), tri_start, link_T, pt_start or workspace, a null pts, dist2 or
+ * tri_idx with n_pts > 0, a NaN or negative d_max, a workspace smaller than creg_point_mesh_workspace_bytes(...) (posed vertices,
+ * chunk and link boxes; 0 for the counts refused here).  Poses are posed in slices of 65535. */
+size_t creg_point_mesh_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pts);
+int creg_point_mesh_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                        int64_t n_poses, const double* pts, const int64_t* pt_start, int64_t n_pts, double d_max, double* dist2,
+                        int32_t* tri_idx, double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Containment: is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
  * call, the generalized winding number of one link's posed triangle mesh at a few points of the other.  It closes the hole the
  * two entries above share (no edge pierces a face when a mesh lies wholly inside another); the reference rejects such a pose
