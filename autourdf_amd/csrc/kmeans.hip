@@ -320,8 +320,13 @@ __device__ void km_mstep_tail(const double* __restrict__ X, int n, const int* __
         for (int d = 0; d < 3; ++d) a[d] = (double)(long long)ld_agent(acc + 4 * j + d) * finv;
         a[3] = (double)(long long)ld_agent(acc + 4 * j + 3);
         if (a[3] == 0.0) atomicAdd(&S.nempty, 1);                  // integer count: order independent
-        if (relocate) for (int d = 0; d < 4; ++d) Cw[4 * j + d] = a[d];
-        else {
+        if (relocate) {
+            for (int d = 0; d < 4; ++d) Cw[4 * j + d] = a[d];
+            // the list of empty clusters is FIXED before anything moves (sklearn's _relocate_empty_clusters_dense takes
+            // np.where(weight_in_clusters == 0) first): a cluster that the pass empties -- its only point was the farthest one -- is
+            // not refilled in this pass (k_km_nd's rule; cpark is free on this path)
+            cpark[j] = a[3] == 0.0 ? 1.0 : 0.0;
+        } else {
             // common path: straight to the centre, parked in LDS until the barrier says "no empty cluster" (an empty
             // cluster defers the whole tail, nothing is kept)
             double s2 = 0;
@@ -352,7 +357,7 @@ __device__ void km_mstep_tail(const double* __restrict__ X, int n, const int* __
             km_block_argmax<NT>(dv, di, S);
             if (dv > 0) {                                        // the largest distance: all zero -> nothing moves (sklearn)
                 for (int j = 0; j < k; ++j) {
-                    if (Cw[4 * j + 3] != 0.0) continue;          // uniform: Cw only changes under barriers
+                    if (cpark[j] == 0.0) continue;               // uniform: written before the barrier above, never after
                     double bv = -1; int bi = 0x7fffffff;
                     for (int sg = tid; sg < nseg; sg += NT) { const double v = ld_agent(segv + sg); const int i = ld_agent(segi + sg); if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; } }
                     km_block_argmax<NT>(bv, bi, S);
@@ -1166,6 +1171,7 @@ __global__ __launch_bounds__(1024) void k_km_small(KmBatch A, int n, int k, int 
     __shared__ int s_changed, s_done, s_strict, s_it, s_nempty, s_argmax;
     __shared__ double s_dmax, s_fv[16];
     __shared__ int s_fi[16];
+    __shared__ unsigned char s_emp[128];                      // (k <= 128) the clusters that were empty when the relocation started
     const int z = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const double* X = A.X[z];
     char* w = ws + (size_t)z * ws_stride;                     // per-problem global scratch: C2 (6k), Cw (4k), far (n)
@@ -1291,8 +1297,12 @@ __global__ __launch_bounds__(1024) void k_km_small(KmBatch A, int n, int k, int 
             if (tid == 0) { double m = 0; for (int i = 0; i < 16; ++i) m = fmax(m, sc[i]); s_dmax = m; }
             __syncthreads();
             if (s_dmax > 0) {
+                // the list of empty clusters is FIXED before anything moves (km_mstep_tail, k_km_nd): a cluster that the pass
+                // empties is not refilled in this pass
+                if (tid < k) s_emp[tid] = a4[3] == 0.0;
+                __syncthreads();
                 for (int j = 0; j < k; ++j) {
-                    if (Cw[4 * j + 3] != 0.0) continue;
+                    if (!s_emp[j]) continue;                   // block-uniform (LDS value)
                     double bv = -1; int bi = 0x7fffffff;
                     for (int i = tid; i < n; i += 1024) if (far_d[i] > bv) { bv = far_d[i]; bi = i; }
                     for (int off = 32; off >= 1; off >>= 1) {
@@ -1643,6 +1653,8 @@ extern "C" int creg_kmeans_lloyd_f64(const double* X, int64_t n, const double* i
     CREG_REQUIRE(X && init && centers && labels && inertia && n_iter && workspace, "creg_kmeans_lloyd_f64: null pointer");
     CREG_REQUIRE(n >= 1 && n < (1ll << 31) && k >= 1 && k <= 1024 && max_iter >= 1,
                  "creg_kmeans_lloyd_f64: need 1 <= n < 2^31, 1 <= k <= 1024, max_iter >= 1");
+    // n >= k: a pass relocates a cluster at most once, so at most k - 1 <= n - 1 points are taken when a farthest-point search starts
+    CREG_REQUIRE(n >= k, "creg_kmeans_lloyd_f64: n_samples=%lld should be >= n_clusters=%d", (long long)n, k);
     const KmGeom geo = km_geometry(n);
     const KmLayout L = km_layout(n, k, geo);
     CREG_REQUIRE(workspace_bytes >= L.total, "creg_kmeans_lloyd_f64: workspace too small (%zu < %zu)", workspace_bytes, L.total);
@@ -1694,6 +1706,8 @@ extern "C" int creg_kmeans_lloyd_batch_f64(const double* const* X, int64_t n, co
     CREG_REQUIRE(batch >= 1 && batch <= KMS_MAXB, "creg_kmeans_lloyd_batch_f64: batch must be in [1, %d]", KMS_MAXB);
     CREG_REQUIRE(n >= 1 && n <= 16384 && k >= 1 && k <= 128 && max_iter >= 1,
                  "creg_kmeans_lloyd_batch_f64: needs n <= 16384 and k <= 128 (centres and labels resident in LDS; the frame too up to 5120 points); use creg_kmeans_lloyd_f64 otherwise");
+    // n >= k: a pass relocates a cluster at most once, so at most k - 1 <= n - 1 points are taken when a farthest-point search starts
+    CREG_REQUIRE(n >= k, "creg_kmeans_lloyd_batch_f64: n_samples=%lld should be >= n_clusters=%d", (long long)n, k);
     CREG_REQUIRE(workspace_bytes >= kms_stride(n, k) * (size_t)batch, "creg_kmeans_lloyd_batch_f64: workspace too small");
     KmBatch A;
     for (int b = 0; b < batch; ++b) {

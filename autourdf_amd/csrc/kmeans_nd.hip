@@ -270,6 +270,8 @@ extern "C" int creg_kmeans_lloyd_nd_f64(const double* X, int64_t n, int32_t dim,
     CREG_REQUIRE(dim == 6 || dim == 3, "creg_kmeans_lloyd_nd_f64: dim must be 6 ([xyz | 0.5 normal], the --normal branch) or 3");
     CREG_REQUIRE(n >= 1 && n < (1ll << 24) && k >= 1 && k <= KND_MAXK && max_iter >= 1,
                  "creg_kmeans_lloyd_nd_f64: needs n < 2^24 and k <= %d (one workgroup, centres in LDS)", KND_MAXK);
+    // n >= k: a pass relocates a cluster at most once, so at most k - 1 <= n - 1 points are taken when a farthest-point search starts
+    CREG_REQUIRE(n >= k, "creg_kmeans_lloyd_nd_f64: n_samples=%lld should be >= n_clusters=%d", (long long)n, k);
     CREG_REQUIRE(workspace_bytes >= creg_kmeans_nd_workspace_bytes(n), "creg_kmeans_lloyd_nd_f64: workspace too small");
     const int bw = dim + 1;
     const bool gl = n > KND_LDS_N;

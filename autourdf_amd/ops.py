@@ -120,10 +120,18 @@ def pack_clusters(clusters, device, dtype=torch.float32):
 
 
 # ------------------------------------------------------------------------------ K2 k-means
+def _need_n_ge_k(n: int, k: int) -> None:
+    """sklearn's refusal, in its words, before the library loads: with fewer points than clusters the empty-cluster relocation of
+    the Lloyd kernels runs out of points to take (the C entry points refuse it too)."""
+    if n < k:
+        raise ValueError(f"n_samples={n} should be >= n_clusters={k}.")
+
+
 def kmeans_lloyd(X: torch.Tensor, init: torch.Tensor, max_iter: int = 300, tol: float = 1e-4,
                  use_mfma: bool = False):
     """sklearn.cluster.k_means(X, init=init, n_init=1): returns (centers (k,3) f64, labels (n) int32,
     inertia (1) f64, n_iter (1) int32), all on the device."""
+    _need_n_ge_k(X.shape[0], init.shape[0])
     L = _lib.load()
     X, init = _need(X, torch.float64, "X"), _need(init, torch.float64, "init")
     n, k = X.shape[0], init.shape[0]
@@ -139,9 +147,10 @@ def kmeans_lloyd(X: torch.Tensor, init: torch.Tensor, max_iter: int = 300, tol: 
 
 
 def kmeans_lloyd_nd(X: torch.Tensor, init: torch.Tensor, max_iter: int = 300, tol: float = 1e-4):
-    """sklearn.cluster.k_means(X, init=init, n_init=1) over (n,6) features -- the `--normal` branch clusters [xyz | 0.5 normal]
-    (mlp_reg.py:196-203) -- in one workgroup (n <= 16384, k <= 128): (centers (k,d) f64, labels (n) int32, inertia (1) f64,
-    n_iter (1) int32), all on the device."""
+    """sklearn.cluster.k_means(X, init=init, n_init=1) over (n,6) or (n,3) features -- the `--normal` branch clusters
+    [xyz | 0.5 normal] (mlp_reg.py:196-203) -- in one workgroup (k <= n < 2^24, k <= 128; the labels stay in LDS up to 16384 points
+    and live in the workspace above): (centers (k,d) f64, labels (n) int32, inertia (1) f64, n_iter (1) int32), all on the device."""
+    _need_n_ge_k(X.shape[0], init.shape[0])
     L = _lib.load()
     X, init = _need(X, torch.float64, "X"), _need(init, torch.float64, "init")
     n, d, k = X.shape[0], X.shape[1], init.shape[0]
@@ -191,6 +200,8 @@ def _batchable(limit, *lists):
 def kmeans_lloyd_batch(Xs, inits, max_iter: int = 300, tol: float = 1e-4):
     """k_means() for a list of same-sized frames in ONE asynchronous launch (one workgroup per frame,
     n <= 16384).  Returns a list of (centers, labels, inertia, n_iter) like `kmeans_lloyd`."""
+    for x, c in zip(Xs, inits):
+        _need_n_ge_k(x.shape[0], c.shape[0])
     L = _lib.load()
     Xs = [_need(x, torch.float64, "X") for x in Xs]
     inits = [_need(c, torch.float64, "init") for c in inits]

@@ -85,6 +85,8 @@ int creg_cluster_transform_bwd_f32(const float* pts, const int32_t* seg_offsets,
  * (cluster_icp.py:67, after k-means++ seeding on the host).
  *   distance  d = fma(x2,b2, fma(x1,b1, fma(x0,b0, |c|^2))),  b = -2c   (first minimum wins)
  * X (n,3) fp64 is read only (centring happens on an internal copy), init (k,3) fp64.
+ * n >= k is required, as by sklearn ("n_samples=.. should be >= n_clusters=.."): the three Lloyd entry points return an error
+ * before any launch otherwise (the relocation of empty clusters would run out of points to take).
  * Outputs: centers (k,3) fp64, labels (n) int32, inertia (1) fp64, n_iter (1) int32 -- device.
  * use_mfma != 0 selects the v_mfma_f64_16x16x4_f64 assignment kernel: every centre for every point, in the caller's order,
  * one launch per Lloyd iteration (E-step, exact incremental M-step sums, M-step tail; the convergence test runs on the
@@ -574,7 +576,8 @@ int creg_lattice_hull_emit_i32(const int32_t* pts, int64_t n, const int64_t* off
 int creg_knn_normals_f64(const double* X, int64_t n, double radius, int32_t max_nn, int32_t* idx_out, int32_t* cnt_out,
                          double* normals, creg_stream_t stream);
 /* sklearn.cluster.k_means(X, init=<array>, n_clusters=k, n_init=1) over DIM-dimensional features (dim = 6: the --normal
- * branch's [xyz | 0.5 n]; 3 also accepted), n <= 16384, k <= 128, one workgroup, no host sync.  X (n,dim), init (k,dim),
+ * branch's [xyz | 0.5 n]; 3 also accepted), k <= n < 2^24, k <= 128, one workgroup (labels in LDS up to 16384 points, in the
+ * workspace above), no host sync.  X (n,dim), init (k,dim),
  * centers (k,dim) fp64; labels (n) int32; inertia (1) fp64; n_iter (1) int32; tol_rel = 1e-4 in the reference.
  * workspace: creg_kmeans_nd_workspace_bytes(n). */
 size_t creg_kmeans_nd_workspace_bytes(int64_t n);

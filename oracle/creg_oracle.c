@@ -185,8 +185,12 @@ int oracle_kmeans_lloyd_f64(const double* X_in, int64_t n, const double* C0, int
                 if (dist_far[i] > dmax) dmax = dist_far[i];
             }
             if (dmax > 0) {
+                /* the list of empty clusters is fixed before anything moves (np.where(weight_in_clusters == 0) comes
+                 * first): a cluster that the pass empties is not refilled in it */
+                unsigned char* was_empty = (unsigned char*)malloc((size_t)k);
+                for (int j = 0; j < k; ++j) was_empty[j] = (w[j] == 0.0);
                 for (int j = 0; j < k; ++j) {
-                    if (w[j] != 0.0) continue;
+                    if (!was_empty[j]) continue;
                     int64_t far = 0; double best = -1;
                     for (int64_t i = 0; i < n; ++i)
                         if (dist_far[i] > best) { best = dist_far[i]; far = i; }
@@ -198,6 +202,7 @@ int oracle_kmeans_lloyd_f64(const double* X_in, int64_t n, const double* C0, int
                     }
                     w[j] = 1.0; w[old] -= 1.0;
                 }
+                free(was_empty);
             }
         }
         int argmax = 0;
