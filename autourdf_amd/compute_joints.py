@@ -128,20 +128,29 @@ def optimize_joint_axis(poses_parent, poses_child, axes, poses):
     return principal_axis, global_axes, (Tc @ local)[:3], local
 
 
+def _tree_pairs(links):
+    """The tree's joints as (parent, child) indices into ``links``, in the links' order."""
+    by_id = {l["id"]: i for i, l in enumerate(links)}
+    return [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+
+
+def _need_a_turning_step(count, pid, cid):
+    if count == 0:
+        raise ValueError(f"joint between parent link {pid} and child link {cid}: no step turns the child by at least "
+                         f"{ops.JOINT_THETA_MIN} rad relative to the parent, its axis is undefined")
+
+
 def estimate_joint_axes_from_tree(links, cm_list, start_step=0, num_steps=500, interval=1):
     """Joint axes between connected links of the kinematics tree (compute_joints.py:216-268), one launch.  Returns the
     reference's list of dicts (parent_link, child_link, local_axis, local_pos, global_pos, global_axis) in its order.
     A joint without a usable step (the child never turns relative to its parent) raises ValueError."""
-    by_id = {l["id"]: i for i, l in enumerate(links)}
-    pairs = [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+    pairs = _tree_pairs(links)
     out = ops.joint_axes(_coords(cm_list), [list(l["cluster_idx"]) for l in links], pairs, start_step, num_steps, interval)
     res = {k: out[k].cpu().numpy() for k in ("local_axis", "local_pos", "global_pos", "global_axis", "count")}
     joint_data = []
     for j, (p, c) in enumerate(pairs):
         pid, cid = links[p]["id"], links[c]["id"]
-        if res["count"][j] == 0:
-            raise ValueError(f"joint between parent link {pid} and child link {cid}: no step turns the child by at least "
-                             f"{ops.JOINT_THETA_MIN} rad relative to the parent, its axis is undefined")
+        _need_a_turning_step(res["count"][j], pid, cid)
         print(f"Joint between parent link {pid} and child link {cid}: axis {res['local_axis'][j]}")
         joint_data.append({"parent_link": pid, "child_link": cid, "local_axis": res["local_axis"][j],
                            "local_pos": res["local_pos"][j], "global_pos": res["global_pos"][j],
@@ -165,8 +174,7 @@ def estimate_typed_joints_from_tree(links, cm_list, start_step=0, num_steps=500,
     ``start_step``; a fixed joint has the same point and a NaN axis.  ValueError for a joint without a finite sample, or for
     a revolute one whose axis is undefined (possible only with ``turn_min`` below ``ops.JOINT_THETA_MIN``)."""
     turn_min = ops.JOINT_THETA_MIN if turn_min is None else turn_min
-    by_id = {l["id"]: i for i, l in enumerate(links)}
-    pairs = [(by_id[l["parent_id"]], i) for i, l in enumerate(links) if l["parent_id"] is not None]
+    pairs = _tree_pairs(links)
     coords, clusters = _coords(cm_list), [list(l["cluster_idx"]) for l in links]
     kinds = ops.joint_types(coords, clusters, pairs, start_step, num_steps, interval, turn_min, slide_min)
     axes = ops.joint_axes(coords, clusters, pairs, start_step, num_steps, interval)
@@ -180,9 +188,7 @@ def estimate_typed_joints_from_tree(links, cm_list, start_step=0, num_steps=500,
                              f"undefined")
         name = JOINT_TYPE_NAMES[int(typ["type"][j])]
         if name == "revolute":
-            if res["count"][j] == 0:
-                raise ValueError(f"joint between parent link {pid} and child link {cid}: no step turns the child by at least "
-                                 f"{ops.JOINT_THETA_MIN} rad relative to the parent, its axis is undefined")
+            _need_a_turning_step(res["count"][j], pid, cid)
             jd = {k: res[k][j] for k in ("local_axis", "local_pos", "global_pos", "global_axis")}
         else:
             jd = {"local_axis": typ["slide_axis"][j], "local_pos": np.array([0.0, 0.0, 0.0, 1.0]),

@@ -20,6 +20,9 @@
 //
 // Motion error (k_motion_error, one thread per (pose, link)): how differently a link moved from its reference pose under
 // two descriptions, Ma = A A0^-1 against Mb = B B0^-1, as an angle and as the distance between the images of one point.
+//
+// Every angle here is atan2 of skew_and_cos and norm3 of joints_dev.h, the expressions k_joint_axes and k_joint_types
+// use.  The two series entries differ in their samples kernel only and share the rest as joint_series below.
 #include <climits>
 #include "creg_common.h"
 #include "joints_dev.h"
@@ -38,14 +41,6 @@ __device__ inline void load_rigid(const double* __restrict__ M, double R[9], dou
         t[r] = M[4 * r + 3];
     }
 }
-
-// sin(angle) axis and cos(angle) of a rotation matrix: v = vee of the skew part, c = (trace - 1) / 2
-__device__ inline void skew_and_cos(const double R[9], double v[3], double& c) {
-    v[0] = (R[7] - R[5]) * 0.5; v[1] = (R[2] - R[6]) * 0.5; v[2] = (R[3] - R[1]) * 0.5;
-    c = (((R[0] + R[4]) + R[8]) - 1.0) * 0.5;
-}
-
-__device__ inline double norm3(const double v[3]) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
 
 __global__ __launch_bounds__(JM_NT) void k_link_poses(const double* __restrict__ coords, int n_poses, int K, int L,
                                                       const int32_t* __restrict__ cl, const int32_t* __restrict__ off,
@@ -274,10 +269,32 @@ extern "C" int creg_link_poses_f64(const double* coords, int32_t S, int32_t T, i
                                    const int32_t* link_offsets, int32_t n_link_clusters, int32_t L, double* link_T,
                                    creg_stream_t stream) {
     CREG_REQUIRE(coords && link_clusters && link_offsets && link_T, "creg_link_poses_f64: null pointer");
-    CREG_REQUIRE(S >= 1 && T >= 1 && K >= 1 && K <= 256 && L >= 1 && n_link_clusters >= 1 && (int64_t)S * T * L <= INT_MAX,
-                 "creg_link_poses_f64: bad size (S=%d, T=%d, K=%d, L=%d; K <= 256, S*T*L < 2^31)", S, T, K, L);
+    CREG_REQUIRE(S >= 1 && T >= 1 && K >= 1 && K <= JOINT_MAX_K && L >= 1 && n_link_clusters >= 1 && (int64_t)S * T * L <= INT_MAX,
+                 "creg_link_poses_f64: bad size (S=%d, T=%d, K=%d, L=%d; K <= %d, S*T*L < 2^31)", S, T, K, L, JOINT_MAX_K);
     hipLaunchKernelGGL(k_link_poses, dim3(cdiv((int64_t)S * T * L, JM_NT)), dim3(JM_NT), 0, (hipStream_t)stream, coords, S * T, K, L,
                        link_clusters, link_offsets, n_link_clusters, link_T);
+    CREG_LAUNCH_CHECK();
+    return CREG_OK;
+}
+
+// creg_joint_positions_f64 and creg_joint_slides_f64 but for their samples kernel: the checks, the J == 0 return before
+// any pointer is looked at, the entry's own samples launch (`samples(grid, stream)`, over (joint, sequence)) and
+// k_joint_summary.  `inputs` says that the entry's own input pointers are set.
+template <class Samples>
+static int joint_series(const char* who, int32_t S, int32_t T, int32_t L, const int32_t* joints, int32_t J, int32_t ref_seq,
+                        int32_t ref_step, int32_t start_step, int32_t num_steps, bool inputs, double* q, double* tilt,
+                        double* slip, double* summary, int32_t* where, creg_stream_t stream, Samples samples) {
+    CREG_REQUIRE(S >= 1 && S <= 65535 && T >= 1 && L >= 1 && J >= 0, "%s: bad size (S=%d, T=%d, L=%d, J=%d; S <= 65535)", who, S, T, L, J);
+    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && (int64_t)start_step + num_steps <= T && (int64_t)S * num_steps <= INT_MAX,
+                 "%s: steps [%d, %d + %d) out of range for T=%d", who, start_step, start_step, num_steps, T);
+    CREG_REQUIRE(ref_seq >= 0 && ref_seq < S && ref_step >= 0 && ref_step < T, "%s: reference pose (%d, %d) outside (S=%d, T=%d)", who,
+                 ref_seq, ref_step, S, T);
+    if (J == 0) return CREG_OK;
+    CREG_REQUIRE(inputs && joints && q && tilt && slip && summary && where, "%s: null pointer", who);
+    samples(dim3(J, S), (hipStream_t)stream);
+    CREG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_joint_summary, dim3(J), dim3(JM_NT), 0, (hipStream_t)stream, q, tilt, slip, joints, L, S, num_steps, summary,
+                       where);
     CREG_LAUNCH_CHECK();
     return CREG_OK;
 }
@@ -286,43 +303,22 @@ extern "C" int creg_joint_positions_f64(const double* link_T, int32_t S, int32_t
                                         const double* local_axis, const double* local_pos, int32_t ref_seq, int32_t ref_step,
                                         int32_t start_step, int32_t num_steps, double* q, double* tilt, double* slip,
                                         double* summary, int32_t* where, creg_stream_t stream) {
-    CREG_REQUIRE(S >= 1 && S <= 65535 && T >= 1 && L >= 1 && J >= 0, "creg_joint_positions_f64: bad size (S=%d, T=%d, L=%d, J=%d; S <= 65535)",
-                 S, T, L, J);
-    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && (int64_t)start_step + num_steps <= T && (int64_t)S * num_steps <= INT_MAX,
-                 "creg_joint_positions_f64: steps [%d, %d + %d) out of range for T=%d", start_step, start_step, num_steps, T);
-    CREG_REQUIRE(ref_seq >= 0 && ref_seq < S && ref_step >= 0 && ref_step < T,
-                 "creg_joint_positions_f64: reference pose (%d, %d) outside (S=%d, T=%d)", ref_seq, ref_step, S, T);
-    if (J == 0) return CREG_OK;
-    CREG_REQUIRE(link_T && joints && local_axis && local_pos && q && tilt && slip && summary && where,
-                 "creg_joint_positions_f64: null pointer");
-    hipLaunchKernelGGL(k_joint_samples, dim3(J, S), dim3(JM_NT), 0, (hipStream_t)stream, link_T, T, L, joints, local_axis, local_pos,
-                       ref_seq, ref_step, start_step, num_steps, S, q, tilt, slip);
-    CREG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_joint_summary, dim3(J), dim3(JM_NT), 0, (hipStream_t)stream, q, tilt, slip, joints, L, S, num_steps, summary,
-                       where);
-    CREG_LAUNCH_CHECK();
-    return CREG_OK;
+    return joint_series("creg_joint_positions_f64", S, T, L, joints, J, ref_seq, ref_step, start_step, num_steps,
+                        link_T && local_axis && local_pos, q, tilt, slip, summary, where, stream, [&](dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(k_joint_samples, grid, dim3(JM_NT), 0, st, link_T, T, L, joints, local_axis, local_pos, ref_seq, ref_step,
+                           start_step, num_steps, S, q, tilt, slip);
+    });
 }
 
 extern "C" int creg_joint_slides_f64(const double* link_T, int32_t S, int32_t T, int32_t L, const int32_t* joints, int32_t J,
                                      const double* local_axis, int32_t ref_seq, int32_t ref_step, int32_t start_step,
                                      int32_t num_steps, double* q, double* tilt, double* slip, double* summary, int32_t* where,
                                      creg_stream_t stream) {
-    CREG_REQUIRE(S >= 1 && S <= 65535 && T >= 1 && L >= 1 && J >= 0, "creg_joint_slides_f64: bad size (S=%d, T=%d, L=%d, J=%d; S <= 65535)",
-                 S, T, L, J);
-    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && (int64_t)start_step + num_steps <= T && (int64_t)S * num_steps <= INT_MAX,
-                 "creg_joint_slides_f64: steps [%d, %d + %d) out of range for T=%d", start_step, start_step, num_steps, T);
-    CREG_REQUIRE(ref_seq >= 0 && ref_seq < S && ref_step >= 0 && ref_step < T,
-                 "creg_joint_slides_f64: reference pose (%d, %d) outside (S=%d, T=%d)", ref_seq, ref_step, S, T);
-    if (J == 0) return CREG_OK;
-    CREG_REQUIRE(link_T && joints && local_axis && q && tilt && slip && summary && where, "creg_joint_slides_f64: null pointer");
-    hipLaunchKernelGGL(k_slide_samples, dim3(J, S), dim3(JM_NT), 0, (hipStream_t)stream, link_T, T, L, joints, local_axis, ref_seq,
-                       ref_step, start_step, num_steps, S, q, tilt, slip);
-    CREG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_joint_summary, dim3(J), dim3(JM_NT), 0, (hipStream_t)stream, q, tilt, slip, joints, L, S, num_steps, summary,
-                       where);
-    CREG_LAUNCH_CHECK();
-    return CREG_OK;
+    return joint_series("creg_joint_slides_f64", S, T, L, joints, J, ref_seq, ref_step, start_step, num_steps, link_T && local_axis, q,
+                        tilt, slip, summary, where, stream, [&](dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(k_slide_samples, grid, dim3(JM_NT), 0, st, link_T, T, L, joints, local_axis, ref_seq, ref_step, start_step,
+                           num_steps, S, q, tilt, slip);
+    });
 }
 
 extern "C" int creg_motion_error_f64(const double* A, const double* A0, const double* B, const double* B0, const double* point,

@@ -3,8 +3,9 @@
 // workgroup of 256 threads per joint, thread tid taking samples tid, tid + 256, ... of the sequence-major / phase / step
 // enumeration (sample_steps of joints_dev.h).
 //
-// Per sample the relative motion D = X_{i-1}^-1 X_i = [R t] is built exactly as k_joint_axes builds it, and its angle
-// theta = atan2(|v(R)|, c(R)) by the expressions of screw_axis, so sample_angle has k_joint_axes' bits.  A sample turns
+// Per sample the relative motion D = X_{i-1}^-1 X_i = [R t] is joint_sample_motion of joints_dev.h, the function
+// k_joint_axes calls, and its angle theta = atan2(|v(R)|, c(R)) comes from skew_and_cos and norm3 of the same header,
+// which screw_axis calls too, so sample_angle has k_joint_axes' bits.  A sample turns
 // (theta >= turn_min), slides (it does not turn and |t| >= slide_min), stands still, or is bad (not finite).  A joint with
 // a turning sample is revolute, else one with a sliding sample prismatic, else one with a still sample fixed.  The slide
 // direction is the top eigenvector of sum t t^T over the slide samples, signed by the first of them; its six sums run per
@@ -15,12 +16,11 @@
 #include "creg_common.h"
 #include "creg_dev.h"
 #include "joints_dev.h"
+#include "joints_host.h"
 
 namespace creg {
 
 constexpr int JT_NT = 256;
-constexpr int JT_MAX_K = 256;
-constexpr int JT_MAX_SAMPLES = 4096;
 
 __global__ __launch_bounds__(JT_NT) void k_joint_types(
     const double* __restrict__ coords, int S, int T, int K, const int32_t* __restrict__ cl, const int32_t* __restrict__ off,
@@ -40,26 +40,11 @@ __global__ __launch_bounds__(JT_NT) void k_joint_types(
     int n[4] = {0, 0, 0, 0};                                      // still, turn, slide, bad
     int first = INT_MAX;                                          // this thread's first slide sample
     for (int i = tid; i < NS; i += JT_NT) {
-        const int seq = i / per_seq;
-        int i0, i1;
-        sample_steps(i - seq * per_seq, start, num_steps, interval, i0, i1);
-        const double* c0 = coords + ((size_t)seq * T + i0) * K * 7;
-        const double* c1 = coords + ((size_t)seq * T + i1) * K * 7;
-        double tp0[3], tc0[3], tp1[3], tc1[3], Rp0[9], Rc0[9], Rp1[9], Rc1[9], q[4];
-        link_mean_pose(c0, K, P.idx, P.n, tp0, q, Rp0);
-        link_mean_pose(c0, K, C.idx, C.n, tc0, q, Rc0);
-        link_mean_pose(c1, K, P.idx, P.n, tp1, q, Rp1);
-        link_mean_pose(c1, K, C.idx, C.n, tc1, q, Rc1);
-        double x0t[3], x0R[9], x1t[3], x1R[9], t[3], R[9];
-        child_in_parent(tp0, Rp0, tc0, Rc0, x0t, x0R);
-        child_in_parent(tp1, Rp1, tc1, Rc1, x1t, x1R);
-        child_in_parent(x0t, x0R, x1t, x1R, t, R);                // X_{i-1}^-1 X_i
-        // screw_axis's own expressions (joints.hip), so the angle has its bits
-        const double c = (((R[0] + R[4]) + R[8]) - 1.0) * 0.5;
-        const double v[3] = {(R[7] - R[5]) * 0.5, (R[2] - R[6]) * 0.5, (R[3] - R[1]) * 0.5};
-        const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-        const double th = atan2(s, c);
-        const double len = sqrt((t[0] * t[0] + t[1] * t[1]) + t[2] * t[2]);
+        double t[3], R[9], v[3], c;                               // X_{i-1}^-1 X_i of sample i (sample_steps() order)
+        joint_sample_motion(coords, T, K, P, C, i, per_seq, start, num_steps, interval, t, R);
+        skew_and_cos(R, v, c);                                    // as screw_axis (joints.hip): the angle has its bits
+        const double th = atan2(norm3(v), c);
+        const double len = norm3(t);
         int kind;
         if (!(isfinite(th) && isfinite(t[0]) && isfinite(t[1]) && isfinite(t[2]))) kind = -1;
         else if (th >= turn_min) kind = 1;
@@ -132,16 +117,10 @@ extern "C" int creg_joint_types_f64(const double* coords, int32_t S, int32_t T, 
                                     double slide_min, double* sample_angle, double* sample_slide, int32_t* sample_kind,
                                     int32_t* counts, int32_t* type, double* slide_axis, double* global_axis,
                                     double* global_pos, creg_stream_t stream) {
-    CREG_REQUIRE(S >= 1 && T >= 1 && K >= 1 && K <= JT_MAX_K && J >= 0 && L >= 1 && n_link_clusters >= 1,
-                 "creg_joint_types_f64: bad size (S=%d, T=%d, K=%d, L=%d, J=%d; K <= %d)", S, T, K, L, J, JT_MAX_K);
-    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && interval >= 1,
-                 "creg_joint_types_f64: bad steps (start=%d, num=%d, interval=%d)", start_step, num_steps, interval);
-    CREG_REQUIRE((int64_t)start_step + num_steps <= T, "creg_joint_types_f64: step %lld out of range for T=%d",
-                 (long long)start_step + num_steps - 1, T);
+    const int NS = joint_sample_count("creg_joint_types_f64", S, T, K, &L, J, n_link_clusters, start_step, num_steps, interval);
+    if (NS < 0) return CREG_EINVAL;
     CREG_REQUIRE(std::isfinite(turn_min) && turn_min >= 0.0 && std::isfinite(slide_min) && slide_min >= 0.0,
                  "creg_joint_types_f64: turn_min and slide_min must be finite and >= 0 (got %g, %g)", turn_min, slide_min);
-    const int NS = creg_joint_axes_samples(S, num_steps, interval);
-    CREG_REQUIRE(NS <= JT_MAX_SAMPLES, "creg_joint_types_f64: %d samples per joint (max %d)", NS, JT_MAX_SAMPLES);
     if (J == 0) return CREG_OK;
     CREG_REQUIRE(coords && link_clusters && link_offsets && joints && counts && type && slide_axis && global_axis && global_pos,
                  "creg_joint_types_f64: null pointer");

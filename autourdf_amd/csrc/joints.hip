@@ -6,7 +6,8 @@
 // (i - interval, i) of one phase of one sequence.  Per step, a link's mean pose is the mean xyz of its clusters plus the
 // top eigenvector of (1/n) sum q q^T (cyclic Jacobi in registers; the sign is irrelevant, quaternion_to_matrix divides by
 // |q|^2).  With X_i = P_i^-1 C_i the child's pose in the parent's frame, the relative motion of the reference's T_r1 is
-// X_{i-1}^-1 X_i.  Its screw axis comes in closed form (direction from the skew part, from the symmetric part past 90 deg;
+// X_{i-1}^-1 X_i (joint_sample_motion of joints_dev.h, which k_joint_types shares; the limits JOINT_* and the argument
+// checks of joints_host.h are shared likewise).  Its screw axis comes in closed form (direction from the skew part, from the symmetric part past 90 deg;
 // angle atan2(|vee|, (tr - 1) / 2) in [0, pi]; the point of the axis closest to the origin
 // 1/2 (t_perp + cot(theta/2) d x t_perp)), canonicalised as init_position does.  DESIGN N4 has why this equals the
 // reference's eig of the 4x4 wherever that is well-posed.  The principal axis is the top eigenvector of sum a a^T over the
@@ -20,13 +21,11 @@
 #include "creg_common.h"
 #include "creg_dev.h"
 #include "joints_dev.h"
+#include "joints_host.h"
 
 namespace creg {
 
 constexpr int JA_NT = 256;
-constexpr int JA_MAX_K = 256;
-constexpr int JA_MAX_SAMPLES = 4096;
-constexpr double JA_THETA_MIN = 2e-4;   // see creg.h: below ~1.4e-4 rad the reference's own 4x4 eigen test breaks down
 constexpr int LC_NT = 256;
 constexpr int LC_ROWS = 4 * LC_NT;      // output rows per workgroup slice of one (frame, link)
 constexpr int LC_MAX_SLICES = 256;      // grid.y cap; a workgroup strides over slices y, y + G, ...
@@ -34,9 +33,9 @@ constexpr int LC_MAX_SLICES = 256;      // grid.y cap; a workgroup strides over 
 // Screw axis of [R t]: unit direction d and angle theta in [0, pi] with R = rot(d, theta), and the canonical point
 // of the axis (init_position of compute_joints.py:68-77 applied to the point closest to the origin).
 __device__ void screw_axis(const double R[9], const double t[3], double d[3], double& theta, double p[3]) {
-    const double c = (((R[0] + R[4]) + R[8]) - 1.0) * 0.5;
-    const double v[3] = {(R[7] - R[5]) * 0.5, (R[2] - R[6]) * 0.5, (R[3] - R[1]) * 0.5};   // sin(theta) d
-    const double s = sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    double v[3], c;                                       // sin(theta) d, cos(theta)
+    skew_and_cos(R, v, c);
+    const double s = norm3(v);
     theta = atan2(s, c);
     if (c >= 0.0) {
         d[0] = v[0] / s; d[1] = v[1] / s; d[2] = v[2] / s;
@@ -128,23 +127,11 @@ __global__ __launch_bounds__(JA_NT) void k_joint_axes(
     const size_t base = (size_t)jt * NS;
     int first = INT_MAX;
     for (int i = tid; i < NS; i += blockDim.x) {
-        const int seq = i / per_seq;
-        int i0, i1;
-        sample_steps(i - seq * per_seq, start, num_steps, interval, i0, i1);
-        const double* c0 = coords + ((size_t)seq * T + i0) * K * 7;
-        const double* c1 = coords + ((size_t)seq * T + i1) * K * 7;
-        double tp0[3], tc0[3], tp1[3], tc1[3], Rp0[9], Rc0[9], Rp1[9], Rc1[9], q[4];
-        link_mean_pose(c0, K, P.idx, P.n, tp0, q, Rp0);
-        link_mean_pose(c0, K, C.idx, C.n, tc0, q, Rc0);
-        link_mean_pose(c1, K, P.idx, P.n, tp1, q, Rp1);
-        link_mean_pose(c1, K, C.idx, C.n, tc1, q, Rc1);
-        double x0t[3], x0R[9], x1t[3], x1R[9], t[3], R[9];
-        child_in_parent(tp0, Rp0, tc0, Rc0, x0t, x0R);
-        child_in_parent(tp1, Rp1, tc1, Rc1, x1t, x1R);
-        child_in_parent(x0t, x0R, x1t, x1R, t, R);                // X_{i-1}^-1 X_i
+        double t[3], R[9];                                        // X_{i-1}^-1 X_i of sample i (sample_steps() order)
+        joint_sample_motion(coords, T, K, P, C, i, per_seq, start, num_steps, interval, t, R);
         double d[3], th, p[3];
         screw_axis(R, t, d, th, p);
-        const bool ok = th >= JA_THETA_MIN && isfinite(th) && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) &&
+        const bool ok = th >= JOINT_THETA_MIN && isfinite(th) && isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]) &&
                         isfinite(d[0]) && isfinite(d[1]) && isfinite(d[2]);
         s_angle[base + i] = th;
         s_usable[base + i] = ok;
@@ -338,14 +325,8 @@ extern "C" int creg_joint_axes_f64(const double* coords, int32_t S, int32_t T, i
                                    double* first_pose, creg_stream_t stream) {
     CREG_REQUIRE(coords && link_clusters && link_offsets && joints && local_axis && local_pos && global_pos && global_axis &&
                  count, "creg_joint_axes_f64: null pointer");
-    CREG_REQUIRE(S >= 1 && T >= 1 && K >= 1 && K <= JA_MAX_K && J >= 0 && n_link_clusters >= 1,
-                 "creg_joint_axes_f64: bad size (S=%d, T=%d, K=%d, J=%d; K <= %d)", S, T, K, J, JA_MAX_K);
-    CREG_REQUIRE(start_step >= 0 && num_steps >= 1 && interval >= 1,
-                 "creg_joint_axes_f64: bad steps (start=%d, num=%d, interval=%d)", start_step, num_steps, interval);
-    CREG_REQUIRE((int64_t)start_step + num_steps <= T, "creg_joint_axes_f64: step %lld out of range for T=%d",
-                 (long long)start_step + num_steps - 1, T);
-    const int NS = creg_joint_axes_samples(S, num_steps, interval);
-    CREG_REQUIRE(NS <= JA_MAX_SAMPLES, "creg_joint_axes_f64: %d samples per joint (max %d)", NS, JA_MAX_SAMPLES);
+    const int NS = joint_sample_count("creg_joint_axes_f64", S, T, K, nullptr, J, n_link_clusters, start_step, num_steps, interval);
+    if (NS < 0) return CREG_EINVAL;
     CREG_REQUIRE(NS == 0 || (sample_axis && sample_angle && sample_point && sample_usable),
                  "creg_joint_axes_f64: null sample output");
     if (J == 0) return CREG_OK;
@@ -364,8 +345,8 @@ extern "C" int creg_link_clouds_f64(const double* coords, const double* matrices
                                     float* mean_matrices, double* clouds_wf, double* clouds_lf, creg_stream_t stream) {
     CREG_REQUIRE(coords && matrices && link_clusters && link_offsets && point_offsets && out_offsets && link_matrices,
                  "creg_link_clouds_f64: null pointer");
-    CREG_REQUIRE(T >= 1 && K >= 1 && K <= JA_MAX_K && L >= 1 && L <= K && n_link_clusters >= 1 && n_points >= 0 && n_out >= 0,
-                 "creg_link_clouds_f64: bad size (T=%d, K=%d, L=%d; K <= %d)", T, K, L, JA_MAX_K);
+    CREG_REQUIRE(T >= 1 && K >= 1 && K <= JOINT_MAX_K && L >= 1 && L <= K && n_link_clusters >= 1 && n_points >= 0 && n_out >= 0,
+                 "creg_link_clouds_f64: bad size (T=%d, K=%d, L=%d; K <= %d)", T, K, L, JOINT_MAX_K);
     CREG_REQUIRE((n_points == 0 || points) && (n_out == 0 || (clouds_wf && clouds_lf)), "creg_link_clouds_f64: null cloud");
     CREG_REQUIRE(max_link_rows >= 0, "creg_link_clouds_f64: max_link_rows < 0");
     const int64_t slices = (max_link_rows + LC_ROWS - 1) / LC_ROWS;

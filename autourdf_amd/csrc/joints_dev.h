@@ -1,13 +1,21 @@
-// joints_dev.h -- device helpers of the URDF stage's pose arithmetic, fp64, shared by joints.hip (joint axes, link clouds),
-// joint_types.hip (joint kinds) and joint_motion.hip (link poses, joint positions, slides): the top eigenvector by cyclic Jacobi, a link's mean pose
-// (get_cluster_pose_mean), the child's pose in the parent's frame, a link's span of the flat cluster list and the
-// enumeration of a joint's samples, which joint_types.hip shares with joints.hip.
+// joints_dev.h -- what the joint part of the URDF stage shares, fp64: joints.hip (joint axes, link clouds), joint_types.hip
+// (joint kinds) and joint_motion.hip (link poses, joint positions, slides, motion error) all start from here, and so does
+// a new joint kind.  Limits of the stage (ops.py holds the same figures for its own checks); the top eigenvector by cyclic
+// Jacobi; a link's mean pose (get_cluster_pose_mean); the child's pose in the parent's frame; a link's span of the flat
+// cluster list; sin(angle) axis, cos(angle) and |.| of a rotation matrix, whose bits every angle of the stage has; the
+// enumeration of a joint's samples and the relative motion of one of them, which k_joint_axes and k_joint_types both
+// classify.  The host side of those two entries shares its argument checks in joints_host.h.
 // quat_to_matrix is creg_dev.h's, which this header brings in.
 #pragma once
 #include <cstdint>
 #include "creg_dev.h"
 
 namespace creg {
+
+// ops.py repeats these as LINK_SWEEP_MAX_K, JOINT_MAX_SAMPLES and JOINT_THETA_MIN for the checks it makes before a launch.
+constexpr int JOINT_MAX_K = 256;             // clusters per pose table
+constexpr int JOINT_MAX_SAMPLES = 4096;      // samples per joint of k_joint_axes / k_joint_types
+constexpr double JOINT_THETA_MIN = 2e-4;     // see creg.h: below ~1.4e-4 rad the reference's own 4x4 eigen test breaks down
 
 // Top eigenvector of a symmetric N x N matrix (cyclic Jacobi, fp64, registers).  Ties: the first largest diagonal.
 template <int N>
@@ -117,6 +125,14 @@ __device__ inline LinkSpan link_span(const int32_t* cl, const int32_t* off, int 
     return {cl + a, b - a};
 }
 
+// sin(angle) axis and cos(angle) of a rotation matrix: v = vee of the skew part, c = (trace - 1) / 2
+__device__ inline void skew_and_cos(const double R[9], double v[3], double& c) {
+    v[0] = (R[7] - R[5]) * 0.5; v[1] = (R[2] - R[6]) * 0.5; v[2] = (R[3] - R[1]) * 0.5;
+    c = (((R[0] + R[4]) + R[8]) - 1.0) * 0.5;
+}
+
+__device__ inline double norm3(const double v[3]) { return sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]); }
+
 // Sample r of a sequence -> (step_prev, step): phases a = 0..interval-1, then steps, as the reference's loops.
 __device__ inline void sample_steps(int r, int start, int num_steps, int interval, int& i0, int& i1) {
     for (int a = 0; a < interval; ++a) {
@@ -130,6 +146,26 @@ __device__ inline void sample_steps(int r, int start, int num_steps, int interva
         r -= ns;
     }
     i0 = i1 = start;                                      // unreachable: r < samples per sequence
+}
+
+// Relative motion [R t] = X_{i-1}^-1 X_i of sample i of a joint (sequence-major, then sample_steps' order), with
+// X = P^-1 C the child link's mean pose in the parent's frame: the reference's T_r1.
+__device__ inline void joint_sample_motion(const double* __restrict__ coords, int T, int K, LinkSpan P, LinkSpan C, int i,
+                                           int per_seq, int start, int num_steps, int interval, double t[3], double R[9]) {
+    const int seq = i / per_seq;
+    int i0, i1;
+    sample_steps(i - seq * per_seq, start, num_steps, interval, i0, i1);
+    const double* c0 = coords + ((size_t)seq * T + i0) * K * 7;
+    const double* c1 = coords + ((size_t)seq * T + i1) * K * 7;
+    double tp0[3], tc0[3], tp1[3], tc1[3], Rp0[9], Rc0[9], Rp1[9], Rc1[9], q[4];
+    link_mean_pose(c0, K, P.idx, P.n, tp0, q, Rp0);
+    link_mean_pose(c0, K, C.idx, C.n, tc0, q, Rc0);
+    link_mean_pose(c1, K, P.idx, P.n, tp1, q, Rp1);
+    link_mean_pose(c1, K, C.idx, C.n, tc1, q, Rc1);
+    double x0t[3], x0R[9], x1t[3], x1R[9];
+    child_in_parent(tp0, Rp0, tc0, Rc0, x0t, x0R);
+    child_in_parent(tp1, Rp1, tc1, Rc1, x1t, x1R);
+    child_in_parent(x0t, x0R, x1t, x1R, t, R);
 }
 
 }  // namespace creg

@@ -817,22 +817,75 @@ def coord_mst(coords: torch.Tensor):
 
 
 # ------------------------------------------------------------------------------ N4 URDF stage: joint axes, link clouds
+# csrc/joints_dev.h holds the same limits as JOINT_MAX_K (LINK_SWEEP_MAX_K here), JOINT_MAX_SAMPLES and JOINT_THETA_MIN
 JOINT_MAX_SAMPLES = 4096
 JOINT_THETA_MIN = 2e-4             # rad: a sample below it is not usable (creg.h)
 
 
-def _link_table(link_clusters, K, what):
+def _max_clusters(who, K):
+    if K > LINK_SWEEP_MAX_K:
+        raise ValueError(f"{who} supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+
+
+def _link_tables(who, link_clusters, K, dev):
+    """The links' clusters as one flat host list with its offsets, and both as int32 device tables (keep them alive across
+    the launch): (flat, off, cl, lo).  ValueError under ``who``'s name for an empty link or a cluster outside [0, K).
+    ``dev`` None: the host lists alone, for a caller that allocates its outputs before it copies a table -- a host-to-device
+    copy waits for the stream's earlier work, whatever the host does after it no longer overlaps that work."""
     flat, off = [], [0]
     for l, c in enumerate(link_clusters):
         c = [int(x) for x in c]
         if not c:
-            raise ValueError(f"{what}: link {l} has no cluster")
+            raise ValueError(f"{who}: link {l} has no cluster")
         bad = [x for x in c if not 0 <= x < K]
         if bad:
-            raise ValueError(f"{what}: link {l} names clusters {bad} outside [0, {K})")
+            raise ValueError(f"{who}: link {l} names clusters {bad} outside [0, {K})")
         flat.extend(c)
         off.append(len(flat))
-    return flat, off
+    return (flat, off, None, None) if dev is None else (flat, off, *_i32_tables(dev, flat, off))
+
+
+def _i32_tables(dev, *lists):
+    return tuple(torch.tensor(x, dtype=torch.int32, device=dev) for x in lists)
+
+
+def _joint_pairs(who, joints, L):
+    jt = [(int(p), int(c)) for p, c in joints]
+    for p, c in jt:
+        if not (0 <= p < L and 0 <= c < L):
+            raise ValueError(f"{who}: joint ({p}, {c}) names a link outside [0, {L})")
+    return jt
+
+
+def _joint_sample_args(who, coords, link_clusters, joints, start_step, num_steps, interval, outputs):
+    """What joint_axes and joint_types check and build alike, under ``who``'s name: coords, the K cap, the steps (ValueError,
+    then IndexError in numpy's words), the link table, the joint pairs and the sample count; then the caller's
+    ``outputs(J, NS, dev)`` are allocated, and only then the device tables copied (see _link_tables).  Returns (library,
+    head, L, tail, keep, J, NS, out): the entry's leading C arguments up to n_link_clusters, the link count, its arguments
+    from joints to interval, the tensors that must outlive every launch, and what ``outputs`` returned."""
+    lib = _lib.load()
+    coords = _need(coords, torch.float64, "coords")
+    if coords.dim() != 4 or coords.shape[3] != 7:
+        raise ValueError(f"{who}: coords must be (S,T,K,7)")
+    S, T, K = coords.shape[:3]
+    _max_clusters(who, K)
+    start_step, num_steps, interval = int(start_step), int(num_steps), int(interval)
+    if start_step < 0 or num_steps < 1 or interval < 1:
+        raise ValueError(f"{who}: need start_step >= 0, num_steps >= 1, interval >= 1 "
+                         f"(got {start_step}, {num_steps}, {interval})")
+    if start_step + num_steps > T:
+        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 0 with size {T}")
+    flat, off, _, _ = _link_tables(who, link_clusters, K, None)
+    L = len(off) - 1
+    jt = _joint_pairs(who, joints, L)
+    NS = joint_samples(S, num_steps, interval)
+    if NS > JOINT_MAX_SAMPLES:
+        raise ValueError(f"{who}: {NS} samples per joint, at most {JOINT_MAX_SAMPLES} are supported")
+    J, dev = len(jt), coords.device
+    out = outputs(J, NS, dev)
+    cl, lo, jn = _i32_tables(dev, flat, off, jt or [(0, 0)])
+    return (lib, (_p(coords), S, T, K, _p(cl), _p(lo), len(flat)), L, (_p(jn), J, start_step, num_steps, interval),
+            (coords, cl, lo, jn), J, NS, out)
 
 
 def joint_samples(S: int, num_steps: int, interval: int) -> int:
@@ -858,46 +911,22 @@ def joint_axes_prepare(coords: torch.Tensor, link_clusters, joints, start_step: 
                        interval: int = 1):
     """Checks and device tables of joint_axes, done once: returns (launch, outputs), where launch() only enqueues
     creg_joint_axes_f64 on the current stream (sample_usable stays int32 here)."""
-    L = _lib.load()
-    coords = _need(coords, torch.float64, "coords")
-    if coords.dim() != 4 or coords.shape[3] != 7:
-        raise ValueError("joint_axes: coords must be (S,T,K,7)")
-    S, T, K = coords.shape[:3]
-    if K > LINK_SWEEP_MAX_K:
-        raise ValueError(f"joint_axes supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
-    start_step, num_steps, interval = int(start_step), int(num_steps), int(interval)
-    if start_step < 0 or num_steps < 1 or interval < 1:
-        raise ValueError(f"joint_axes: need start_step >= 0, num_steps >= 1, interval >= 1 "
-                         f"(got {start_step}, {num_steps}, {interval})")
-    if start_step + num_steps > T:
-        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 0 with size {T}")
-    flat, off = _link_table(link_clusters, K, "joint_axes")
-    jt = [(int(p), int(c)) for p, c in joints]
-    for p, c in jt:
-        if not (0 <= p < len(off) - 1 and 0 <= c < len(off) - 1):
-            raise ValueError(f"joint_axes: joint ({p}, {c}) names a link outside [0, {len(off) - 1})")
-    NS = joint_samples(S, num_steps, interval)
-    if NS > JOINT_MAX_SAMPLES:
-        raise ValueError(f"joint_axes: {NS} samples per joint, at most {JOINT_MAX_SAMPLES} are supported")
-    dev, J = coords.device, len(jt)
-    i32 = dict(dtype=torch.int32, device=dev)
-    f64 = dict(dtype=torch.float64, device=dev)
-    cl = torch.tensor(flat, **i32)
-    lo = torch.tensor(off, **i32)
-    jn = torch.tensor(jt, **i32).reshape(-1, 2) if J else torch.zeros(1, 2, **i32)
-    out = {"sample_axis": torch.empty(J, NS, 3, **f64), "sample_angle": torch.empty(J, NS, **f64),
-           "sample_point": torch.empty(J, NS, 3, **f64), "sample_usable": torch.empty(J, NS, **i32),
-           "local_axis": torch.empty(J, 3, **f64), "local_pos": torch.empty(J, 4, **f64),
-           "global_pos": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
-           "count": torch.zeros(J, **i32), "first_pose": torch.empty(J, 2, 7, **f64)}
+    def outputs(J, NS, dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        return {"sample_axis": torch.empty(J, NS, 3, **f64), "sample_angle": torch.empty(J, NS, **f64),
+                "sample_point": torch.empty(J, NS, 3, **f64), "sample_usable": torch.empty(J, NS, **i32),
+                "local_axis": torch.empty(J, 3, **f64), "local_pos": torch.empty(J, 4, **f64),
+                "global_pos": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
+                "count": torch.zeros(J, **i32), "first_pose": torch.empty(J, 2, 7, **f64)}
+    L, head, _, tail, keep, J, NS, out = _joint_sample_args("joint_axes", coords, link_clusters, joints, start_step, num_steps,
+                                                            interval, outputs)
     smp = (_p(out["sample_axis"]), _p(out["sample_angle"]), _p(out["sample_point"]),
            _p(out["sample_usable"])) if NS else (None, None, None, None)
-    args = (_p(coords), S, T, K, _p(cl), _p(lo), len(flat), _p(jn), J, start_step, num_steps, interval, *smp,
-            _p(out["local_axis"]), _p(out["local_pos"]), _p(out["global_pos"]), _p(out["global_axis"]), _p(out["count"]),
-            _p(out["first_pose"]))
-    keep = (coords, cl, lo, jn)                                    # the tables must outlive every launch
+    args = (*head, *tail, *smp, _p(out["local_axis"]), _p(out["local_pos"]), _p(out["global_pos"]), _p(out["global_axis"]),
+            _p(out["count"]), _p(out["first_pose"]))
 
-    def launch():
+    def launch():                                                  # returns the tables, which must outlive every launch
         if J:
             _lib.check(L.creg_joint_axes_f64(*args, _stream()), "creg_joint_axes_f64")
         return keep
@@ -919,42 +948,18 @@ def joint_types(coords: torch.Tensor, link_clusters, joints, start_step: int = 0
     turn_min, slide_min = float(turn_min), float(slide_min)
     if not (np.isfinite(turn_min) and turn_min >= 0.0 and np.isfinite(slide_min) and slide_min >= 0.0):
         raise ValueError(f"joint_types: turn_min and slide_min must be finite and >= 0 (got {turn_min}, {slide_min})")
-    L_ = _lib.load()
-    coords = _need(coords, torch.float64, "coords")
-    if coords.dim() != 4 or coords.shape[3] != 7:
-        raise ValueError("joint_types: coords must be (S,T,K,7)")
-    S, T, K = coords.shape[:3]
-    if K > LINK_SWEEP_MAX_K:
-        raise ValueError(f"joint_types supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
-    start_step, num_steps, interval = int(start_step), int(num_steps), int(interval)
-    if start_step < 0 or num_steps < 1 or interval < 1:
-        raise ValueError(f"joint_types: need start_step >= 0, num_steps >= 1, interval >= 1 "
-                         f"(got {start_step}, {num_steps}, {interval})")
-    if start_step + num_steps > T:
-        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 0 with size {T}")
-    flat, off = _link_table(link_clusters, K, "joint_types")
-    L = len(off) - 1
-    jt = [(int(p), int(c)) for p, c in joints]
-    for p, c in jt:
-        if not (0 <= p < L and 0 <= c < L):
-            raise ValueError(f"joint_types: joint ({p}, {c}) names a link outside [0, {L})")
-    NS = joint_samples(S, num_steps, interval)
-    if NS > JOINT_MAX_SAMPLES:
-        raise ValueError(f"joint_types: {NS} samples per joint, at most {JOINT_MAX_SAMPLES} are supported")
-    dev, J = coords.device, len(jt)
-    i32 = dict(dtype=torch.int32, device=dev)
-    f64 = dict(dtype=torch.float64, device=dev)
-    out = {"sample_angle": torch.empty(J, NS, **f64), "sample_slide": torch.empty(J, NS, 3, **f64),
-           "sample_kind": torch.empty(J, NS, **i32), "counts": torch.empty(J, 4, **i32), "type": torch.empty(J, **i32),
-           "slide_axis": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
-           "global_pos": torch.empty(J, 3, **f64)}
+    def outputs(J, NS, dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        f64 = dict(dtype=torch.float64, device=dev)
+        return {"sample_angle": torch.empty(J, NS, **f64), "sample_slide": torch.empty(J, NS, 3, **f64),
+                "sample_kind": torch.empty(J, NS, **i32), "counts": torch.empty(J, 4, **i32), "type": torch.empty(J, **i32),
+                "slide_axis": torch.empty(J, 3, **f64), "global_axis": torch.empty(J, 3, **f64),
+                "global_pos": torch.empty(J, 3, **f64)}
+    L_, head, L, tail, keep, J, NS, out = _joint_sample_args("joint_types", coords, link_clusters, joints, start_step, num_steps,
+                                                             interval, outputs)    # keep: the tables live until the call is enqueued
     if J:
-        cl = torch.tensor(flat, **i32)
-        lo = torch.tensor(off, **i32)
-        jn = torch.tensor(jt, **i32).reshape(-1, 2)
         smp = (_p(out["sample_angle"]), _p(out["sample_slide"]), _p(out["sample_kind"])) if NS else (None, None, None)
-        _lib.check(L_.creg_joint_types_f64(_p(coords), S, T, K, _p(cl), _p(lo), len(flat), L, _p(jn), J, start_step, num_steps,
-                                           interval, turn_min, slide_min, *smp, _p(out["counts"]), _p(out["type"]),
+        _lib.check(L_.creg_joint_types_f64(*head, L, *tail, turn_min, slide_min, *smp, _p(out["counts"]), _p(out["type"]),
                                            _p(out["slide_axis"]), _p(out["global_axis"]), _p(out["global_pos"]), _stream()),
                    "creg_joint_types_f64")
     return out
@@ -989,11 +994,10 @@ def link_clouds_prepare(coords: torch.Tensor, matrices: torch.Tensor, link_clust
     if coords.dim() != 3 or coords.shape[2] != 7 or tuple(matrices.shape) != tuple(coords.shape[:2]) + (4, 4):
         raise ValueError("link_clouds: coords must be (T,K,7) and matrices (T,K,4,4)")
     T, K = coords.shape[:2]
-    if K > LINK_SWEEP_MAX_K:
-        raise ValueError(f"link_clouds supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
+    _max_clusters("link_clouds", K)
     if points.dim() != 2 or points.shape[1] != 3:
         raise ValueError("link_clouds: points must be (N,3)")
-    flat, off = _link_table(link_clusters, K, "link_clouds")
+    flat, off, _, _ = _link_tables("link_clouds", link_clusters, K, None)
     L = len(off) - 1
     po = np.asarray(point_offsets, np.int64)
     if po.shape != (T * K + 1,) or po[0] != 0 or np.any(np.diff(po) < 0) or po[-1] != points.shape[0]:
@@ -1008,8 +1012,7 @@ def link_clouds_prepare(coords: torch.Tensor, matrices: torch.Tensor, link_clust
     mm = torch.empty(T, L, 4, 4, dtype=torch.float32, device=dev) if mean_matrices else None
     wf = torch.empty(max(n_out, 1), 3, dtype=torch.float64, device=dev)
     lf = torch.empty(max(n_out, 1), 3, dtype=torch.float64, device=dev)
-    cl = torch.tensor(flat, dtype=torch.int32, device=dev)          # named: they must outlive the launch call
-    lo = torch.tensor(off, dtype=torch.int32, device=dev)
+    cl, lo = _i32_tables(dev, flat, off)                           # named: they must outlive the launch call
     po_d, oo_d = torch.from_numpy(po).to(dev), torch.from_numpy(oo).to(dev)
     args = (_p(coords), _p(matrices), T, K, _p(cl), _p(lo), len(flat), L, _p(points) if points.shape[0] else None,
             _p(po_d), int(po[-1]), _p(oo_d), n_out, int(per.max()), _p(lm), _p(mm), _p(wf), _p(lf))
@@ -1031,15 +1034,12 @@ def link_poses(coords: torch.Tensor, link_clusters):
     if coords.dim() != 4 or coords.shape[3] != 7 or 0 in coords.shape[:3]:
         raise ValueError(f"link_poses: coords must be (S,T,K,7) with S, T, K >= 1, got {tuple(coords.shape)}")
     S, T, K = coords.shape[:3]
-    if K > LINK_SWEEP_MAX_K:
-        raise ValueError(f"link_poses supports at most {LINK_SWEEP_MAX_K} clusters, got {K}")
-    flat, off = _link_table(link_clusters, K, "link_poses")
+    _max_clusters("link_poses", K)
+    dev = coords.device
+    flat, off, cl, lo = _link_tables("link_poses", link_clusters, K, dev)
     L = len(off) - 1
     if L < 1 or S * T * L >= 2 ** 31:
         raise ValueError(f"link_poses: need 1 <= S*T*L < 2^31 (S={S}, T={T}, L={L})")
-    dev = coords.device
-    cl = torch.tensor(flat, dtype=torch.int32, device=dev)
-    lo = torch.tensor(off, dtype=torch.int32, device=dev)
     link_T = torch.empty(S, T, L, 4, 4, dtype=torch.float64, device=dev)
     _lib.check(L_.creg_link_poses_f64(_p(coords), S, T, K, _p(cl), _p(lo), len(flat), L, _p(link_T), _stream()), "creg_link_poses_f64")
     return link_T
@@ -1055,31 +1055,38 @@ def joint_positions(link_T: torch.Tensor, joints, local_axis, local_pos, ref_seq
     upper, tilt_rms, tilt_max, slip_rms, slip_max (J) f64; n_used (J) int32; lower_at, upper_at (J,2) int32 = (sequence,
     step - start_step), -1 where n_used is 0.  IndexError for steps or a reference pose outside link_T, ValueError for
     shapes and link indices, all before any launch."""
+    def axis_and_pos(J, ax, dev):
+        lp = torch.as_tensor(local_pos, dtype=torch.float64, device=dev)
+        if lp.numel() == 0:
+            lp = lp.reshape(0, 4)
+        if ax.shape[0] != J or lp.dim() != 2 or lp.shape[0] != J or (J and lp.shape[1] not in (3, 4)):
+            raise ValueError(f"joint_positions: local_axis must be ({J},3) and local_pos ({J},3) or ({J},4), got "
+                             f"{tuple(ax.shape)} and {tuple(lp.shape)}")
+        if J and lp.shape[1] == 3:
+            lp = torch.cat([lp, torch.ones(J, 1, dtype=torch.float64, device=dev)], dim=1)
+        return (lp.contiguous(),)
+    return _joint_series("joint_positions", "creg_joint_positions_f64", link_T, joints, local_axis, axis_and_pos, ref_seq, ref_step,
+                         start_step, num_steps)
+
+
+def _joint_series(who, entry, link_T, joints, local_axis, extra_args, ref_seq, ref_step, start_step, num_steps):
+    """joint_positions and joint_slides but for their entry: the checks under ``who``'s name, the allocation, the call of
+    ``entry`` and the output dict.  ``extra_args(J, ax, dev)`` checks the rows of local_axis, with whatever else the entry
+    takes after it, and returns those further tensors."""
     L_ = _lib.load()
     link_T = _need(link_T, torch.float64, "link_T")
     if link_T.dim() != 5 or tuple(link_T.shape[3:]) != (4, 4) or 0 in link_T.shape[:3]:
-        raise ValueError(f"joint_positions: link_T must be (S,T,L,4,4) with S, T, L >= 1, got {tuple(link_T.shape)}")
+        raise ValueError(f"{who}: link_T must be (S,T,L,4,4) with S, T, L >= 1, got {tuple(link_T.shape)}")
     S, T, L = link_T.shape[:3]
     dev = link_T.device
-    jt = [(int(p), int(c)) for p, c in joints]
+    jt = _joint_pairs(who, joints, L)
     J = len(jt)
-    for p, c in jt:
-        if not (0 <= p < L and 0 <= c < L):
-            raise ValueError(f"joint_positions: joint ({p}, {c}) names a link outside [0, {L})")
     ax = _need(torch.as_tensor(local_axis, dtype=torch.float64, device=dev).reshape(-1, 3), torch.float64, "local_axis")
-    lp = torch.as_tensor(local_pos, dtype=torch.float64, device=dev)
-    if lp.numel() == 0:
-        lp = lp.reshape(0, 4)
-    if ax.shape[0] != J or lp.dim() != 2 or lp.shape[0] != J or (J and lp.shape[1] not in (3, 4)):
-        raise ValueError(f"joint_positions: local_axis must be ({J},3) and local_pos ({J},3) or ({J},4), got "
-                         f"{tuple(ax.shape)} and {tuple(lp.shape)}")
-    if J and lp.shape[1] == 3:
-        lp = torch.cat([lp, torch.ones(J, 1, dtype=torch.float64, device=dev)], dim=1)
-    lp = lp.contiguous()
+    extra = extra_args(J, ax, dev)
     start_step, ref_seq, ref_step = int(start_step), int(ref_seq), int(ref_step)
     num_steps = T - start_step if num_steps is None else int(num_steps)
     if start_step < 0 or num_steps < 1:
-        raise ValueError(f"joint_positions: need start_step >= 0 and num_steps >= 1 (got {start_step}, {num_steps})")
+        raise ValueError(f"{who}: need start_step >= 0 and num_steps >= 1 (got {start_step}, {num_steps})")
     if start_step + num_steps > T:
         raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 1 with size {T}")
     if not 0 <= ref_seq < S:
@@ -1087,16 +1094,15 @@ def joint_positions(link_T: torch.Tensor, joints, local_axis, local_pos, ref_seq
     if not 0 <= ref_step < T:
         raise IndexError(f"index {ref_step} is out of bounds for axis 1 with size {T}")
     if S > 65535 or S * num_steps >= 2 ** 31:
-        raise ValueError(f"joint_positions: at most 65535 sequences and 2^31 samples per joint (S={S}, num_steps={num_steps})")
+        raise ValueError(f"{who}: at most 65535 sequences and 2^31 samples per joint (S={S}, num_steps={num_steps})")
     f64 = dict(dtype=torch.float64, device=dev)
     q, tilt, slip = (torch.empty(J, S, num_steps, **f64) for _ in range(3))
     summary = torch.empty(J, 6, **f64)
     where = torch.empty(J, 5, dtype=torch.int32, device=dev)
     if J:
         jn = torch.tensor(jt, dtype=torch.int32, device=dev).reshape(-1, 2)
-        _lib.check(L_.creg_joint_positions_f64(_p(link_T), S, T, L, _p(jn), J, _p(ax), _p(lp), ref_seq, ref_step, start_step,
-                                               num_steps, _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()),
-                   "creg_joint_positions_f64")
+        _lib.check(getattr(L_, entry)(_p(link_T), S, T, L, _p(jn), J, _p(ax), *map(_p, extra), ref_seq, ref_step, start_step,
+                                      num_steps, _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()), entry)
     out = {"q": q, "tilt": tilt, "slip": slip}
     for i, k in enumerate(("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")):
         out[k] = summary[:, i]
@@ -1110,46 +1116,12 @@ def joint_slides(link_T: torch.Tensor, joints, local_axis, ref_seq: int = 0, ref
     unit vector in the child's frame, or zero for a fixed joint; tilt is the whole rotation of the child against the
     reference pose and slip the motion off the axis.  There is no local_pos and nothing is unwrapped.  Returns the dict
     ``joint_positions`` returns and raises what it raises."""
-    L_ = _lib.load()
-    link_T = _need(link_T, torch.float64, "link_T")
-    if link_T.dim() != 5 or tuple(link_T.shape[3:]) != (4, 4) or 0 in link_T.shape[:3]:
-        raise ValueError(f"joint_slides: link_T must be (S,T,L,4,4) with S, T, L >= 1, got {tuple(link_T.shape)}")
-    S, T, L = link_T.shape[:3]
-    dev = link_T.device
-    jt = [(int(p), int(c)) for p, c in joints]
-    J = len(jt)
-    for p, c in jt:
-        if not (0 <= p < L and 0 <= c < L):
-            raise ValueError(f"joint_slides: joint ({p}, {c}) names a link outside [0, {L})")
-    ax = _need(torch.as_tensor(local_axis, dtype=torch.float64, device=dev).reshape(-1, 3), torch.float64, "local_axis")
-    if ax.shape[0] != J:
-        raise ValueError(f"joint_slides: local_axis must be ({J},3), got {tuple(ax.shape)}")
-    start_step, ref_seq, ref_step = int(start_step), int(ref_seq), int(ref_step)
-    num_steps = T - start_step if num_steps is None else int(num_steps)
-    if start_step < 0 or num_steps < 1:
-        raise ValueError(f"joint_slides: need start_step >= 0 and num_steps >= 1 (got {start_step}, {num_steps})")
-    if start_step + num_steps > T:
-        raise IndexError(f"index {start_step + num_steps - 1} is out of bounds for axis 1 with size {T}")
-    if not 0 <= ref_seq < S:
-        raise IndexError(f"index {ref_seq} is out of bounds for axis 0 with size {S}")
-    if not 0 <= ref_step < T:
-        raise IndexError(f"index {ref_step} is out of bounds for axis 1 with size {T}")
-    if S > 65535 or S * num_steps >= 2 ** 31:
-        raise ValueError(f"joint_slides: at most 65535 sequences and 2^31 samples per joint (S={S}, num_steps={num_steps})")
-    f64 = dict(dtype=torch.float64, device=dev)
-    q, tilt, slip = (torch.empty(J, S, num_steps, **f64) for _ in range(3))
-    summary = torch.empty(J, 6, **f64)
-    where = torch.empty(J, 5, dtype=torch.int32, device=dev)
-    if J:
-        jn = torch.tensor(jt, dtype=torch.int32, device=dev).reshape(-1, 2)
-        _lib.check(L_.creg_joint_slides_f64(_p(link_T), S, T, L, _p(jn), J, _p(ax), ref_seq, ref_step, start_step, num_steps,
-                                            _p(q), _p(tilt), _p(slip), _p(summary), _p(where), _stream()),
-                   "creg_joint_slides_f64")
-    out = {"q": q, "tilt": tilt, "slip": slip}
-    for i, k in enumerate(("lower", "upper", "tilt_rms", "tilt_max", "slip_rms", "slip_max")):
-        out[k] = summary[:, i]
-    out.update(n_used=where[:, 0], lower_at=where[:, 1:3], upper_at=where[:, 3:5])
-    return out
+    def axis_alone(J, ax, dev):
+        if ax.shape[0] != J:
+            raise ValueError(f"joint_slides: local_axis must be ({J},3), got {tuple(ax.shape)}")
+        return ()
+    return _joint_series("joint_slides", "creg_joint_slides_f64", link_T, joints, local_axis, axis_alone, ref_seq, ref_step,
+                         start_step, num_steps)
 
 
 def motion_error(A, A0, B, B0, point):

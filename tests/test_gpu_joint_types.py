@@ -262,6 +262,54 @@ def test_joint_slides_without_joints_and_refusals(dev):
         ops.joint_slides(lt.float(), *args)
 
 
+def test_refusals_of_the_five_wrappers_keep_their_words(dev):
+    """One fault per call on the typed tree (S=3, T=20, K=8, L=5, J=4): the exception's type and its whole text, as they were
+    before the wrappers shared their checks.  Every call raises before any launch."""
+    from autourdf_amd import ops
+    t, (_, lt) = _tree(20), _poses(20)
+    c, cl, jt = t["coords_dev"], t["link_clusters"], t["joints"]
+    ax, lp = np.zeros((4, 3)), np.zeros((4, 4))
+    past = [list(x) for x in cl[:4]] + [[8]]                                  # link 4 names cluster K
+    empty = [list(x) for x in cl[:3]] + [[]] + [list(cl[4])]
+    wide = torch.zeros(1, 2, 257, 7, dtype=torch.float64, device=dev)
+    f32 = "must be torch.float64, got torch.float32"
+    table = []
+    for name, fn, more in (("joint_axes", ops.joint_axes, {}), ("joint_types", ops.joint_types, {"slide_min": 1e-6})):
+        table += [
+            (fn, (c, cl, jt, 0, 21, 1), more, IndexError, "index 20 is out of bounds for axis 0 with size 20"),
+            (fn, (c, cl, [(0, 5)], 0, 20, 1), more, ValueError, f"{name}: joint (0, 5) names a link outside [0, 5)"),
+            (fn, (c, past, jt, 0, 20, 1), more, ValueError, f"{name}: link 4 names clusters [8] outside [0, 8)"),
+            (fn, (c, empty, jt, 0, 20, 1), more, ValueError, f"{name}: link 3 has no cluster"),
+            (fn, (wide, cl, jt, 0, 2, 1), more, ValueError, f"{name} supports at most 256 clusters, got 257"),
+            (fn, (c, cl, jt, 0, 0, 1), more, ValueError,
+             f"{name}: need start_step >= 0, num_steps >= 1, interval >= 1 (got 0, 0, 1)"),
+            (fn, (c.float(), cl, jt, 0, 20, 1), more, TypeError, "coords " + f32)]
+    table += [
+        (ops.link_poses, (c, past), {}, ValueError, "link_poses: link 4 names clusters [8] outside [0, 8)"),
+        (ops.link_poses, (c, empty), {}, ValueError, "link_poses: link 3 has no cluster"),
+        (ops.link_poses, (wide, cl), {}, ValueError, "link_poses supports at most 256 clusters, got 257"),
+        (ops.link_poses, (c.float(), cl), {}, TypeError, "coords " + f32),
+        (ops.joint_positions, (lt, jt, np.zeros((3, 3)), lp), {}, ValueError,
+         "joint_positions: local_axis must be (4,3) and local_pos (4,3) or (4,4), got (3, 3) and (4, 4)"),
+        (ops.joint_positions, (lt, jt, ax, np.zeros((4, 5))), {}, ValueError,
+         "joint_positions: local_axis must be (4,3) and local_pos (4,3) or (4,4), got (4, 3) and (4, 5)"),
+        (ops.joint_slides, (lt, jt, np.zeros((3, 3))), {}, ValueError, "joint_slides: local_axis must be (4,3), got (3, 3)")]
+    for name, fn, rest in (("joint_positions", ops.joint_positions, (lp,)), ("joint_slides", ops.joint_slides, ())):
+        one = tuple(x[:1] for x in (ax,) + rest)
+        table += [
+            (fn, (lt, jt, ax, *rest, 0, 0, 0, 21), {}, IndexError, "index 20 is out of bounds for axis 1 with size 20"),
+            (fn, (lt, jt, ax, *rest, 3, 0, 0, 5), {}, IndexError, "index 3 is out of bounds for axis 0 with size 3"),
+            (fn, (lt, jt, ax, *rest, 0, 20, 0, 5), {}, IndexError, "index 20 is out of bounds for axis 1 with size 20"),
+            (fn, (lt, [(0, 5)], *one), {}, ValueError, f"{name}: joint (0, 5) names a link outside [0, 5)"),
+            (fn, (lt, jt, ax, *rest, 0, 0, 0, 0), {}, ValueError, f"{name}: need start_step >= 0 and num_steps >= 1 (got 0, 0)"),
+            (fn, (lt.float(), jt, ax, *rest), {}, TypeError, "link_T " + f32)]
+    assert len(table) == 33
+    for fn, args, more, kind, text in table:
+        with pytest.raises(kind) as e:
+            fn(*args, **more)
+        assert type(e.value) is kind and str(e.value) == text, (fn.__name__, str(e.value), text)
+
+
 # ------------------------------------------------------------------------------------------------ end to end
 def _replay_worst(replay):
     return max(r["rot_max"] for r in replay), max(r["pos_max"] for r in replay)

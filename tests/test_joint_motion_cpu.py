@@ -68,6 +68,17 @@ def test_shared_device_helpers_moved_to_the_header():
     for name in ("jacobi_top", "link_mean_pose", "child_in_parent", "link_span"):
         assert re.search(r"__device__ (inline )?\w+ %s\(" % name, hdr), name
         assert not re.search(r"__device__ (inline )?\w+ %s\(" % name, src), name
+    # the rotation's sine, cosine and norm, and a sample's relative motion: defined in the header and in no .hip file
+    csrc = os.path.join(ROOT, "autourdf_amd", "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    for name in ("skew_and_cos", "norm3", "joint_sample_motion"):
+        assert re.search(r"__device__ inline \w+ %s\(" % name, hdr), name
+        for f, body in text.items():
+            if f.endswith(".hip"):
+                assert not re.search(r"__device__ [\w ]*\b%s\(" % name, body), (name, f)
+    for f in ("joints.hip", "joint_types.hip"):
+        assert "joint_sample_motion(" in text[f] and "skew_and_cos(" in text[f] and "norm3(" in text[f], f
+    assert sum(body.count("(R[7] - R[5]) * 0.5") for body in text.values()) == 1
 
 
 def test_ops_need_device_tensors():

@@ -53,6 +53,16 @@ def test_sample_enumeration_is_shared():
         src = open(os.path.join(ROOT, "autourdf_amd", "csrc", name)).read()
         assert '#include "joints_dev.h"' in src and "sample_steps(" in src
         assert not re.search(r"__device__ (inline )?void sample_steps\(", src)
+        # ... through the one helper that builds a sample's relative motion, which alone calls sample_steps
+        assert len(re.findall(r"\bjoint_sample_motion\(coords, ", src)) == 1 and "link_mean_pose(c1" not in src
+        assert not re.search(r"__device__ [\w ]*\bjoint_sample_motion\(", src)
+    motion = hdr[hdr.index("__device__ inline void joint_sample_motion("):]
+    assert "sample_steps(i - seq * per_seq" in motion and motion.count("link_mean_pose(") == 4 and motion.count("child_in_parent(") == 3
+    # one set of limits, the header's
+    assert all(re.search(r"constexpr \w+ %s = " % n, hdr) for n in ("JOINT_MAX_K", "JOINT_MAX_SAMPLES", "JOINT_THETA_MIN"))
+    for name in ("joints.hip", "joint_types.hip", "joint_motion.hip"):
+        src = open(os.path.join(ROOT, "autourdf_amd", "csrc", name)).read()
+        assert not re.search(r"\b(JA|JT)_(MAX_K|MAX_SAMPLES|THETA_MIN)\b", src) and "K <= 256" not in src, name
 
 
 def test_ops_need_device_tensors_and_a_slide_min():

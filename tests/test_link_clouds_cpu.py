@@ -28,7 +28,9 @@ def test_kernel_constants_are_the_helpers():
     nt = int(re.search(r"constexpr int LC_NT = (\d+);", src).group(1))
     mult = int(re.search(r"constexpr int LC_ROWS = (\d+) \* LC_NT;", src).group(1))
     slices = int(re.search(r"constexpr int LC_MAX_SLICES = (\d+);", src).group(1))
-    max_k = int(re.search(r"constexpr int JA_MAX_K = (\d+);", src).group(1))
+    hdr = open(os.path.join(ROOT, "autourdf_amd", "csrc", "joints_dev.h")).read()       # the joint stage's one set of limits
+    max_k = int(re.search(r"constexpr int JOINT_MAX_K = (\d+);", hdr).group(1))
+    assert "K <= JOINT_MAX_K" in src[src.index('extern "C" int creg_link_clouds_f64('):]
     assert (nt, mult * nt, slices, max_k) == (E.LC_NT, E.LC_ROWS, E.LC_MAX_SLICES, E.MAX_K)
     assert E.STRIDE_ROWS == slices * mult * nt + mult * nt + 5
 
