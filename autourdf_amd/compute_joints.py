@@ -15,7 +15,8 @@ scope.  No CPU fallback.
 This project's own, beyond the reference: ``estimate_typed_joints_from_tree`` also tells prismatic and fixed joints
 (``creg_joint_types_f64``), and ``estimate_joint_motion``, ``set_joint_limits`` and ``replay_urdf`` recover every joint's
 positions, write the observed limits and check the written file against the registration; ``cloud_fit_poses`` and
-``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``).
+``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``); ``fit_cloud_poses`` and ``fit_positions``
+fit the joint positions and the base pose to clouds (``ops.pose_fit_system``, Levenberg-Marquardt).
 """
 import os
 import xml.etree.ElementTree as ET
@@ -515,6 +516,14 @@ def cloud_fit_link_poses(urdf_file, links, motion, cm_list, start_step, num_step
     expressions, which add offsets taken in the world frame to offsets taken in link frames; they hold when the registered link
     frames of (sequence 0, ``time_step``) are unrotated, which is how the registration defines step 0 (DESIGN N4 has the
     figures for both cases).  At another ``time_step`` the file's zero pose is off, and this check says so, as the replay does."""
+    robot, q, G = _cloud_fit_state(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
+    fk = ops.urdf_fk(robot.fk_table(), q, np.eye(4))                           # (S*n, L_urdf, 4, 4)
+    return robot, (G[:, None] @ fk).contiguous()
+
+
+def _cloud_fit_state(urdf_file, links, motion, cm_list, start_step, num_steps, time_step=0):
+    """(robot, q (S*num_steps,J) host rows in ``fk_table()``'s order, G (S*num_steps,4,4) device root motions) of
+    ``cloud_fit_link_poses``: what the cloud fit poses the file by, and what ``fit_positions`` starts from."""
     from .sim_data import UrdfRobot
     robot = UrdfRobot(urdf_file)
     coords = _coords(cm_list)
@@ -528,10 +537,9 @@ def cloud_fit_link_poses(urdf_file, links, motion, cm_list, start_step, num_step
     for col, name in enumerate(names):
         if name in q_by_name:
             q[:, col] = q_by_name[name].reshape(-1)
-    fk = ops.urdf_fk(robot.fk_table(), q, np.eye(4))                           # (S*n, L_urdf, 4, 4)
     (root,) = [i for i, l in enumerate(links) if l["parent_id"] is None]
     G = reg[:, start_step:start_step + n, root].reshape(S * n, 4, 4) @ torch.linalg.inv(reg[0, time_step, root])
-    return robot, (G[:, None] @ fk).contiguous()
+    return robot, q, G
 
 
 def cloud_fit(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf):
@@ -555,4 +563,165 @@ def cloud_fit(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps
             k = int(np.searchsorted(cut, fig["max_at"], side="right") - 1)
             fig["max_at"] = (int(start_step + k), int(fig["max_at"] - cut[k]))
         fit["sequences"].append(fig)
+    return fit
+
+
+FIT_LAMBDA_MIN, FIT_LAMBDA_STOP = 1e-12, 1e8                                   # the floor of the damping, and where a pose gives up
+
+
+def _base_steps(delta, center):
+    """(P,4,4) rigid motions X -> R(w)(X - center) + center + v of base steps delta (P,6) = w | v: Rodrigues' formula, exact; below
+    an angle of 1e-8 the two series' leading terms stand in for sin t / t and (1 - cos t) / t^2 (their error is below 1e-17)."""
+    w, v = delta[:, :3], delta[:, 3:6]
+    t = torch.linalg.vector_norm(w, dim=1)
+    tiny = t < 1e-8
+    ts = torch.where(tiny, torch.ones_like(t), t)
+    a = torch.where(tiny, torch.ones_like(t), torch.sin(ts) / ts)
+    b = torch.where(tiny, torch.full_like(t, 0.5), (1.0 - torch.cos(ts)) / (ts * ts))
+    K = torch.zeros(len(w), 3, 3, dtype=w.dtype, device=w.device)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0], K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -w[:, 2], w[:, 1], w[:, 2], -w[:, 0], -w[:, 1], w[:, 0]
+    R = torch.eye(3, dtype=w.dtype, device=w.device) + a[:, None, None] * K + b[:, None, None] * (K @ K)
+    U = torch.zeros(len(w), 4, 4, dtype=w.dtype, device=w.device)
+    U[:, :3, :3], U[:, 3, 3] = R, 1.0
+    U[:, :3, 3] = center + v - (R @ center[:, :, None])[:, :, 0]
+    return U
+
+
+def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10):
+    """Fit a robot's joint values and base pose to one cloud per pose by Levenberg-Marquardt on the point-to-mesh distance (this
+    project's own): robot a ``UrdfRobot`` loaded with its meshes, clouds a list of P (n_p,3) arrays of world points, q0 (P,J) the
+    starting joint values in ``robot.fk_table()``'s order, base0 (4,4) or (P,4,4) the starting root poses (identity when None).
+    The state is q (P,J) and G (P,4,4); all P poses advance in lock-step, every device call covers all of them.  An iteration:
+      1  link_T = G urdf_fk(q), as ``cloud_fit_link_poses`` composes it
+      2  one ``ops.point_mesh_distance`` call
+      3  per pose the truncated cost, sum of min(d^2, d_max^2) over the live (not NaN) points
+      4  the last step of a pose is accepted iff its cost did not rise: lambda <- max(lambda / 10, 1e-12); otherwise the pose's
+         state is restored and lambda <- 10 lambda
+      5  ``ops.pose_fit_system`` (a pose whose step was rejected keeps the system of the state it went back to)
+      6  (H_f + lambda diag(H_f)) delta = g_f over the free parameters, batched in fp64 on the device (``torch.linalg``).  Left
+         out: fixed joints, the joints named in ``lock`` (names or table rows), the base when ``fit_base`` is False, and a
+         parameter whose diagonal entry is exactly 0 -- no matched point moves with it; it gets delta = 0 and is reported in
+         ``unobserved``.  A failed factorisation counts as a rejection: no step, lambda <- 10 lambda
+      7  q += delta_q and G_p <- [X -> R(w)(X - center_p) + center_p + v] G_p, center_p the mean of the pose's live points
+    A pose stops when an accepted step has max |delta| < ``tol``, when lambda > 1e8, or after ``max_iter`` steps.  ``lam0``,
+    ``tol``, the floor and the factors of 10 are settings of the algorithm, not measurements.  Returns a dict of host values: q
+    (P,J), base (P,4,4), cost_history (P lists, non-increasing by construction: the first entry is the start, one more per step
+    tried), iterations (P) steps tried, rms_before and rms_after (P) = sqrt(cost / live points), unobserved (P,6+J) bool in the
+    order rotation, translation, joints, n (P) the points within ``d_max`` at the returned state, and names (the joints' names in
+    the table's order).  Not done here: joint limits, a point-to-plane metric, warm starts from a neighbouring frame."""
+    table = robot.fk_table()
+    names, kinds = list(table["names"]), np.asarray(table["type"])
+    J, D = len(names), 6 + len(names)
+    dev = _lib.device()
+    d_max, max_iter = float(d_max), int(max_iter)
+    if not d_max >= 0.0 or max_iter < 0 or not lam0 > 0.0:
+        raise ValueError(f"fit_cloud_poses: d_max >= 0, max_iter >= 0 and lam0 > 0 expected, got {d_max}, {max_iter}, {lam0}")
+    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    P = len(parts)
+    q = torch.as_tensor(np.array(q0, np.float64).reshape(-1, J) if not isinstance(q0, torch.Tensor) else q0, dtype=torch.float64, device=dev).clone()
+    if P < 1 or tuple(q.shape) != (P, J):
+        raise ValueError(f"fit_cloud_poses: {P} clouds need q0 ({P},{J}), got {tuple(q.shape)}")
+    G = torch.eye(4, dtype=torch.float64, device=dev) if base0 is None else torch.as_tensor(base0, dtype=torch.float64, device=dev)
+    if tuple(G.shape) not in ((4, 4), (P, 4, 4)):
+        raise ValueError(f"fit_cloud_poses: base0 must be (4,4) or ({P},4,4), got {tuple(G.shape)}")
+    G = G.expand(P, 4, 4).clone()
+    locked = set()
+    for item in lock:
+        if isinstance(item, str) and item not in names:
+            raise ValueError(f"fit_cloud_poses: no joint named {item!r} among {names}")
+        locked.add(names.index(item) if isinstance(item, str) else int(item))
+    free0 = np.array([bool(fit_base)] * 6 + [kinds[j] in (1, 2) and j not in locked for j in range(J)])
+    free0 = torch.as_tensor(free0, device=dev)
+    cut_host = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
+    pts = torch.as_tensor(np.concatenate(parts) if cut_host[-1] else np.zeros((0, 3)), device=dev)
+    cut = torch.as_tensor(cut_host, device=dev)
+    pose_of = torch.repeat_interleave(torch.arange(P, device=dev), cut[1:] - cut[:-1])
+    live = ~torch.isnan(pts).any(1)
+    n_live = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, pose_of, live.to(torch.float64))
+    center = torch.zeros(P, 3, dtype=torch.float64, device=dev).index_add_(0, pose_of, torch.where(live[:, None], pts, torch.zeros_like(pts)))
+    center = center / n_live.clamp_min(1.0)[:, None]
+    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
+    tri_start = torch.as_tensor(robot.tri_start, device=dev)
+    eye, dmax2 = np.eye(4), d_max * d_max
+    lam = torch.full((P,), float(lam0), dtype=torch.float64, device=dev)
+    active = n_live > 0
+    stepped = torch.zeros(P, dtype=torch.bool, device=dev)
+    small = torch.zeros(P, dtype=torch.bool, device=dev)
+    iters = torch.zeros(P, dtype=torch.int64, device=dev)
+    unobserved = torch.zeros(P, D, dtype=torch.bool, device=dev)
+    H_cur = g_cur = cost_cur = n_cur = q_prev = G_prev = None
+    history = []
+    for it in range(max_iter + 1):
+        link_T = (G[:, None] @ ops.urdf_fk(table, q, eye)).contiguous()
+        dist, tri_idx, _ = ops.point_mesh_distance(tri, tri_start, link_T, pts, cut, d_max)
+        d2 = torch.where(live, torch.clamp(dist * dist, max=dmax2), torch.zeros_like(dist))
+        cost = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, pose_of, d2)
+        within = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, pose_of, (live & torch.isfinite(dist)).to(torch.int64))
+        if it == 0:
+            accept, cost_cur, n_cur = torch.ones(P, dtype=torch.bool, device=dev), cost, within
+        else:
+            accept = stepped & (cost <= cost_cur)
+            back = stepped & ~accept
+            q, G = torch.where(back[:, None], q_prev, q), torch.where(back[:, None, None], G_prev, G)
+            lam = torch.where(accept, (lam / 10.0).clamp_min(FIT_LAMBDA_MIN), torch.where(back, lam * 10.0, lam))
+            cost_cur, n_cur = torch.where(accept, cost, cost_cur), torch.where(accept, within, n_cur)
+            active = active & ~(accept & small) & ~(lam > FIT_LAMBDA_STOP)
+        history.append(cost_cur)
+        if it == max_iter or not bool(active.any()):
+            break
+        H, g, _, _ = ops.pose_fit_system(tri, tri_start, link_T, pts, cut, tri_idx, table, center, d_max)
+        if H_cur is None:
+            H_cur, g_cur = H, g
+        else:
+            H_cur, g_cur = torch.where(accept[:, None, None], H, H_cur), torch.where(accept[:, None], g, g_cur)
+        diag = torch.diagonal(H_cur, dim1=1, dim2=2)
+        free = free0[None] & (diag != 0.0)
+        unobserved = torch.where(active[:, None], free0[None] & (diag == 0.0), unobserved)
+        m = free.to(torch.float64)
+        A = H_cur * m[:, :, None] * m[:, None, :] + torch.diag_embed(lam[:, None] * diag * m + (1.0 - m))
+        chol, info = torch.linalg.cholesky_ex(A)
+        delta = torch.cholesky_solve((g_cur * m)[:, :, None], chol)[:, :, 0]
+        failed = (info != 0) | ~torch.isfinite(delta).all(1)
+        stepped = active & ~failed
+        delta = torch.where(stepped[:, None] & free, delta, torch.zeros_like(delta))
+        lam = torch.where(active & failed, lam * 10.0, lam)
+        iters = iters + active.to(torch.int64)
+        small = delta.abs().amax(1) < tol
+        q_prev, G_prev = q, G
+        q = torch.where(delta[:, 6:] != 0.0, q + delta[:, 6:], q)
+        moved = (delta[:, :6] != 0.0).any(1)
+        G = torch.where(moved[:, None, None], _base_steps(delta[:, :6], center) @ G, G)
+    history = torch.stack(history).cpu().numpy()
+    iters = iters.cpu().numpy()
+    n_live = n_live.cpu().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rms = lambda c: np.where(n_live > 0, np.sqrt(c / np.maximum(n_live, 1.0)), np.nan)
+        out = {"q": q.cpu().numpy(), "base": G.cpu().numpy(),
+               "cost_history": [history[:min(int(iters[p]), len(history) - 1) + 1, p].tolist() for p in range(P)],
+               "iterations": iters, "rms_before": rms(history[0]), "rms_after": rms(history[-1]),
+               "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names}
+    return out
+
+
+def fit_positions(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf, max_iter=30):
+    """Fit the written URDF's joint positions to the raw clouds, frame by frame (this project's own): the poses of ``cloud_fit``
+    -- the replay's ``q`` rows and the registered root motion G -- are the start, every frame is fitted with the base free
+    (``fit_cloud_poses``), ``d_max`` is the cloud fit's limit.  Returns ``fit_cloud_poses``' dict with "positions" added, the
+    fitted values (J,S,num_steps) in the order of ``motion`` (the layout of ``joint_positions.npy``), and "shift" (J), per joint
+    the largest |q_fit - q_registered|.  The URDF and its limits are not touched."""
+    from .cluster_icp import read_point_cloud
+    robot, q, G = _cloud_fit_state(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
+    S, n = len(cm_list), int(num_steps)
+    clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
+              for s in range(S) for k in range(n)]
+    fit = fit_cloud_poses(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True)
+    positions = np.array([np.asarray(m["positions"], np.float64).reshape(S, n) for m in motion]).reshape(len(motion), S, n)
+    shift = np.zeros(len(motion))
+    for j, m in enumerate(motion):
+        name = f"joint_{m['child_link']}"
+        if name in fit["names"]:
+            fitted = fit["q"][:, fit["names"].index(name)].reshape(S, n)
+            shift[j] = float(np.abs(fitted - positions[j]).max())
+            positions[j] = fitted
+    fit["positions"], fit["shift"] = positions, shift
     return fit

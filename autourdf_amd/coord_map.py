@@ -394,7 +394,9 @@ def _cli_parser():
     --cloud_fit sets the written URDF's meshes, posed at the recovered joint positions, against the raw clouds and writes
     <name>.cloud_fit.json; --fit_max (the clouds' unit, default inf) is the distance beyond which a point counts as
     unexplained.  --cloud_fit without --voxel_size or without --joint_limits, and --fit_max without --cloud_fit, are usage
-    errors."""
+    errors.  --fit_positions fits every frame's joint positions and base pose to its raw cloud after the cloud fit and writes
+    <name>.fitted_positions.npy; --fit_iters (default 30) caps its iterations.  --fit_positions without --cloud_fit, and
+    --fit_iters without --fit_positions, are usage errors."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
@@ -406,6 +408,8 @@ def _cli_parser():
     parser.add_argument('--turn_min', type=float, default=None)
     parser.add_argument('--cloud_fit', action='store_true')
     parser.add_argument('--fit_max', type=float, default=None)
+    parser.add_argument('--fit_positions', action='store_true')
+    parser.add_argument('--fit_iters', type=int, default=None)
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -422,6 +426,10 @@ def _cli_parser():
             parser.error("--cloud_fit needs --joint_limits: the meshes are posed at the recovered joint positions")
         if ns.fit_max is not None and not ns.cloud_fit:
             parser.error("--fit_max needs --cloud_fit")
+        if ns.fit_positions and not ns.cloud_fit:
+            parser.error("--fit_positions needs --cloud_fit: it starts from the poses the cloud fit measures")
+        if ns.fit_iters is not None and not ns.fit_positions:
+            parser.error("--fit_iters needs --fit_positions")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -455,24 +463,47 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
               f"pos_max {w['pos_max']:.3g} at {w['pos_max_at']}")
 
 
-def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names):
+def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None):
     """Write <name>.cloud_fit.json next to the URDF -- the per-frame, per-sequence, per-link and overall figures of
     ``cloud_fit``, without the per-point arrays -- and print one line per sequence (rms, p95, unexplained share) and the worst
-    frame.  ``fit_max`` is written as null when it is inf."""
+    frame.  ``fit_max`` is written as null when it is inf.  With ``fitted`` (``fit_positions``' dict) the file gains a "fitted"
+    block -- per frame the rms before and after the fit and the steps tried, per sequence and overall the rms before and
+    after, per joint the largest |q_fit - q_registered| --, <name>.fitted_positions.npy (J,S,steps) is written beside
+    joint_positions.npy, and one line per sequence and one per joint are printed."""
     import json
     stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
     clean = lambda d: {k: (None if isinstance(v, float) and not np.isfinite(v) else v) for k, v in d.items()}
     frames = [dict(clean(f), sequence=i // num_steps, step=start_step + i % num_steps) for i, f in enumerate(fit["poses"])]
+    report = {"urdf": urdf_path, "fit_max": None if np.isinf(fit_max) else fit_max, "start_step": start_step,
+              "unit": "the clouds' unit", "all": clean(fit["all"]), "sequences": [clean(s) for s in fit["sequences"]],
+              "links": [clean(l) for l in fit["links"]], "frames": frames}
+    if fitted is not None:
+        np.save(stem + '.fitted_positions.npy', fitted["positions"])
+        S = len(fitted["rms_before"]) // num_steps
+        live = np.array([f["n"] for f in fit["poses"]], np.float64)                 # weights: a frame's points
+        pooled = lambda rms, rows: float(np.sqrt(np.nansum(rms[rows] ** 2 * live[rows]) / max(live[rows].sum(), 1.0)))
+        rows_of = [np.arange(s * num_steps, (s + 1) * num_steps) for s in range(S)]
+        report["fitted"] = {
+            "frames": [clean({"sequence": i // num_steps, "step": start_step + i % num_steps, "rms_before": float(b), "rms_after": float(a),
+                              "iterations": int(k)})
+                       for i, (b, a, k) in enumerate(zip(fitted["rms_before"], fitted["rms_after"], fitted["iterations"]))],
+            "sequences": [{"rms_before": pooled(fitted["rms_before"], r), "rms_after": pooled(fitted["rms_after"], r)} for r in rows_of],
+            "all": {"rms_before": pooled(fitted["rms_before"], np.arange(S * num_steps)),
+                    "rms_after": pooled(fitted["rms_after"], np.arange(S * num_steps))},
+            "joints": [{"joint": name, "max_shift": float(d)} for name, d in zip(fitted["joint_names"], fitted["shift"])]}
     with open(stem + '.cloud_fit.json', 'w') as f:
-        json.dump({"urdf": urdf_path, "fit_max": None if np.isinf(fit_max) else fit_max, "start_step": start_step,
-                   "unit": "the clouds' unit", "all": clean(fit["all"]), "sequences": [clean(s) for s in fit["sequences"]],
-                   "links": [clean(l) for l in fit["links"]], "frames": frames}, f, indent=1)
+        json.dump(report, f, indent=1)
     for name, s in zip(seq_names, fit["sequences"]):
         print(f"cloud_fit {name}: rms {s['rms']:.3g}, p95 {s['p95']:.3g}, unexplained {s['unexplained'] / max(s['n'], 1):.2%} of {s['n']}")
     seen = [f for f in frames if f["rms"] is not None]
     if seen:
         w = max(seen, key=lambda f: f["rms"])
         print(f"cloud_fit: worst frame sequence {w['sequence']} step {w['step']}: rms {w['rms']:.3g}, max {w['max']:.3g} at point {w['max_at']}")
+    if fitted is not None:
+        for name, s in zip(seq_names, report["fitted"]["sequences"]):
+            print(f"fit_positions {name}: rms {s['rms_before']:.3g} -> {s['rms_after']:.3g}")
+        for j in report["fitted"]["joints"]:
+            print(f"fit_positions {j['joint']}: largest |q_fit - q_registered| {j['max_shift']:.3g}")
 
 
 def main(argv=None):
@@ -499,15 +530,21 @@ def main(argv=None):
     default inf, the option wins) the written URDF's meshes, posed by its joints at the recovered positions, are set against
     every loaded raw cloud after the replay (``cloud_fit``: one ``ops.point_mesh_distance`` call), ``<name>.cloud_fit.json`` is
     written next to the URDF and one line per sequence and the worst frame are printed.  It needs the link meshes and the joint
-    limits, and a ``fit_max`` needs it: ValueError before anything is written otherwise."""
+    limits, and a ``fit_max`` needs it: ValueError before anything is written otherwise.  With ``--fit_positions`` (or a boolean
+    ``fit_positions`` key; ``--fit_iters`` / ``fit_iters``, default 30, the option wins) every frame's joint positions and base
+    pose are then fitted to its raw cloud (``fit_positions``: from the replay's positions and the registered root motion, the
+    base free, ``fit_max`` as the distance limit), ``<name>.fitted_positions.npy`` (J,S,steps) is written beside
+    ``joint_positions.npy``, ``cloud_fit.json`` gains a "fitted" block, and one line per sequence (rms before -> after) and per
+    joint (the largest |q_fit - q_registered|) are printed; the URDF and its limits are not touched.  It needs the cloud fit,
+    and a ``fit_iters`` needs it: ValueError before anything is written otherwise."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
     from .compute_joints import (cloud_fit, create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
-                                 estimate_typed_joints_from_tree, replay_urdf, set_collision_meshes, set_inertials,
-                                 set_joint_limits)
+                                 estimate_typed_joints_from_tree, fit_positions, replay_urdf, set_collision_meshes,
+                                 set_inertials, set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
     if not torch.cuda.is_available():
@@ -557,6 +594,17 @@ def main(argv=None):
     fit_max = float("inf") if fit_max is None else float(fit_max)
     if not fit_max >= 0.0:
         raise ValueError(f"fit_max must be >= 0 (inf allowed), got {fit_max}")
+    want_positions = bool(args.fit_positions or robot_params.get('fit_positions'))
+    fit_iters = args.fit_iters if args.fit_iters is not None else robot_params.get('fit_iters')
+    if want_positions and not want_fit:
+        raise ValueError("fit_positions starts from the poses the cloud fit measures: give --cloud_fit (or a cloud_fit key in "
+                         "parameters.json) with --fit_positions")
+    if fit_iters is not None and not want_positions:
+        raise ValueError("a fit_iters is the iteration cap of fit_positions: give --fit_positions (or a fit_positions key in "
+                         "parameters.json) with it")
+    fit_iters = 30 if fit_iters is None else int(fit_iters)
+    if fit_iters < 0:
+        raise ValueError(f"fit_iters must be >= 0, got {fit_iters}")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -633,7 +681,12 @@ def main(argv=None):
         _joint_motion_report(urdf_path, motion, replay, limit_pad, START)
         if want_fit:
             fit = cloud_fit(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START, d_max=fit_max)
-            _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path])
+            fitted = None
+            if want_positions:
+                fitted = fit_positions(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START,
+                                       d_max=fit_max, max_iter=fit_iters)
+                fitted["joint_names"] = [f"joint_{m['child_link']}" for m in motion]
+            _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path], fitted)
     return urdf_path
 
 

@@ -716,6 +716,74 @@ def point_mesh_distance(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"
     return (dist, tri_idx, link) + ((boxes,) if want_boxes else ())
 
 
+POSE_FIT_MAX_D = 64
+
+
+def joint_chains(table):
+    """chain (L) uint64 of a joint table (``UrdfRobot.fk_table()``): bit j of chain[l] is set iff joint j lies on the path from the
+    root to link l.  The table is in topological order, so a child's mask is its parent's plus its own bit; a joint with an index
+    outside [0, L) sets no bit, as the forward kinematics skips it.  At most 64 joints."""
+    n_links, parent, child = int(table["n_links"]), np.asarray(table["parent"]), np.asarray(table["child"])
+    if len(parent) > 64:
+        raise ValueError(f"joint_chains: at most 64 joints fit a mask, got {len(parent)}")
+    chain = [0] * n_links
+    for j, (pa, ch) in enumerate(zip(parent, child)):
+        if 0 <= pa < n_links and 0 <= ch < n_links:
+            chain[ch] = chain[pa] | (1 << j)
+    return np.array(chain, np.uint64)
+
+
+def pose_fit_system(tri, tri_start, link_T, pts, pt_start, tri_idx, table, center, d_max=float("inf")):
+    """The Gauss-Newton system of fitting a robot's base pose and joint values to clouds (creg_pose_fit_system_f64; the contract
+    is in include/creg.h): tri, tri_start, link_T, pts, pt_start and ``d_max`` as ``point_mesh_distance`` takes them, tri_idx (N)
+    int32 the rows it returned (in the order of ``pts``: its ``sort=True`` results are already scattered back), ``table`` from
+    ``UrdfRobot.fk_table()`` and center (P,3) f64 the point each pose's base rotation turns about -> (H (P,D,D), g (P,D),
+    cost (P), n (P) int64) on the device, D = 6 + J: rotation about ``center``, translation, then the table's joints.  One call
+    for all poses.  The table and its chain masks go up once per robot and device and are kept in the dict (``_dev_fit``, as
+    ``urdf_fk`` keeps ``_dev``): change a copy of a table without those keys.  tri_start and pt_start are not read back; the
+    kernel clamps them.  ValueError before any launch: a bad shape or dtype, a negative or NaN ``d_max``, D > 64."""
+    L = _lib.load()
+    d_max = float(d_max)
+    if not d_max >= 0.0:
+        raise ValueError(f"pose_fit_system: d_max must be >= 0 (inf allowed), got {d_max}")
+    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
+    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
+    tri_idx, center = _need(tri_idx, torch.int32, "tri_idx"), _need(center, torch.float64, "center")
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
+            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
+            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1 \
+            or tuple(tri_idx.shape) != (pts.shape[0],) or tuple(center.shape) != (link_T.shape[0], 3):
+        raise ValueError(f"pose_fit_system: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) / tri_idx (N) / "
+                         f"center (P,3) expected, got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, "
+                         f"{tuple(pts.shape)}, {tuple(pt_start.shape)}, {tuple(tri_idx.shape)}, {tuple(center.shape)}")
+    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    J = len(table["parent"])
+    if n_links != int(table["n_links"]) or 6 + J > POSE_FIT_MAX_D:
+        raise ValueError(f"pose_fit_system: the table has {table['n_links']} links and {J} joints; link_T has {n_links} links and "
+                         f"6 + joints must be <= {POSE_FIT_MAX_D}")
+    tdev = table.get("_dev_fit")
+    if tdev is None or tdev[0].device != dev:                     # the table and its chain masks go up once per robot and device
+        tdev = tuple(torch.as_tensor(np.ascontiguousarray(table[k]), device=dev) for k in ("parent", "child", "type", "origin", "axis")) \
+            + (torch.as_tensor(joint_chains(table).view(np.int64), device=dev),)
+        table["_dev_fit"] = tdev
+    parent, child, kind, origin, axis, chain = tdev
+    D = 6 + J
+    H = torch.empty(P, D, D, dtype=torch.float64, device=dev)
+    g = torch.empty(P, D, dtype=torch.float64, device=dev)
+    cost = torch.empty(P, dtype=torch.float64, device=dev)
+    n = torch.empty(P, dtype=torch.int64, device=dev)
+    ws_bytes = L.creg_pose_fit_workspace_bytes(P, N, J)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    tab = lambda t: _p(t) if J else None
+    _lib.check(L.creg_pose_fit_system_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pts) if N else None,
+                                          _p(pt_start), N, d_max, _p(tri_idx) if N else None, tab(parent), tab(child), tab(kind),
+                                          tab(origin), tab(axis), J, _p(chain), _p(center), _p(H), _p(g), _p(cost), _p(n), _p(ws),
+                                          ws_bytes, _stream()), "creg_pose_fit_system_f64")
+    return H, g, cost, n
+
+
 MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")
 
 

@@ -761,6 +761,14 @@ class SimEnv:
         out = ops.point_mesh_distance(tri, tri_start, link_T, pts, torch.as_tensor(cut, device=tri.device), d_max)
         return tuple([a[cut[p]:cut[p + 1]] for p in range(len(parts))] for a in (o.cpu().numpy() for o in out))
 
+    def fit_pose(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10):
+        """Where do the joints stand in these clouds?  Fit the robot's joint values, and its base pose when ``fit_base``, to one
+        cloud of world points per pose, starting from q0 (P,J) in ``robot.fk_table()``'s order and ``base0`` (this environment's
+        base when None): ``compute_joints.fit_cloud_poses``, which states the algorithm, its settings and the returned dict."""
+        from .compute_joints import fit_cloud_poses
+        return fit_cloud_poses(self.robot, clouds, q0, self.base if base0 is None else base0, d_max=d_max, max_iter=max_iter,
+                               fit_base=fit_base, lock=lock, lam0=lam0, tol=tol)
+
     def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0, containment=False):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
         `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""

@@ -825,6 +825,63 @@ int creg_point_mesh_f64(const double* tri, const int64_t* tri_start, int64_t n_t
                         int32_t* tri_idx, double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Pose-fit system: from the correspondences of creg_point_mesh_f64 (every point's nearest triangle, hence its link), per pose the
+ * Gauss-Newton system of fitting the robot's base pose and joint values to that pose's cloud.  The parameters of a pose are
+ * D = 6 + n_joints numbers: a rotation vector about center_p (0..2), a translation (3..5) and one value per joint of the table
+ * (6 + j).  The reference has no such step; this contract is the project's own.
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T (n_poses,n_links,16), n_links, n_poses, pts, pt_start (with its
+ *              clamping), n_pts and d_max are exactly those of creg_point_mesh_f64.
+ *              tri_idx (n_pts) int32: the rows that entry returned; -1 or any value outside [0, n_tri) means no correspondence.
+ *              parent, child, type, origin (n_joints,4,4), axis (n_joints,3), n_joints: the joint table of creg_urdf_fk_f64.
+ *              chain (n_links) uint64: bit j is set iff joint j lies on the path from the root to link l (the caller builds it
+ *              from the table; a joint with a parent or child index outside [0, n_links) sets no bit, as the forward kinematics
+ *              skips it).  center (n_poses,3): the point the base rotation turns about.
+ *   limit      D = 6 + n_joints <= 64.
+ *   frames     per pose and joint, once:  W = link_T[p, parent[j]] * origin[j]  as an affine 3x4 product, the pose on the left:
+ *              W_rc = (T_r0*O_0c + T_r1*O_1c) + T_r2*O_2c, and + T_r3 for c = 3;  o_j = W[:3,3];
+ *              a_j[r] = (W_r0*axis_0 + W_r1*axis_1) + W_r2*axis_2.  A joint with a parent or child outside [0, n_links) has
+ *              o_j = a_j = 0 (and no chain bit).
+ *   contributes   point i of pose p contributes iff (1) it is live (x == x on each coordinate), (2) 0 <= f = tri_idx[i] < n_tri,
+ *              (3) with l the largest link index whose clamped tri_start[l] is <= f (a bisection), f lies in link l's clamped
+ *              rows, and (4) dot(r, r) <= d_max*d_max for the residual r below (false for a NaN; a point with an infinite
+ *              coordinate has tri_idx -1 from creg_point_mesh_f64).
+ *   residual   (a, b, c) = the three vertices of row f posed by link_T[p, l] with the vertex formula of creg_mesh_collide_f64,
+ *              in the thread, so their bits are the posing stage's.  r = pt_tri_vec(p_i; a, b, c): the vector whose dot
+ *              pt_tri2 returns -- ap, bp, cp for cases 1, 2, 3, and q for cases 4..7 -- chosen by the same seven cases in the
+ *              same order with the same operations.  dot(r, r) has the bits of creg_point_mesh_f64's dist2 for that row.  The
+ *              closest point is  c_k = p_i[k] - r_k.
+ *   columns    3-vectors J_k of a contributing point of link l, with u x v = (u_y*v_z - u_z*v_y, u_z*v_x - u_x*v_z,
+ *              u_x*v_y - u_y*v_x) and differences taken per component first:
+ *                k = 0..2   e_k x (c - center_p), written out: (0, -v_z, v_y), (v_z, 0, -v_x), (-v_y, v_x, 0) for v = c - center_p
+ *                k = 3..5   e_(k-3)
+ *                k = 6 + j  a_j x (c - o_j) for type 1,  a_j for type 2,  when bit j of chain[l] is set
+ *              and the zero vector otherwise (type 0 or any other type, or bit j not set).
+ *   outputs    per pose, sums over its contributing points with dot(u,v) = (u_x*v_x + u_y*v_y) + u_z*v_z:
+ *              H (n_poses,D,D) fp64: H[a][b] = sum dot(J_a, J_b), stored in full; H[a][b] and H[b][a] carry the same bits.
+ *              g (n_poses,D) fp64: g[a] = sum dot(J_a, r).      cost (n_poses) fp64: sum dot(r, r).
+ *              n (n_poses) int64: the number of contributing points.
+ *              A pose with no contributing point (an empty one included) gets zeros.  The step that lowers the cost solves
+ *              H delta = g: moving the model by delta moves c by J delta.
+ *   order      a pose's rows are cut into tiles of 32 in row order from its first row.  Within a tile, every entry is summed from
+ *              0.0 over the tile's rows in ascending order, a row that does not contribute (or lies past the pose's end) adding
+ *              an exact zero.  The tiles' partials are then added in ascending tile order into four running sums, tile t into sum
+ *              t mod 4, and the entry is (s0 + s1) + (s2 + s3).  n is summed the same way in fp64, exact below 2^53.
+ * Determinism: no floating-point atomics; the order above depends on the pose's own row count alone.  Two runs give the same
+ * bits, and a pose alone in a call gives the bits it has among others.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, n_pts < 0 or >= 2^31,
+ * (n_pts >> 5) + n_poses >= 2^31, n_joints < 0 or 6 + n_joints > 64, a null tri (with n_tri > 0), tri_start, link_T, pt_start,
+ * chain, center, H, g, cost, n or workspace, a null pts or tri_idx with n_pts > 0, a null table array with n_joints > 0, a NaN
+ * or negative d_max, a workspace smaller than creg_pose_fit_workspace_bytes(n_poses, n_pts, n_joints) (the joint frames and one
+ * partial of D*D + D + 2 doubles per tile slot; 0 for the counts refused here). */
+size_t creg_pose_fit_workspace_bytes(int64_t n_poses, int64_t n_pts, int32_t n_joints);
+int creg_pose_fit_system_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                             int64_t n_poses, const double* pts, const int64_t* pt_start, int64_t n_pts, double d_max,
+                             const int32_t* tri_idx, const int32_t* parent, const int32_t* child, const int32_t* type,
+                             const double* origin, const double* axis, int32_t n_joints, const uint64_t* chain,
+                             const double* center, double* H, double* g, double* cost, int64_t* n, void* workspace,
+                             size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Containment: is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
  * call, the generalized winding number of one link's posed triangle mesh at a few points of the other.  It closes the hole the
  * two entries above share (no edge pierces a face when a mesh lies wholly inside another); the reference rejects such a pose
