@@ -16,7 +16,9 @@ This project's own, beyond the reference: ``estimate_typed_joints_from_tree`` al
 (``creg_joint_types_f64``), and ``estimate_joint_motion``, ``set_joint_limits`` and ``replay_urdf`` recover every joint's
 positions, write the observed limits and check the written file against the registration; ``cloud_fit_poses`` and
 ``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``); ``fit_cloud_poses`` and ``fit_positions``
-fit the joint positions and the base pose to clouds (``ops.pose_fit_system``, Levenberg-Marquardt).
+fit the joint positions and the base pose to clouds (``ops.pose_fit_system``, Levenberg-Marquardt); ``refine_joint_frames``,
+``set_joint_frames`` and ``refine_urdf_joints`` refine the joint frames themselves against the clouds, a bundle adjustment on
+``ops.link_moments`` (``link_twists``, ``twist_system``), and write them into a copy of the URDF.
 """
 import os
 import xml.etree.ElementTree as ET
@@ -724,4 +726,368 @@ def fit_positions(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_s
             shift[j] = float(np.abs(fitted - positions[j]).max())
             positions[j] = fitted
     fit["positions"], fit["shift"] = positions, shift
+    return fit
+
+
+# ------------------------------------------------------------------------------------------ refining the joint frames
+def joint_frame_basis(axis):
+    """u1, u2 (J,3) host arrays of the table's unit axes (J,3): k the index of the smallest |a_k| (the lowest at a tie),
+    u1 = normalize(a x e_k), u2 = a x u1.  A joint's frame parameters turn about and shift along these two: the component of a
+    frame twist along the axis itself moves nothing."""
+    axis = np.asarray(axis, np.float64).reshape(-1, 3)
+    e = np.eye(3)[np.argmin(np.abs(axis), axis=1)]
+    u1 = np.cross(axis, e)
+    u1 = u1 / np.linalg.norm(u1, axis=1, keepdims=True).clip(1e-300)
+    return u1, np.cross(axis, u1)
+
+
+def _cross_matrix(v):
+    """(...,3,3) [v]x of (...,3)."""
+    K = torch.zeros(v.shape[:-1] + (3, 3), dtype=v.dtype, device=v.device)
+    K[..., 0, 1], K[..., 0, 2], K[..., 1, 0], K[..., 1, 2], K[..., 2, 0], K[..., 2, 1] = -v[..., 2], v[..., 1], v[..., 2], -v[..., 0], -v[..., 1], v[..., 0]
+    return K
+
+
+def link_twists(table, link_T, q, center, ref, origin=None, structure=True):
+    """The twist of every parameter on every link, about ``ref`` (this project's own; plain torch on the device): table from
+    ``UrdfRobot.fk_table()``, link_T (P,L,4,4), q (P,J), center (P,3), ref (P,L,3) f64 device tensors, ``origin`` (J,4,4) the
+    joint origins when they differ from the table's -> Tw (P,L,6,M): rows 0..2 Omega, 3..5 V, so that a point c of link l moves by
+    Omega x (c - ref[p,l]) + V per unit of the parameter; zero where the parameter does not move the link (chain bit clear).
+    Columns: rotation about center_p (0..2), translation (3..5), the joints (6 + j: a_j and a_j x (rho - o_j) for a revolute one,
+    a_j as V for a prismatic one -- the columns of ``ops.pose_fit_system``), and with ``structure`` the frame parameters
+    6 + J + 4 j + m of joint j in its own frame, (w, v) = (u1, 0), (u2, 0), (0, u1), (0, u2) of ``joint_frame_basis``: the model
+    origin[j] <- origin[j] E with everything attached to the child pre-multiplied by E^-1, so the child moves by E M(q) E^-1 and
+    nothing moves at q = 0.  Revolute, R_q = Rot(a, q_j): Omega = W_r (w - R_q w), V = W_r (v - R_q v) at o_j, carried to rho by
+    + Omega x (rho - o_j).  Prismatic: V = q_j W_r (w x a), two parameters.  Fixed: none."""
+    dev, dt = link_T.device, torch.float64
+    P, L = link_T.shape[:2]
+    J = len(table["parent"])
+    kinds, parent, child = np.asarray(table["type"]), np.asarray(table["parent"]), np.asarray(table["child"])
+    axis_h = np.asarray(table["axis"], np.float64).reshape(-1, 3)
+    origin = torch.as_tensor(np.ascontiguousarray(table["origin"]), dtype=dt, device=dev) if origin is None else origin
+    chain = ops.joint_chains(table)
+    M = 6 + J + (4 * J if structure else 0)
+    Tw = torch.zeros(P, L, 6, M, dtype=dt, device=dev)
+    eye3 = torch.eye(3, dtype=dt, device=dev)
+    Tw[:, :, :3, :3] = eye3
+    Tw[:, :, 3:, 3:6] = eye3
+    Tw[:, :, 3:, :3] = _cross_matrix(ref - center[:, None, :]).transpose(-1, -2)      # column k: e_k x (rho - center)
+    u1_h, u2_h = joint_frame_basis(axis_h)
+    for j in range(J):
+        pa, ch, kind = int(parent[j]), int(child[j]), int(kinds[j])
+        if kind not in (1, 2) or not (0 <= pa < L and 0 <= ch < L):
+            continue
+        on = torch.as_tensor([float((int(chain[l]) >> j) & 1) for l in range(L)], dtype=dt, device=dev)[None, :, None]
+        W = link_T[:, pa] @ origin[j]
+        Wr, o = W[:, :3, :3], W[:, :3, 3]
+        a = torch.as_tensor(axis_h[j], device=dev)
+        aw = (Wr @ a)[:, None, :]                                                     # (P,1,3)
+        arm = ref - o[:, None, :]                                                     # (P,L,3)
+        col = 6 + J + 4 * j
+        if kind == 1:
+            Tw[:, :, :3, 6 + j] = aw * on
+            Tw[:, :, 3:, 6 + j] = torch.linalg.cross(aw.expand(P, L, 3), arm) * on
+            if structure:
+                K = _cross_matrix(a)
+                Rq = eye3 + torch.sin(q[:, j])[:, None, None] * K + (1.0 - torch.cos(q[:, j]))[:, None, None] * (K @ K)
+                for m, u in enumerate((u1_h[j], u2_h[j])):
+                    u = torch.as_tensor(u, device=dev)
+                    Om = (Wr @ (u - Rq @ u)[:, :, None])[:, None, :, 0]               # (P,1,3)
+                    Tw[:, :, :3, col + m] = Om * on
+                    Tw[:, :, 3:, col + m] = torch.linalg.cross(Om.expand(P, L, 3), arm) * on
+                    Tw[:, :, 3:, col + 2 + m] = Om * on
+        else:
+            Tw[:, :, 3:, 6 + j] = aw * on
+            if structure:
+                for m, u in enumerate((u1_h[j], u2_h[j])):
+                    v = torch.as_tensor(np.cross(u, axis_h[j]), device=dev)
+                    Tw[:, :, 3:, col + m] = (q[:, j, None] * (Wr @ v))[:, None, :] * on
+    return Tw
+
+
+def twist_system(mom, cnt, Tw):
+    """The normal system of twist columns from link moments (this project's own; plain torch on the device): mom (P,L,16) and cnt
+    (P,L) of ``ops.link_moments`` taken about the point the twists Tw (P,L,6,M) of ``link_twists`` are given about ->
+    (H (P,M,M), g (P,M), cost (P)).  With S2 = sum d d^T, S1 = sum d, n, Sx = sum d x r, Sr = sum r of (p, l):
+    H[a][b] = sum_l Om_a^T (tr(S2) I - S2) Om_b + (Om_a x S1).V_b + (Om_b x S1).V_a + n V_a.V_b, g[a] = sum_l Om_a.Sx + V_a.Sr,
+    cost = sum_l mom[15] -- per link one 6 x 6 matrix [[tr(S2) I - S2, [S1]x], [-[S1]x, n I]] between the twists."""
+    P, L = mom.shape[:2]
+    S2 = mom[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(P, L, 3, 3)
+    eye3 = torch.eye(3, dtype=mom.dtype, device=mom.device)
+    X = _cross_matrix(mom[..., 6:9])
+    M6 = torch.zeros(P, L, 6, 6, dtype=mom.dtype, device=mom.device)
+    M6[..., :3, :3] = (mom[..., 0] + mom[..., 3] + mom[..., 5])[..., None, None] * eye3 - S2
+    M6[..., :3, 3:], M6[..., 3:, :3] = X, -X
+    M6[..., 3:, 3:] = cnt.to(mom.dtype)[..., None, None] * eye3
+    H = (Tw.transpose(-1, -2) @ M6 @ Tw).sum(1)
+    g = (Tw.transpose(-1, -2) @ mom[..., 9:15, None]).sum(1)[..., 0]
+    return H, g, mom[..., 15].sum(1)
+
+
+def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lock_frames=(), lam0=1e-3,
+                        tol=1e-10):
+    """Refine the frames of a robot's movable joints against one cloud per pose: a bundle adjustment by Levenberg-Marquardt on the
+    point-to-mesh distance (this project's own).  Shared by all poses: per revolute joint four frame parameters, per prismatic
+    joint two (``link_twists``).  Per pose: its joint values and base pose, as in ``fit_cloud_poses``, whose arguments, settings
+    and stops these are; ``lock_frames`` names the joints whose frame stays.  The geometry of the zero pose is held fixed: a step
+    E_j of joint j's frame is origin[j] <- E_pj^-1 origin[j] E_j (pj the joint whose child is j's parent, if it has a step) and
+    the triangles of link child[j] pre-multiplied by E_j^-1, so the posed meshes at q = 0 do not move.  One lambda and one accept
+    / reject on the total truncated cost sum_p sum min(d^2, d_max^2).  An iteration:
+      1  link_T = G urdf_fk(current origins, q)        2  one ``ops.point_mesh_distance`` call on the current triangles
+      3  the cost                                      4  accept iff the total did not rise, else restore everything, lambda <- 10 lambda
+      5  ``ops.link_moments`` about center_p and ``twist_system``
+      6  the damped arrowhead solve by Schur complement, batched in fp64 on the device: A_p = H_pp + lambda diag,
+         (H_ss + lambda diag H_ss - sum_p H_sp A_p^-1 H_ps) ds = g_s - sum_p H_sp A_p^-1 g_p, d_p = A_p^-1 (g_p - H_ps ds).
+         Left out: what ``fit_cloud_poses`` leaves out, the frames in ``lock_frames``, and a parameter whose diagonal entry is
+         exactly 0 -- for a frame parameter the diagonal summed over the poses: a joint that never left 0 (``unobserved_frames``)
+      7  q, G as in ``fit_cloud_poses``; the origins and triangles as above
+    Returns ``fit_cloud_poses``' dict with one cost_history of totals (non-increasing by construction), iterations the steps
+    tried, rms_before / rms_after per pose and rms_all_before / rms_all_after over all live points, frames (J,4,4) the accumulated
+    E_j = E_j(1) E_j(2) ... (``set_joint_frames`` writes them into a URDF), unobserved_frames (J,4) bool, and the final origin
+    (J,4,4), tri (F,3,3) and link_T (P,L,4,4).  ``robot`` is not changed."""
+    table0 = robot.fk_table()
+    table = {k: v for k, v in table0.items() if not k.startswith("_dev")}
+    names, kinds = list(table["names"]), np.asarray(table["type"])
+    J, Dp, Ds = len(names), 6 + len(names), 4 * len(names)
+    n_links = int(table["n_links"])
+    dev, dt = _lib.device(), torch.float64
+    d_max, max_iter = float(d_max), int(max_iter)
+    if not d_max >= 0.0 or max_iter < 0 or not lam0 > 0.0:
+        raise ValueError(f"refine_joint_frames: d_max >= 0, max_iter >= 0 and lam0 > 0 expected, got {d_max}, {max_iter}, {lam0}")
+    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    P = len(parts)
+    q = torch.as_tensor(np.array(q0, np.float64).reshape(-1, J) if not isinstance(q0, torch.Tensor) else q0, dtype=dt, device=dev).clone()
+    if P < 1 or tuple(q.shape) != (P, J):
+        raise ValueError(f"refine_joint_frames: {P} clouds need q0 ({P},{J}), got {tuple(q.shape)}")
+    G = torch.eye(4, dtype=dt, device=dev) if base0 is None else torch.as_tensor(base0, dtype=dt, device=dev)
+    if tuple(G.shape) not in ((4, 4), (P, 4, 4)):
+        raise ValueError(f"refine_joint_frames: base0 must be (4,4) or ({P},4,4), got {tuple(G.shape)}")
+    G = G.expand(P, 4, 4).clone()
+
+    def rows(items, what):
+        out = set()
+        for item in items:
+            if isinstance(item, str) and item not in names:
+                raise ValueError(f"refine_joint_frames: no joint named {item!r} among {names} ({what})")
+            out.add(names.index(item) if isinstance(item, str) else int(item))
+        return out
+
+    locked, locked_f = rows(lock, "lock"), rows(lock_frames, "lock_frames")
+    free_p0 = torch.as_tensor(np.array([bool(fit_base)] * 6 + [kinds[j] in (1, 2) and j not in locked for j in range(J)]), device=dev)
+    free_s0 = torch.as_tensor(np.array([(kinds[j] == 1 or (kinds[j] == 2 and m < 2)) and j not in locked_f
+                                        for j in range(J) for m in range(4)], bool).reshape(Ds), device=dev)
+    cut_host = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
+    pts = torch.as_tensor(np.concatenate(parts) if cut_host[-1] else np.zeros((0, 3)), device=dev)
+    cut = torch.as_tensor(cut_host, device=dev)
+    pose_of = torch.repeat_interleave(torch.arange(P, device=dev), cut[1:] - cut[:-1])
+    live = ~torch.isnan(pts).any(1)
+    n_live = torch.zeros(P, dtype=dt, device=dev).index_add_(0, pose_of, live.to(dt))
+    center = torch.zeros(P, 3, dtype=dt, device=dev).index_add_(0, pose_of, torch.where(live[:, None], pts, torch.zeros_like(pts)))
+    center = center / n_live.clamp_min(1.0)[:, None]
+    ref = center[:, None, :].expand(P, n_links, 3).contiguous()
+    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
+    tri_start_host = np.asarray(robot.tri_start, np.int64)
+    tri_start = torch.as_tensor(tri_start_host, device=dev)
+    # the tables of the update: which joint's step a joint's origin is pre-multiplied by, and which a triangle's; J = "none"
+    child_joint = {int(c): j for j, c in enumerate(table["child"])}
+    before = torch.as_tensor([child_joint.get(int(pa), J) for pa in table["parent"]], dtype=torch.int64, device=dev).reshape(J)
+    tri_joint = torch.as_tensor(np.repeat([child_joint.get(l, J) for l in range(n_links)], np.diff(tri_start_host).clip(0)),
+                                dtype=torch.int64, device=dev)
+    fixed_tab = tuple(torch.as_tensor(np.ascontiguousarray(table[k]), device=dev) for k in ("parent", "child", "type"))
+    axis_dev = torch.as_tensor(np.ascontiguousarray(table["axis"]), device=dev)
+    origin = torch.as_tensor(np.ascontiguousarray(table["origin"]), dtype=dt, device=dev).clone()
+    u1, u2 = (torch.as_tensor(u, device=dev) for u in joint_frame_basis(table["axis"]))
+    revolute = torch.as_tensor((kinds == 1).astype(np.float64), device=dev)[:, None]
+    frames = torch.eye(4, dtype=dt, device=dev).expand(J, 4, 4).clone()
+    eye, eye_dev, dmax2 = np.eye(4), torch.eye(4, dtype=dt, device=dev), d_max * d_max
+    lam = float(lam0)
+    active = bool((n_live > 0).any())
+    stepped = small = False
+    iters = 0
+    unobserved = torch.zeros(P, Dp, dtype=torch.bool, device=dev)
+    unobserved_s = torch.zeros(Ds, dtype=torch.bool, device=dev)
+    H_cur = g_cur = total_cur = cost_cur = n_cur = prev = cost_first = None
+    history = []
+    for it in range(max_iter + 1):
+        tab = dict(table, _dev=fixed_tab + (origin.contiguous(), axis_dev))
+        link_T = (G[:, None] @ ops.urdf_fk(tab, q, eye)).contiguous()
+        dist, tri_idx, _ = ops.point_mesh_distance(tri, tri_start, link_T, pts, cut, d_max)
+        d2 = torch.where(live, torch.clamp(dist * dist, max=dmax2), torch.zeros_like(dist))
+        cost = torch.zeros(P, dtype=dt, device=dev).index_add_(0, pose_of, d2)
+        within = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, pose_of, (live & torch.isfinite(dist)).to(torch.int64))
+        total = float(cost.sum())
+        if it == 0:
+            accept, total_cur, cost_cur, n_cur, cost_first, link_T_cur = True, total, cost, within, cost, link_T
+        else:
+            accept = stepped and total <= total_cur
+            if stepped and not accept:
+                q, G, origin, tri, frames = prev
+                lam *= 10.0
+            elif accept:
+                lam = max(lam / 10.0, FIT_LAMBDA_MIN)
+                total_cur, cost_cur, n_cur, link_T_cur = total, cost, within, link_T
+            active = active and not (accept and small) and not lam > FIT_LAMBDA_STOP
+        history.append(total_cur)
+        if it == max_iter or not active:
+            break
+        if accept:                                                # a rejected step keeps the system of the state it went back to
+            mom, cnt = ops.link_moments(tri, tri_start, link_T, pts, cut, tri_idx, ref, d_max)
+            H_cur, g_cur, _ = twist_system(mom, cnt, link_twists(table, link_T, q, center, ref, origin))
+        dp = torch.diagonal(H_cur[:, :Dp, :Dp], dim1=1, dim2=2)
+        ds = torch.diagonal(H_cur[:, Dp:, Dp:], dim1=1, dim2=2).sum(0)
+        free_p, free_s = free_p0[None] & (dp != 0.0), free_s0 & (ds != 0.0)
+        unobserved, unobserved_s = free_p0[None] & (dp == 0.0), free_s0 & (ds == 0.0)
+        mp, ms = free_p.to(dt), free_s.to(dt)
+        A = H_cur[:, :Dp, :Dp] * mp[:, :, None] * mp[:, None, :] + torch.diag_embed(lam * dp * mp + (1.0 - mp))
+        B = H_cur[:, :Dp, Dp:] * mp[:, :, None] * ms[None, None, :]
+        chol, info = torch.linalg.cholesky_ex(A)
+        sol = torch.cholesky_solve(torch.cat([B, (g_cur[:, :Dp] * mp)[:, :, None]], 2), chol)       # A_p^-1 (H_ps | g_p)
+        S = H_cur[:, Dp:, Dp:].sum(0) * ms[:, None] * ms[None, :] + torch.diag(lam * ds * ms + (1.0 - ms)) \
+            - (B.transpose(1, 2) @ sol[:, :, :Ds]).sum(0)
+        rhs = g_cur[:, Dp:].sum(0) * ms - (B.transpose(1, 2) @ sol[:, :, Ds:]).sum(0)[:, 0]
+        chol_s, info_s = torch.linalg.cholesky_ex(S)
+        delta_s = torch.cholesky_solve(rhs[:, None], chol_s)[:, 0] * ms
+        delta_p = (sol[:, :, Ds] - (sol[:, :, :Ds] @ delta_s[:, None])[:, :, 0]) * mp
+        failed = bool((info != 0).any()) or bool(info_s != 0) or not bool(torch.isfinite(delta_s).all() & torch.isfinite(delta_p).all())
+        iters += 1
+        stepped = not failed
+        if failed:
+            lam *= 10.0
+            continue
+        small = float(torch.maximum(delta_p.abs().max(), delta_s.abs().max())) < tol
+        prev = (q, G, origin, tri, frames)
+        q = torch.where(delta_p[:, 6:] != 0.0, q + delta_p[:, 6:], q)
+        moved = (delta_p[:, :6] != 0.0).any(1)
+        G = torch.where(moved[:, None, None], _base_steps(delta_p[:, :6], center) @ G, G)
+        s = delta_s.reshape(J, 4)
+        turned = (s != 0.0).any(1)
+        w = s[:, 0:1] * u1 + s[:, 1:2] * u2
+        v = (s[:, 2:3] * u1 + s[:, 3:4] * u2) * revolute
+        E = _base_steps(torch.cat([w, v], 1), torch.zeros(J, 3, dtype=dt, device=dev))
+        E = torch.where(turned[:, None, None], E, eye_dev)
+        E_inv = torch.cat([torch.linalg.inv(E), eye_dev[None]])                # row J: no step
+        changed = turned | torch.cat([turned, torch.zeros(1, dtype=torch.bool, device=dev)])[before]
+        origin = torch.where(changed[:, None, None], E_inv[before] @ origin @ E, origin)
+        frames = torch.where(turned[:, None, None], frames @ E, frames)
+        Ei = E_inv[tri_joint]
+        shifted = torch.einsum("fij,fvj->fvi", Ei[:, :3, :3], tri) + Ei[:, None, :3, 3]
+        tri = torch.where(torch.cat([turned, torch.zeros(1, dtype=torch.bool, device=dev)])[tri_joint][:, None, None], shifted, tri).contiguous()
+    n_live_h = n_live.cpu().numpy()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rms = lambda c: np.where(n_live_h > 0, np.sqrt(c.cpu().numpy() / np.maximum(n_live_h, 1.0)), np.nan)
+        rms_all = lambda c: float(np.sqrt(c / n_live_h.sum())) if n_live_h.sum() > 0 else float("nan")
+        out = {"q": q.cpu().numpy(), "base": G.cpu().numpy(), "cost_history": history, "iterations": iters,
+               "rms_before": rms(cost_first), "rms_after": rms(cost_cur), "rms_all_before": rms_all(history[0]),
+               "rms_all_after": rms_all(history[-1]), "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names,
+               "frames": frames.cpu().numpy(), "unobserved_frames": unobserved_s.reshape(J, 4).cpu().numpy(),
+               "origin": origin.cpu().numpy(), "tri": tri.cpu().numpy(), "link_T": link_T_cur.cpu().numpy()}
+    return out
+
+
+def _xyz_rpy(T):
+    """(xyz, rpy) strings of a rigid 4x4 in URDF's fixed-axis roll-pitch-yaw, the convention ``set_inertials`` reads."""
+    return " ".join(map(str, T[:3, 3])), " ".join(map(str, R.from_matrix(T[:3, :3]).as_euler("xyz")))
+
+
+def _read_origin(elem):
+    """The 4x4 of an element's <origin> child (identity without one), xyz and rpy as ``set_inertials`` reads them."""
+    T = np.eye(4)
+    o = elem.find("origin")
+    if o is not None:
+        T[:3, :3] = R.from_euler("xyz", np.array(o.get("rpy", "0 0 0").split(), np.float64)).as_matrix()
+        T[:3, 3] = np.array(o.get("xyz", "0 0 0").split(), np.float64)
+    return T
+
+
+def set_joint_frames(urdf_file, frames_by_name, output_file):
+    """Write refined joint frames into a copy of a URDF (this project's own): frames_by_name = {joint name: E (4,4)}, the
+    accumulated steps ``refine_joint_frames`` returns in "frames".  Every joint's <origin> becomes E_pj^-1 O E_j (pj the named
+    joint whose child is this joint's parent; a joint that is not named has E = identity), and the <visual>, <collision> and
+    <inertial> origins of a named joint's child link are pre-multiplied by E_j^-1 -- xyz and rpy in URDF's fixed-axis
+    roll-pitch-yaw, as ``set_inertials`` reads them -- so the file's zero pose keeps its geometry.  An origin that does not change
+    keeps its text; a rewritten element without an <origin> (URDF's identity) gets one as its first child; <axis>, limits, names,
+    meshes and the layout are untouched; ``urdf_file`` is only read.  KeyError for a name the file does not have, ValueError for
+    a frame that is not (4,4) or a named joint whose child link the file does not hold; nothing is written in either case."""
+    tree = ET.parse(urdf_file)
+    root = tree.getroot()
+    joints = {j.get("name"): j for j in root.findall("joint")}
+    links = {l.get("name"): l for l in root.findall("link")}
+    E = {}
+    for name, frame in frames_by_name.items():
+        if name not in joints:
+            raise KeyError(f"{urdf_file}: no joint named {name!r}")
+        frame = np.asarray(frame, np.float64)
+        if frame.shape != (4, 4):
+            raise ValueError(f"set_joint_frames: the frame of {name} must be (4,4), got {frame.shape}")
+        E[name] = frame
+    by_child = {j.find("child").get("link"): name for name, j in joints.items()}
+    todo = []
+    for name, j in joints.items():
+        before = by_child.get(j.find("parent").get("link"))
+        if name not in E and before not in E:
+            continue
+        T = np.linalg.inv(E[before]) @ _read_origin(j) if before in E else _read_origin(j)
+        todo.append((j, T @ E[name] if name in E else T))
+    for name in E:
+        link = links.get(joints[name].find("child").get("link"))
+        if link is None:
+            raise ValueError(f"{urdf_file}: joint {name} has no child link in the file")
+        Ei = np.linalg.inv(E[name])
+        for tag in ("visual", "collision", "inertial"):
+            for block in link.findall(tag):
+                todo.append((block, Ei @ _read_origin(block)))
+    for elem, T in todo:
+        xyz, rpy = _xyz_rpy(T)
+        if elem.find("origin") is None:
+            elem.insert(0, ET.Element("origin"))
+        elem.find("origin").attrib.update(xyz=xyz, rpy=rpy)
+    if os.path.dirname(output_file):
+        os.makedirs(os.path.dirname(output_file), exist_ok=True)
+    tree.write(output_file, encoding="utf-8", xml_declaration=True)
+
+
+def frame_shift(frame, axis, kind=1):
+    """What an accumulated frame step E (4,4) did to a joint with unit axis ``axis`` in its own frame -> (angle between the old
+    axis and the new one E_r a in rad, distance of the old joint point -- the frame's origin -- from the new line through E_t
+    along E_r a; None for a joint that does not turn, whose line has no position)."""
+    frame, a = np.asarray(frame, np.float64), np.asarray(axis, np.float64)
+    b = frame[:3, :3] @ a
+    angle = float(np.arctan2(np.linalg.norm(np.cross(a, b)), a @ b))
+    if kind != 1:
+        return angle, None
+    t = -frame[:3, 3]
+    return angle, float(np.linalg.norm(t - (t @ b) * b / (b @ b)))
+
+
+def refine_urdf_joints(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, output_file, time_step=0, d_max=np.inf,
+                       max_iter=30):
+    """Refine the written URDF's joint frames against the raw clouds and write the result beside it (this project's own): the
+    poses of ``cloud_fit`` are the start, all loaded frames are fitted at once with the base free (``refine_joint_frames``),
+    ``d_max`` is the cloud fit's limit, and ``set_joint_frames`` writes ``output_file``; ``urdf_file`` is only read.  Returns
+    ``refine_joint_frames``' dict with "positions" (J,S,num_steps) and "shift" (J) as ``fit_positions`` adds them, and "joints",
+    per joint of ``motion`` a dict of joint, axis_angle and line_distance (``frame_shift`` of its accumulated step) and
+    max_shift."""
+    from .cluster_icp import read_point_cloud
+    robot, q, G = _cloud_fit_state(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
+    S, n = len(cm_list), int(num_steps)
+    clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
+              for s in range(S) for k in range(n)]
+    fit = refine_joint_frames(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True)
+    table = robot.fk_table()
+    set_joint_frames(urdf_file, {name: fit["frames"][j] for j, name in enumerate(fit["names"])
+                                 if not np.array_equal(fit["frames"][j], np.eye(4))}, output_file)
+    positions = np.array([np.asarray(m["positions"], np.float64).reshape(S, n) for m in motion]).reshape(len(motion), S, n)
+    shift, joints = np.zeros(len(motion)), []
+    for j, m in enumerate(motion):
+        name = f"joint_{m['child_link']}"
+        row = {"joint": name, "axis_angle": 0.0, "line_distance": None, "max_shift": 0.0}
+        if name in fit["names"]:
+            k = fit["names"].index(name)
+            fitted = fit["q"][:, k].reshape(S, n)
+            shift[j] = float(np.abs(fitted - positions[j]).max())
+            positions[j] = fitted
+            row["axis_angle"], row["line_distance"] = frame_shift(fit["frames"][k], table["axis"][k], int(table["type"][k]))
+            row["max_shift"] = float(shift[j])
+        joints.append(row)
+    fit["positions"], fit["shift"], fit["joints"] = positions, shift, joints
     return fit

@@ -396,7 +396,10 @@ def _cli_parser():
     unexplained.  --cloud_fit without --voxel_size or without --joint_limits, and --fit_max without --cloud_fit, are usage
     errors.  --fit_positions fits every frame's joint positions and base pose to its raw cloud after the cloud fit and writes
     <name>.fitted_positions.npy; --fit_iters (default 30) caps its iterations.  --fit_positions without --cloud_fit, and
-    --fit_iters without --fit_positions, are usage errors."""
+    --fit_iters without --fit_positions, are usage errors.  --refine_joints refines the URDF's joint frames against all loaded
+    raw clouds after the cloud fit and writes <name>.refined.urdf and <name>.refined_positions.npy; --refine_iters (default
+    30) caps its iterations.  --refine_joints without --cloud_fit, and --refine_iters without --refine_joints, are usage
+    errors."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
@@ -410,6 +413,8 @@ def _cli_parser():
     parser.add_argument('--fit_max', type=float, default=None)
     parser.add_argument('--fit_positions', action='store_true')
     parser.add_argument('--fit_iters', type=int, default=None)
+    parser.add_argument('--refine_joints', action='store_true')
+    parser.add_argument('--refine_iters', type=int, default=None)
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -430,6 +435,10 @@ def _cli_parser():
             parser.error("--fit_positions needs --cloud_fit: it starts from the poses the cloud fit measures")
         if ns.fit_iters is not None and not ns.fit_positions:
             parser.error("--fit_iters needs --fit_positions")
+        if ns.refine_joints and not ns.cloud_fit:
+            parser.error("--refine_joints needs --cloud_fit: it starts from the poses the cloud fit measures")
+        if ns.refine_iters is not None and not ns.refine_joints:
+            parser.error("--refine_iters needs --refine_joints")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -463,13 +472,16 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
               f"pos_max {w['pos_max']:.3g} at {w['pos_max_at']}")
 
 
-def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None):
+def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None, refined=None):
     """Write <name>.cloud_fit.json next to the URDF -- the per-frame, per-sequence, per-link and overall figures of
     ``cloud_fit``, without the per-point arrays -- and print one line per sequence (rms, p95, unexplained share) and the worst
     frame.  ``fit_max`` is written as null when it is inf.  With ``fitted`` (``fit_positions``' dict) the file gains a "fitted"
     block -- per frame the rms before and after the fit and the steps tried, per sequence and overall the rms before and
     after, per joint the largest |q_fit - q_registered| --, <name>.fitted_positions.npy (J,S,steps) is written beside
-    joint_positions.npy, and one line per sequence and one per joint are printed."""
+    joint_positions.npy, and one line per sequence and one per joint are printed.  With ``refined`` (``refine_urdf_joints``'
+    dict, "urdf" naming the file it wrote) the file gains a "refined" block -- the overall rms before and after, the steps tried,
+    per joint the angle between the old and the new axis, the distance of the old joint point from the new line and the largest
+    |q - q_registered| --, <name>.refined_positions.npy (J,S,steps) is written, and one line per joint is printed."""
     import json
     stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
     clean = lambda d: {k: (None if isinstance(v, float) and not np.isfinite(v) else v) for k, v in d.items()}
@@ -491,6 +503,11 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
             "all": {"rms_before": pooled(fitted["rms_before"], np.arange(S * num_steps)),
                     "rms_after": pooled(fitted["rms_after"], np.arange(S * num_steps))},
             "joints": [{"joint": name, "max_shift": float(d)} for name, d in zip(fitted["joint_names"], fitted["shift"])]}
+    if refined is not None:
+        np.save(stem + '.refined_positions.npy', refined["positions"])
+        report["refined"] = {"urdf": refined["urdf"], "iterations": int(refined["iterations"]),
+                             "all": clean({"rms_before": float(refined["rms_all_before"]), "rms_after": float(refined["rms_all_after"])}),
+                             "joints": [clean(dict(j)) for j in refined["joints"]]}
     with open(stem + '.cloud_fit.json', 'w') as f:
         json.dump(report, f, indent=1)
     for name, s in zip(seq_names, fit["sequences"]):
@@ -504,6 +521,13 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
             print(f"fit_positions {name}: rms {s['rms_before']:.3g} -> {s['rms_after']:.3g}")
         for j in report["fitted"]["joints"]:
             print(f"fit_positions {j['joint']}: largest |q_fit - q_registered| {j['max_shift']:.3g}")
+    if refined is not None:
+        r = report["refined"]
+        print(f"refine_joints: rms {r['all']['rms_before']:.3g} -> {r['all']['rms_after']:.3g} in {r['iterations']} steps, {r['urdf']}")
+        for j in r["joints"]:
+            line = "no line" if j["line_distance"] is None else f"old point {j['line_distance']:.3g} from the new line"
+            print(f"refine_joints {j['joint']}: axis turned by {j['axis_angle']:.3g} rad, {line}, "
+                  f"largest |q - q_registered| {j['max_shift']:.3g}")
 
 
 def main(argv=None):
@@ -536,14 +560,20 @@ def main(argv=None):
     base free, ``fit_max`` as the distance limit), ``<name>.fitted_positions.npy`` (J,S,steps) is written beside
     ``joint_positions.npy``, ``cloud_fit.json`` gains a "fitted" block, and one line per sequence (rms before -> after) and per
     joint (the largest |q_fit - q_registered|) are printed; the URDF and its limits are not touched.  It needs the cloud fit,
-    and a ``fit_iters`` needs it: ValueError before anything is written otherwise."""
+    and a ``fit_iters`` needs it: ValueError before anything is written otherwise.  With ``--refine_joints`` (or a boolean
+    ``refine_joints`` key; ``--refine_iters`` / ``refine_iters``, default 30, the option wins) the frames of the URDF's movable
+    joints are then refined against all loaded raw clouds at once (``refine_urdf_joints``: from the cloud fit's poses, the base
+    free, ``fit_max`` as the distance limit), ``<name>.refined.urdf`` and ``<name>.refined_positions.npy`` (J,S,steps) are
+    written beside the URDF, ``cloud_fit.json`` gains a "refined" block and one line per joint is printed; the original URDF
+    keeps every byte.  It needs the cloud fit, and a ``refine_iters`` needs it: ValueError before anything is written
+    otherwise."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
     from .compute_joints import (cloud_fit, create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
-                                 estimate_typed_joints_from_tree, fit_positions, replay_urdf, set_collision_meshes,
+                                 estimate_typed_joints_from_tree, fit_positions, refine_urdf_joints, replay_urdf, set_collision_meshes,
                                  set_inertials, set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
     args = _cli_parser().parse_args(argv)
@@ -605,6 +635,17 @@ def main(argv=None):
     fit_iters = 30 if fit_iters is None else int(fit_iters)
     if fit_iters < 0:
         raise ValueError(f"fit_iters must be >= 0, got {fit_iters}")
+    want_refine = bool(args.refine_joints or robot_params.get('refine_joints'))
+    refine_iters = args.refine_iters if args.refine_iters is not None else robot_params.get('refine_iters')
+    if want_refine and not want_fit:
+        raise ValueError("refine_joints starts from the poses the cloud fit measures: give --cloud_fit (or a cloud_fit key in "
+                         "parameters.json) with --refine_joints")
+    if refine_iters is not None and not want_refine:
+        raise ValueError("a refine_iters is the iteration cap of refine_joints: give --refine_joints (or a refine_joints key in "
+                         "parameters.json) with it")
+    refine_iters = 30 if refine_iters is None else int(refine_iters)
+    if refine_iters < 0:
+        raise ValueError(f"refine_iters must be >= 0, got {refine_iters}")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -686,7 +727,14 @@ def main(argv=None):
                 fitted = fit_positions(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START,
                                        d_max=fit_max, max_iter=fit_iters)
                 fitted["joint_names"] = [f"joint_{m['child_link']}" for m in motion]
-            _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path], fitted)
+            refined = None
+            if want_refine:
+                refined_path = urdf_path[:-len('.urdf')] + '.refined.urdf'
+                refined = refine_urdf_joints(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START,
+                                             refined_path, d_max=fit_max, max_iter=refine_iters)
+                refined["urdf"] = refined_path
+            _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path], fitted,
+                              refined)
     return urdf_path
 
 

@@ -784,6 +784,41 @@ def pose_fit_system(tri, tri_start, link_T, pts, pt_start, tri_idx, table, cente
     return H, g, cost, n
 
 
+def link_moments(tri, tri_start, link_T, pts, pt_start, tri_idx, ref, d_max=float("inf")):
+    """The 16 moment sums per (pose, link) of the correspondences (creg_link_moments_f64; the contract is in include/creg.h): tri,
+    tri_start, link_T, pts, pt_start, tri_idx and ``d_max`` as ``pose_fit_system`` takes them, ref (P,L,3) f64 the point the
+    moments of every (pose, link) are taken about -> (mom (P,L,16) f64, cnt (P,L) int64) on the device: per (pose, link) the sums
+    of d d^T (6: xx xy xz yy yz zz), d (3), d x r (3), r (3) and r.r over its contributing points, d = c - ref, and their number.
+    One call for all poses; no joint table and no limit on a parameter count (``compute_joints.twist_system`` turns the moments
+    into a normal system).  tri_start and pt_start are not read back; the kernel clamps them.  ValueError before any launch: a bad
+    shape or dtype, a negative or NaN ``d_max``."""
+    L = _lib.load()
+    d_max = float(d_max)
+    if not d_max >= 0.0:
+        raise ValueError(f"link_moments: d_max must be >= 0 (inf allowed), got {d_max}")
+    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
+    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
+    tri_idx, ref = _need(tri_idx, torch.int32, "tri_idx"), _need(ref, torch.float64, "ref")
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
+            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
+            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1 \
+            or tuple(tri_idx.shape) != (pts.shape[0],) or tuple(ref.shape) != (link_T.shape[0], link_T.shape[1], 3):
+        raise ValueError(f"link_moments: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) / tri_idx (N) / "
+                         f"ref (P,L,3) expected, got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, "
+                         f"{tuple(pts.shape)}, {tuple(pt_start.shape)}, {tuple(tri_idx.shape)}, {tuple(ref.shape)}")
+    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    mom = torch.empty(P, n_links, 16, dtype=torch.float64, device=dev)
+    cnt = torch.empty(P, n_links, dtype=torch.int64, device=dev)
+    ws_bytes = L.creg_link_moments_workspace_bytes(P, N, n_links)
+    ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+    _lib.check(L.creg_link_moments_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pts) if N else None,
+                                       _p(pt_start), N, d_max, _p(tri_idx) if N else None, _p(ref), _p(mom), _p(cnt), _p(ws), ws_bytes,
+                                       _stream()), "creg_link_moments_f64")
+    return mom, cnt
+
+
 MESH_INERTIA_KEYS = ("sums", "volume", "area", "closure", "mass", "com", "inertia", "principal", "axes")
 
 

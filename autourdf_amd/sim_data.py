@@ -769,6 +769,16 @@ class SimEnv:
         return fit_cloud_poses(self.robot, clouds, q0, self.base if base0 is None else base0, d_max=d_max, max_iter=max_iter,
                                fit_base=fit_base, lock=lock, lam0=lam0, tol=tol)
 
+    def refine_joints(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lock_frames=(), lam0=1e-3,
+                      tol=1e-10):
+        """Where do the joint axes and origins lie in these clouds?  Refine the frames of the robot's movable joints, shared by
+        all poses, together with every pose's joint values and base pose (``fit_pose``'s arguments; ``lock_frames`` names the
+        joints whose frame stays): ``compute_joints.refine_joint_frames``, which states the algorithm and the returned dict.
+        The environment's robot is not changed; ``compute_joints.set_joint_frames`` writes the result's "frames" into a URDF."""
+        from .compute_joints import refine_joint_frames
+        return refine_joint_frames(self.robot, clouds, q0, self.base if base0 is None else base0, d_max=d_max, max_iter=max_iter,
+                                   fit_base=fit_base, lock=lock, lock_frames=lock_frames, lam0=lam0, tol=tol)
+
     def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0, containment=False):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.
         `link_T` (L,4,4) device poses replace the host forward kinematics and its upload."""

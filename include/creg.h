@@ -882,7 +882,46 @@ int creg_pose_fit_system_f64(const double* tri, const int64_t* tri_start, int64_
                              size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Containment: is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
+ * Link moments: from the same correspondences, per pose and link the 16 sums that every least-squares problem whose columns are
+ * rigid twist fields is a small product around.  Restricted to the points of one link, a column of the pose-fit system above, or
+ * of any refinement of the joint frames, moves the closest point c by Omega x (c - rho) + V; with d = c - rho the normal system
+ * is  H[a][b] = Omega_a^T (tr(S2) I - S2) Omega_b + (Omega_a x S1).V_b + (Omega_b x S1).V_a + n V_a.V_b,
+ * g[a] = Omega_a.Sx + V_a.Sr  summed over the links, for S2 = sum d d^T, S1 = sum d, Sx = sum d x r, Sr = sum r and the count n.
+ * The sums do not depend on the parameter count.  The reference has no such step; this contract is the project's own.
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T, n_links, n_poses, pts, pt_start (with its clamping), n_pts,
+ *              d_max and tri_idx are exactly those of the pose-fit entry above.  There is no joint table and no limit on a
+ *              parameter count.  ref (n_poses,n_links,3) fp64: the point rho the moments of (p, l) are taken about.
+ *   contributes, residual   word for word those of the pose-fit entry: the same four conditions, the same bisection for the link
+ *              l, the vertices posed in the thread, r = pt_tri_vec(p_i; a, b, c), the test dot(r, r) <= d_max*d_max, c_k =
+ *              p_i[k] - r_k.  dot(r, r) has the bits of the point-mesh entry's dist2 for that row.
+ *   terms      of a contributing row of (p, l), with d_k = c_k - ref[p,l][k] per component and dot and x as written above, single
+ *              operations, no contraction, in this order:
+ *                0..5    d_x*d_x, d_x*d_y, d_x*d_z, d_y*d_y, d_y*d_z, d_z*d_z
+ *                6..8    d_x, d_y, d_z
+ *                9..11   (d x r)_x, (d x r)_y, (d x r)_z
+ *                12..14  r_x, r_y, r_z
+ *                15      dot(r, r)
+ *   outputs    mom (n_poses,n_links,16) fp64: the 16 sums in that order over the contributing rows of (p, l).
+ *              cnt (n_poses,n_links) int64: their number.  Every (p, l) is written, with zeros where nothing contributes.
+ *   order      a pose's rows are cut into tiles of 64 in row order from its first row.  Within a tile, every sum of (p, l) starts
+ *              from 0.0 and runs over the tile's rows in ascending order; a row that does not contribute to (p, l) is skipped
+ *              (adding +0.0 would give the same bits).  The tiles' partials are then added in ascending tile order into four
+ *              running sums, tile t into sum t mod 4, and the result is (s0 + s1) + (s2 + s3).  cnt is summed the same way in
+ *              fp64, exact below 2^53.
+ * Determinism: no floating-point atomics.  Two runs give the same bits, a pose alone in a call gives the bits it has among
+ * others, and the result of (p, l) does not depend on the rows of other links in the same tiles.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, n_pts < 0 or >= 2^31,
+ * (n_pts >> 6) + n_poses >= 2^31, n_poses * n_links * 17 >= 2^39, a null tri (with n_tri > 0), tri_start, link_T, pt_start, ref,
+ * mom, cnt or workspace, a null pts or tri_idx with n_pts > 0, a NaN or negative d_max, a workspace smaller than
+ * creg_link_moments_workspace_bytes(n_poses, n_pts, n_links) (17 doubles per tile slot and link; 0 for the counts refused here). */
+size_t creg_link_moments_workspace_bytes(int64_t n_poses, int64_t n_pts, int32_t n_links);
+int creg_link_moments_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                          int64_t n_poses, const double* pts, const int64_t* pt_start, int64_t n_pts, double d_max,
+                          const int32_t* tri_idx, const double* ref, double* mom, int64_t* cnt, void* workspace,
+                          size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Containment:is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
  * call, the generalized winding number of one link's posed triangle mesh at a few points of the other.  It closes the hole the
  * two entries above share (no edge pierces a face when a mesh lies wholly inside another); the reference rejects such a pose
  * because Bullet's hulls overlap.  The winding number is +1 inside a closed outward-oriented mesh, -1 inside an inward-oriented
