@@ -1,0 +1,263 @@
+"""CPU: the builders of tests/_fit_edges.py reach what they are built for, and its ordered restatements of the pose-fit system and
+the link moments are sums of the right terms: they lie within the bounds the GPU tests of both entries already use, measured
+against the long-double sums of _pose_fit_ref.system and _link_moments_ref.moments --
+
+    (n + 64) 2^-53 sum |term|     pose fit, n the pose's count
+    (2 n + 8) 2^-53 sum |term|    link moments, n the pair's count
+
+-- on every layout and width the GPU file compares bit for bit.  No GPU, no kernel: every figure here comes from numpy."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _fit_edges as E  # noqa: E402
+import _link_moments_ref as lm  # noqa: E402
+import _pose_fit_ref as pf  # noqa: E402
+
+EPS = 2.0 ** -53
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.int64)
+
+
+@pytest.fixture(scope="module")
+def robot():
+    return E.chain_robot()
+
+
+@pytest.fixture(scope="module")
+def cases(robot):
+    out = {name: E.layout(robot, name) for name in "ABCD"}
+    out["C_loose"] = E.loose_ends(out["C"])
+    return out
+
+
+# ------------------------------------------------------------------------------------------ the robot and the layouts
+def test_chain_robot_and_its_tables(robot):
+    table = robot["table"]
+    assert robot["tri"].shape == (236, 3, 3) and list(robot["tri_start"]) == list(4 * np.arange(60))
+    assert set(table["type"]) == {0, 1, 2, 3}                                   # "any other type" is there
+    assert table["type"][E.HIGH_BIT] == 1 and table["type"][E.HIGH_BIT + 1] == 2 and all(table["type"][j] in (1, 2) for j in E.SKIPPED)
+    for J in E.POSE_FIT_WIDTHS:
+        t = E.table_of_width(robot, J)
+        assert len(t["parent"]) == len(t["type"]) == len(t["origin"]) == J and t["n_links"] == 59
+        assert "_dev_fit" not in t and t["parent"] is not table["parent"]
+    full = E.table_of_width(robot, 58)
+    assert full["parent"][1] == -1 and full["child"][3] == 59 and table["parent"][1] == 1 and table["child"][3] == 4
+    chain = pf.chains(full)
+    assert chain[58] == sum(1 << j for j in range(4, 58)) and chain[3] == 1 << 2 and chain[4] == 0     # the chain restarts after joint 3
+    from autourdf_amd import ops
+    assert [int(x) for x in ops.joint_chains(full)] == chain
+    T = E.link_states(robot)
+    assert T.shape == (15, 59, 4, 4) and np.abs(T[:, :, :3, :3] @ T[:, :, :3, :3].transpose(0, 1, 3, 2) - np.eye(3)).max() < 1e-12
+
+
+def test_layouts_have_the_rows_they_are_built_for(cases):
+    """Layout A: its listed row counts and tile counts, empty poses first, last and in a run, pose starts on and off a multiple of
+    the tile.  B: every pose its own slot.  C: A's rows with 5 unowned rows in front and 7 behind.  In each: all seven pt_tri_vec
+    cases among the contributing rows, every link hit, a good share of rows beyond d_max, and the NaN row and the five rows
+    without correspondence contribute nothing."""
+    a, b, c = cases["A"], cases["B"], cases["C"]
+    assert tuple(np.diff(a["pt_start"])) == E.LAYOUT_A and len(a["pts"]) == sum(E.LAYOUT_A) == 1093 and a["pt_start"][0] == 0
+    sizes = np.array(E.LAYOUT_A)
+    assert tuple((sizes + 31) // 32) == E.PF_TILES_A and tuple((sizes + 63) // 64) == E.LM_TILES_A
+    assert {t % 4 for t in E.PF_TILES_A if t >= 4} == {0, 1, 2} and 3 in E.PF_TILES_A and 6 % 4 == 2       # a main loop with a tail of 0, 1, 2 ...
+    assert {t % 4 for t in E.LM_TILES_A if t >= 4} == {0, 1} and {2, 3} <= set(E.LM_TILES_A)                # ... and the tails alone: 1, 2, 3 tiles
+    starts = a["pt_start"][:-1][sizes > 0]
+    assert (starts % 64 == 0).any() and (starts % 32 != 0).any() and (starts % 32 == 0).sum() >= 3
+    assert tuple(np.diff(b["pt_start"])) == E.LAYOUT_B and len(b["link_T"]) == 101
+    assert tuple(np.diff(c["pt_start"])) == E.LAYOUT_A and c["pt_start"][0] == 5 and c["pt_start"][-1] == len(c["pts"]) - 7
+    loose = cases["C_loose"]["pt_start"]
+    assert loose[0] == -3 and loose[-1] == len(c["pts"]) + 9 and (np.diff(loose) >= 0).all()
+    for name in "ABCD":
+        case = cases[name]
+        assert (np.diff(case["pt_start"]) >= 0).all() and case["tri_idx"].dtype == np.int32
+        assert np.isfinite(np.delete(case["pts"], case["nan_row"], 0)).all() and np.isnan(case["pts"][case["nan_row"], 0])
+        assert list(case["tri_idx"][case["bad_rows"]]) == [-1, 236, 237, -2 ** 31, 2 ** 31 - 1]
+        want = E.moments_of(case)
+        ok = want["ok"]
+        counts = np.bincount(want["case"][ok], minlength=8)[1:]
+        print(name, dict(zip(pf.CASES, counts)), "contributing", int(ok.sum()), "of", len(ok))
+        if name != "B":                                            # B's 170 rows are about slots, not coverage
+            assert (counts >= 2).all(), (name, dict(zip(pf.CASES, counts)))
+            assert set(want["link"][ok]) == set(range(59)), name
+        owned = slice(int(case["pt_start"][0]), int(case["pt_start"][-1]))
+        assert 0.05 < 1.0 - ok[owned].mean() < 0.5, name                       # rows beyond d_max in most tiles, most rows within
+        assert not ok[case["bad_rows"]].any() and not ok[case["nan_row"]]
+        f = case["tri_idx"][owned]
+        assert {0, 3} <= set(f[(f >= 0) & (f < 236)] % 4)                       # rows at a link's first and last triangle
+
+
+# ------------------------------------------------------------------------------------------ the restatements against the long-double sums
+@pytest.mark.parametrize("J", E.POSE_FIT_WIDTHS)
+@pytest.mark.parametrize("name", ["A", "B", "C", "C_loose", "D"])
+def test_ordered_system_lies_within_the_summation_bound(robot, cases, name, J):
+    case, table = cases[name], E.table_of_width(robot, J)
+    got, want = E.system_of(case, table), E.system_of(case, table, ordered=False)
+    D = 6 + J
+    assert got["H"].shape == (len(case["link_T"]), D, D)
+    np.testing.assert_array_equal(got["n"], want["n"])
+    np.testing.assert_array_equal(bits(got["H"]), bits(got["H"].transpose(0, 2, 1)))
+    worst = 0.0
+    for p in range(len(got["n"])):
+        k = (got["n"][p] + 64) * EPS
+        for key in ("H", "g", "cost"):
+            err, bound = np.abs(got[key][p] - want[key][p]), k * want[key + "_abs"][p]
+            assert (err <= bound).all(), (p, key, float(np.max(err - bound)))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                worst = max(worst, float(np.nanmax(np.where(bound > 0, err / bound, 0.0))))
+        if got["n"][p] == 0:
+            assert not bits(got["H"][p]).any() and not bits(got["g"][p]).any() and bits(got["cost"][p:p + 1])[0] == 0       # +0.0, not -0.0
+    print(f"{name} D = {D}: largest |ordered - long double| / bound {worst:.3g}")
+    empty = np.diff(np.stack(E.pose_rows(case["pt_start"], len(case["pts"]))), axis=0)[0] == 0
+    assert (got["n"][empty] == 0).all() and empty.sum() == {"A": 4, "B": 0, "C": 4, "C_loose": 2, "D": 0}[name]
+    # columns that nothing moves: type 0, type 3, the skipped joints, and a joint no contributing link hangs on
+    kinds = np.asarray(table["type"])
+    still = [6 + j for j in range(J) if kinds[j] not in (1, 2) or (J == 58 and j in E.SKIPPED)]
+    assert not bits(got["H"][:, still, :]).any() and not bits(got["H"][:, :, still]).any() and not bits(got["g"][:, still]).any()
+    if J == 58 and name != "B":
+        moving = [6 + j for j in range(J) if 6 + j not in still]
+        big = int(np.argmax(got["n"]))
+        assert len(still) >= 10 and (got["H"][big][moving, moving] > 0).all() and max(moving) >= 6 + 32
+
+
+@pytest.mark.parametrize("L", E.MOMENT_WIDTHS)
+@pytest.mark.parametrize("name", ["A", "B", "C", "C_loose", "D"])
+def test_ordered_moments_lie_within_the_summation_bound(cases, name, L):
+    case = E.cut_links(cases[name], L)
+    assert len(case["tri"]) == 4 * L and case["ref"].shape[1] == L and case["tri_start"][-1] == 4 * L
+    got, want = E.moments_of(case), E.moments_of(case, ordered=False)
+    np.testing.assert_array_equal(got["cnt"], want["cnt"])
+    bound = (2.0 * got["cnt"][:, :, None] + 8.0) * EPS * want["mom_abs"]
+    err = np.abs(got["mom"] - want["mom"])
+    assert (err <= bound).all(), float((err - bound).max())
+    with np.errstate(invalid="ignore", divide="ignore"):
+        print(f"{name} L = {L}: largest |ordered - long double| / bound {float(np.nanmax(np.where(bound > 0, err / bound, 0.0))):.3g}")
+    assert not bits(got["mom"][got["cnt"] == 0]).any()
+    assert got["cnt"].sum() > 0 and (name == "B" or (got["cnt"].sum(0) > 0).all())        # every one of the L links is hit
+    assert not got["ok"][case["tri_idx"] >= 4 * L].any()                        # a row past the cut mesh: no correspondence
+
+
+def test_order_changes_bits_where_the_mutations_would(robot, cases):
+    """The bit comparison can see what the bound cannot: on pose 11 of layout A (161 rows: six tiles of 32, a main loop and a tail
+    of two), the tail's second tile added into s0, a sum in plain row order and a tile's last row dropped each change bits of H,
+    and the first two stay inside the (n + 64) 2^-53 sum |term| bound."""
+    case, table = cases["A"], E.table_of_width(robot, 10)
+    p = 11
+    s, e = int(case["pt_start"][p]), int(case["pt_start"][p + 1])
+    dmax2 = np.float64(case["d_max"]) ** 2
+    ok, _, _, _, _, Jm = pf.point_terms(case["tri"], case["tri_start"], case["link_T"][p], case["pts"][s:e], case["tri_idx"][s:e], table,
+                                        pf.chains(table), case["center"][p], dmax2)
+    terms = ((Jm[:, :, None, 0] * Jm[:, None, :, 0] + Jm[:, :, None, 1] * Jm[:, None, :, 1]) + Jm[:, :, None, 2] * Jm[:, None, :, 2]).reshape(e - s, -1)
+    right = E.ordered_sum(terms, 32)
+    np.testing.assert_array_equal(bits(right), bits(E.system_of(case, table)["H"][p].ravel()))
+    parts = [E.ordered_sum(terms[32 * t:32 * t + 32], 32) for t in range(6)]
+    by_hand = ((parts[0] + parts[4]) + (parts[1] + parts[5])) + (parts[2] + parts[3])
+    np.testing.assert_array_equal(bits(by_hand), bits(right))
+    tail_into_s0 = (((parts[0] + parts[4]) + parts[5]) + parts[1]) + (parts[2] + parts[3])
+    in_row_order = np.zeros(terms.shape[1])
+    for row in terms:
+        in_row_order = in_row_order + row
+    last = next(row for row in (31, 63, 95, 127, 159) if ok[row])              # a tile's last row that contributes
+    dropped = terms.copy()
+    dropped[last] = 0.0
+    changed = [int((bits(other) != bits(right)).sum()) for other in (tail_into_s0, in_row_order, E.ordered_sum(dropped, 32))]
+    print("entries of H (16 x 16) whose bits change: tail into s0, row order, a last row dropped:", changed)
+    assert min(changed) >= 8
+    bound = (ok.sum() + 64) * EPS * np.abs(terms).sum(0)
+    assert (np.abs(tail_into_s0 - right) <= bound).all() and (np.abs(in_row_order - right) <= bound).all()
+
+
+def test_moments_tail_routing_shows_only_behind_a_main_loop(cases):
+    """Why layout D exists.  With two or three tiles and no main loop, the tail's second tile added into s0 instead of s1 gives
+    (p0 + p1) + (p2 + 0) either way: no pose of layout A (at most five tiles of 64) can see that mistake in the moments' finish
+    pass.  Pose 1 of layout D has seven tiles -- s0 = p0 + p4, s1 = p1 + p5, s2 = p2 + p6, s3 = p3 -- and there it changes bits."""
+    sizes = np.array(E.LAYOUT_D)
+    assert tuple((sizes + 63) // 64) == E.LM_TILES_D and tuple((sizes + 31) // 32) == E.PF_TILES_D and max(E.LM_TILES_A) < 6
+    one = E.one_pose(cases["D"], 1)
+    right = E.moments_of(one)["mom"][0]
+    tiles = 7
+    by_tile = dict(one, link_T=np.repeat(one["link_T"], tiles, 0), ref=np.repeat(one["ref"], tiles, 0), center=np.repeat(one["center"], tiles, 0),
+                   pt_start=np.minimum(64 * np.arange(tiles + 1), 385).astype(np.int64))
+    p = E.moments_of(by_tile)["mom"]
+    by_hand = ((p[0] + p[4]) + (p[1] + p[5])) + ((p[2] + p[6]) + p[3])
+    np.testing.assert_array_equal(bits(by_hand), bits(right))
+    tail_into_s0 = (((p[0] + p[4]) + p[5]) + p[1]) + ((p[2] + p[6]) + p[3])
+    changed = int((bits(tail_into_s0) != bits(right)).sum())
+    print(f"moments of pose 1 of layout D whose bits change with tile 5 added into s0: {changed} of {right.size}")
+    assert changed >= 8
+
+
+def test_loose_ends_own_the_rows_in_front_and_behind(robot, cases):
+    """pt_start[0] = -3 and pt_start[P] = n_pts + 9 are clamped to 0 and n_pts: the restatement then gives pose 0 the five rows in
+    front (it had none) and the last pose the seven behind, and every pose between keeps its bits."""
+    c, loose, table = cases["C"], cases["C_loose"], E.table_of_width(robot, 9)
+    owning = dict(c, pt_start=np.concatenate([[0], c["pt_start"][1:-1], [len(c["pts"])]]))
+    a, b, tight = E.system_of(loose, table), E.system_of(owning, table), E.system_of(c, table)
+    for key in ("H", "g", "cost", "n"):
+        np.testing.assert_array_equal(bits(a[key]), bits(b[key]))
+        np.testing.assert_array_equal(bits(a[key][1:-1]), bits(tight[key][1:-1]))
+    assert tight["n"][0] == 0 and a["n"][0] > 0 and tight["n"][-1] == 0 and a["n"][-1] > 0
+    ma, mb = E.moments_of(loose), E.moments_of(owning)
+    np.testing.assert_array_equal(bits(ma["mom"]), bits(mb["mom"]))
+    assert ma["cnt"][0].sum() == a["n"][0] and ma["cnt"][-1].sum() == a["n"][-1]
+
+
+# ------------------------------------------------------------------------------------------ table and link edges
+def test_border_case_counts_by_hand():
+    for bad in (False, True):
+        case = E.border_case(bad=bad)
+        assert list(case["tri_start"]) == [-5, 4, 4, 4, 12, 23] and list(case["tri_idx"][:6]) == [0, 3, 4, 11, 12, 15]
+        want = E.moments_of(case)
+        by_hand = np.bincount(E.border_links(case["tri_idx"]), minlength=5)
+        np.testing.assert_array_equal(want["cnt"][0], by_hand)
+        assert by_hand[1] == by_hand[2] == 0 and (by_hand[[0, 3, 4]] >= 2).all() and by_hand.sum() == (35 if bad else 40)
+        sys_ = E.system_of(case, lm._no_joints(5))
+        assert sys_["n"][0] == by_hand.sum() and sys_["ok"].sum() == by_hand.sum()
+        if bad:
+            assert not sys_["ok"][8:13].any() and sys_["ok"][[7, 13]].all()
+            # the neighbours keep their bits: the same answer as with the five rows' points made NaN instead
+            other = E.border_case(bad=False)
+            other["pts"][8:13] = np.nan
+            for key in ("H", "g", "cost"):
+                np.testing.assert_array_equal(bits(sys_[key]), bits(E.system_of(other, lm._no_joints(5))[key]))
+
+
+def test_gate_and_zero_gate_in_the_restatement():
+    below = float(np.nextafter(E.GATE, 0.0))
+    assert below * below < 0.0625 == E.GATE * E.GATE
+    for d_max, n in ((E.GATE, 1), (below, 0), (np.inf, 1)):
+        case = E.gate_case(d_max)
+        got = E.system_of(case, lm._no_joints(1))
+        assert got["n"][0] == n and got["cost"][0] == 0.0625 * n and (got["case"][0] == 1) == bool(n)
+        assert E.moments_of(case)["cnt"][0, 0] == n
+    z = E.zero_gate_case()
+    got = E.system_of(z, lm._no_joints(1))
+    assert list(got["n"]) == [1, 0] and got["cost"][0] == 0.0 and not got["g"].any() and not got["H"][1].any()
+    np.testing.assert_array_equal(got["H"][0, 3:6, 3:6], np.eye(3))
+    assert list(E.moments_of(z)["cnt"][:, 0]) == [1, 0]
+
+
+def test_last_link_carries_the_chain_above_bit_32(robot):
+    case, table = E.last_link_case(robot), E.table_of_width(robot, 58)
+    chain = pf.chains(table)
+    got = E.system_of(case, table)
+    assert got["n"][0] == 48
+    kinds = np.asarray(table["type"])
+    diag = np.diagonal(got["H"][0])
+    for j in range(58):
+        moves = kinds[j] in (1, 2) and j >= 4                                   # joints 4 .. 57 are on the last link's chain
+        assert (diag[6 + j] > 0) == moves and (got["g"][0, 6 + j] != 0) == moves, j
+    assert sum(1 for j in range(32, 58) if kinds[j] == 1) >= 2 and sum(1 for j in range(32, 58) if kinds[j] == 2) >= 2
+    cleared = list(chain)
+    cleared[58] &= ~(1 << E.HIGH_BIT)
+    less = E.system_of(case, table, chain=cleared)
+    k = 6 + E.HIGH_BIT
+    assert not less["H"][0, k].any() and not less["H"][0, :, k].any() and less["g"][0, k] == 0.0
+    keep = np.arange(64) != k
+    np.testing.assert_array_equal(bits(less["H"][0][np.ix_(keep, keep)]), bits(got["H"][0][np.ix_(keep, keep)]))
+    np.testing.assert_array_equal(bits(less["g"][0][keep]), bits(got["g"][0][keep]))
