@@ -22,6 +22,7 @@ fit the joint positions and the base pose to clouds (``ops.pose_fit_system``, Le
 """
 import os
 import xml.etree.ElementTree as ET
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -589,6 +590,66 @@ def _base_steps(delta, center):
     return U
 
 
+def _fit_arguments(who, J, clouds, q0, base0, d_max, max_iter, lam0, dev):
+    """The arguments ``fit_cloud_poses`` and ``refine_joint_frames`` share, checked (ValueError with ``who`` in front) and coerced ->
+    (d_max, max_iter, parts: the P clouds as (n_p,3) host arrays, q (P,J) and G (P,4,4): fresh f64 device tensors)."""
+    d_max, max_iter = float(d_max), int(max_iter)
+    if not d_max >= 0.0 or max_iter < 0 or not lam0 > 0.0:
+        raise ValueError(f"{who}: d_max >= 0, max_iter >= 0 and lam0 > 0 expected, got {d_max}, {max_iter}, {lam0}")
+    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    P = len(parts)
+    q = torch.as_tensor(np.array(q0, np.float64).reshape(-1, J) if not isinstance(q0, torch.Tensor) else q0, dtype=torch.float64, device=dev).clone()
+    if P < 1 or tuple(q.shape) != (P, J):
+        raise ValueError(f"{who}: {P} clouds need q0 ({P},{J}), got {tuple(q.shape)}")
+    G = torch.eye(4, dtype=torch.float64, device=dev) if base0 is None else torch.as_tensor(base0, dtype=torch.float64, device=dev)
+    if tuple(G.shape) not in ((4, 4), (P, 4, 4)):
+        raise ValueError(f"{who}: base0 must be (4,4) or ({P},4,4), got {tuple(G.shape)}")
+    return d_max, max_iter, parts, q, G.expand(P, 4, 4).clone()
+
+
+def _joint_rows(who, names, items, what=""):
+    """The table rows of ``items``, joint names or rows (``what`` names the argument in the ValueError for an unknown name)."""
+    out = set()
+    for item in items:
+        if isinstance(item, str) and item not in names:
+            raise ValueError(f"{who}: no joint named {item!r} among {names}" + (f" ({what})" if what else ""))
+        out.add(names.index(item) if isinstance(item, str) else int(item))
+    return out
+
+
+def _pack_clouds(parts, robot, dev):
+    """The clouds of a fit on the device, packed for ``ops.point_mesh_distance``: pts (N,3), cut (P+1) its pt_start, pose_of (N),
+    live (N) not NaN, n_live (P) f64, center (P,3) the mean of a pose's live points, and the robot's tri (F,3,3) and tri_start."""
+    P = len(parts)
+    cut_host = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
+    pts = torch.as_tensor(np.concatenate(parts) if cut_host[-1] else np.zeros((0, 3)), device=dev)
+    cut = torch.as_tensor(cut_host, device=dev)
+    pose_of = torch.repeat_interleave(torch.arange(P, device=dev), cut[1:] - cut[:-1])
+    live = ~torch.isnan(pts).any(1)
+    n_live = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, pose_of, live.to(torch.float64))
+    center = torch.zeros(P, 3, dtype=torch.float64, device=dev).index_add_(0, pose_of, torch.where(live[:, None], pts, torch.zeros_like(pts)))
+    center = center / n_live.clamp_min(1.0)[:, None]
+    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
+    tri_start = torch.as_tensor(robot.tri_start, device=dev)
+    return SimpleNamespace(pts=pts, cut=cut, pose_of=pose_of, live=live, n_live=n_live, center=center, tri=tri, tri_start=tri_start)
+
+
+def _truncated_cost(c, tri, link_T, d_max):
+    """Steps 2 and 3 of an iteration on the clouds ``c`` of ``_pack_clouds``: one ``ops.point_mesh_distance`` call -> (tri_idx (N),
+    cost (P) the sum of min(d^2, d_max^2) over a pose's live points, within (P) int64 its live points within ``d_max``)."""
+    dist, tri_idx, _ = ops.point_mesh_distance(tri, c.tri_start, link_T, c.pts, c.cut, d_max)
+    d2 = torch.where(c.live, torch.clamp(dist * dist, max=d_max * d_max), torch.zeros_like(dist))
+    cost = torch.zeros(len(c.n_live), dtype=torch.float64, device=dist.device).index_add_(0, c.pose_of, d2)
+    within = torch.zeros(len(c.n_live), dtype=torch.int64, device=dist.device).index_add_(0, c.pose_of, (c.live & torch.isfinite(dist)).to(torch.int64))
+    return tri_idx, cost, within
+
+
+def _rms(n_live, cost):
+    """sqrt(cost / live points) per pose on the host, NaN for a pose without live points."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(n_live > 0, np.sqrt(cost / np.maximum(n_live, 1.0)), np.nan)
+
+
 def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10):
     """Fit a robot's joint values and base pose to one cloud per pose by Levenberg-Marquardt on the point-to-mesh distance (this
     project's own): robot a ``UrdfRobot`` loaded with its meshes, clouds a list of P (n_p,3) arrays of world points, q0 (P,J) the
@@ -615,36 +676,13 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
     names, kinds = list(table["names"]), np.asarray(table["type"])
     J, D = len(names), 6 + len(names)
     dev = _lib.device()
-    d_max, max_iter = float(d_max), int(max_iter)
-    if not d_max >= 0.0 or max_iter < 0 or not lam0 > 0.0:
-        raise ValueError(f"fit_cloud_poses: d_max >= 0, max_iter >= 0 and lam0 > 0 expected, got {d_max}, {max_iter}, {lam0}")
-    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    d_max, max_iter, parts, q, G = _fit_arguments("fit_cloud_poses", J, clouds, q0, base0, d_max, max_iter, lam0, dev)
     P = len(parts)
-    q = torch.as_tensor(np.array(q0, np.float64).reshape(-1, J) if not isinstance(q0, torch.Tensor) else q0, dtype=torch.float64, device=dev).clone()
-    if P < 1 or tuple(q.shape) != (P, J):
-        raise ValueError(f"fit_cloud_poses: {P} clouds need q0 ({P},{J}), got {tuple(q.shape)}")
-    G = torch.eye(4, dtype=torch.float64, device=dev) if base0 is None else torch.as_tensor(base0, dtype=torch.float64, device=dev)
-    if tuple(G.shape) not in ((4, 4), (P, 4, 4)):
-        raise ValueError(f"fit_cloud_poses: base0 must be (4,4) or ({P},4,4), got {tuple(G.shape)}")
-    G = G.expand(P, 4, 4).clone()
-    locked = set()
-    for item in lock:
-        if isinstance(item, str) and item not in names:
-            raise ValueError(f"fit_cloud_poses: no joint named {item!r} among {names}")
-        locked.add(names.index(item) if isinstance(item, str) else int(item))
+    locked = _joint_rows("fit_cloud_poses", names, lock)
     free0 = np.array([bool(fit_base)] * 6 + [kinds[j] in (1, 2) and j not in locked for j in range(J)])
     free0 = torch.as_tensor(free0, device=dev)
-    cut_host = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
-    pts = torch.as_tensor(np.concatenate(parts) if cut_host[-1] else np.zeros((0, 3)), device=dev)
-    cut = torch.as_tensor(cut_host, device=dev)
-    pose_of = torch.repeat_interleave(torch.arange(P, device=dev), cut[1:] - cut[:-1])
-    live = ~torch.isnan(pts).any(1)
-    n_live = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, pose_of, live.to(torch.float64))
-    center = torch.zeros(P, 3, dtype=torch.float64, device=dev).index_add_(0, pose_of, torch.where(live[:, None], pts, torch.zeros_like(pts)))
-    center = center / n_live.clamp_min(1.0)[:, None]
-    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
-    tri_start = torch.as_tensor(robot.tri_start, device=dev)
-    eye, dmax2 = np.eye(4), d_max * d_max
+    c = _pack_clouds(parts, robot, dev)
+    pts, cut, n_live, center, tri, tri_start, eye = c.pts, c.cut, c.n_live, c.center, c.tri, c.tri_start, np.eye(4)
     lam = torch.full((P,), float(lam0), dtype=torch.float64, device=dev)
     active = n_live > 0
     stepped = torch.zeros(P, dtype=torch.bool, device=dev)
@@ -655,10 +693,7 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
     history = []
     for it in range(max_iter + 1):
         link_T = (G[:, None] @ ops.urdf_fk(table, q, eye)).contiguous()
-        dist, tri_idx, _ = ops.point_mesh_distance(tri, tri_start, link_T, pts, cut, d_max)
-        d2 = torch.where(live, torch.clamp(dist * dist, max=dmax2), torch.zeros_like(dist))
-        cost = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, pose_of, d2)
-        within = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, pose_of, (live & torch.isfinite(dist)).to(torch.int64))
+        tri_idx, cost, within = _truncated_cost(c, tri, link_T, d_max)
         if it == 0:
             accept, cost_cur, n_cur = torch.ones(P, dtype=torch.bool, device=dev), cost, within
         else:
@@ -696,13 +731,10 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
     history = torch.stack(history).cpu().numpy()
     iters = iters.cpu().numpy()
     n_live = n_live.cpu().numpy()
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rms = lambda c: np.where(n_live > 0, np.sqrt(c / np.maximum(n_live, 1.0)), np.nan)
-        out = {"q": q.cpu().numpy(), "base": G.cpu().numpy(),
-               "cost_history": [history[:min(int(iters[p]), len(history) - 1) + 1, p].tolist() for p in range(P)],
-               "iterations": iters, "rms_before": rms(history[0]), "rms_after": rms(history[-1]),
-               "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names}
-    return out
+    return {"q": q.cpu().numpy(), "base": G.cpu().numpy(),
+            "cost_history": [history[:min(int(iters[p]), len(history) - 1) + 1, p].tolist() for p in range(P)],
+            "iterations": iters, "rms_before": _rms(n_live, history[0]), "rms_after": _rms(n_live, history[-1]),
+            "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names}
 
 
 def fit_positions(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf, max_iter=30):
@@ -851,43 +883,16 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     J, Dp, Ds = len(names), 6 + len(names), 4 * len(names)
     n_links = int(table["n_links"])
     dev, dt = _lib.device(), torch.float64
-    d_max, max_iter = float(d_max), int(max_iter)
-    if not d_max >= 0.0 or max_iter < 0 or not lam0 > 0.0:
-        raise ValueError(f"refine_joint_frames: d_max >= 0, max_iter >= 0 and lam0 > 0 expected, got {d_max}, {max_iter}, {lam0}")
-    parts = [np.asarray(c, np.float64).reshape(-1, 3) for c in clouds]
+    d_max, max_iter, parts, q, G = _fit_arguments("refine_joint_frames", J, clouds, q0, base0, d_max, max_iter, lam0, dev)
     P = len(parts)
-    q = torch.as_tensor(np.array(q0, np.float64).reshape(-1, J) if not isinstance(q0, torch.Tensor) else q0, dtype=dt, device=dev).clone()
-    if P < 1 or tuple(q.shape) != (P, J):
-        raise ValueError(f"refine_joint_frames: {P} clouds need q0 ({P},{J}), got {tuple(q.shape)}")
-    G = torch.eye(4, dtype=dt, device=dev) if base0 is None else torch.as_tensor(base0, dtype=dt, device=dev)
-    if tuple(G.shape) not in ((4, 4), (P, 4, 4)):
-        raise ValueError(f"refine_joint_frames: base0 must be (4,4) or ({P},4,4), got {tuple(G.shape)}")
-    G = G.expand(P, 4, 4).clone()
-
-    def rows(items, what):
-        out = set()
-        for item in items:
-            if isinstance(item, str) and item not in names:
-                raise ValueError(f"refine_joint_frames: no joint named {item!r} among {names} ({what})")
-            out.add(names.index(item) if isinstance(item, str) else int(item))
-        return out
-
-    locked, locked_f = rows(lock, "lock"), rows(lock_frames, "lock_frames")
+    locked, locked_f = (_joint_rows("refine_joint_frames", names, v, k) for k, v in (("lock", lock), ("lock_frames", lock_frames)))
     free_p0 = torch.as_tensor(np.array([bool(fit_base)] * 6 + [kinds[j] in (1, 2) and j not in locked for j in range(J)]), device=dev)
     free_s0 = torch.as_tensor(np.array([(kinds[j] == 1 or (kinds[j] == 2 and m < 2)) and j not in locked_f
                                         for j in range(J) for m in range(4)], bool).reshape(Ds), device=dev)
-    cut_host = np.concatenate([[0], np.cumsum([len(c) for c in parts])]).astype(np.int64)
-    pts = torch.as_tensor(np.concatenate(parts) if cut_host[-1] else np.zeros((0, 3)), device=dev)
-    cut = torch.as_tensor(cut_host, device=dev)
-    pose_of = torch.repeat_interleave(torch.arange(P, device=dev), cut[1:] - cut[:-1])
-    live = ~torch.isnan(pts).any(1)
-    n_live = torch.zeros(P, dtype=dt, device=dev).index_add_(0, pose_of, live.to(dt))
-    center = torch.zeros(P, 3, dtype=dt, device=dev).index_add_(0, pose_of, torch.where(live[:, None], pts, torch.zeros_like(pts)))
-    center = center / n_live.clamp_min(1.0)[:, None]
+    c = _pack_clouds(parts, robot, dev)
+    pts, cut, n_live, center, tri, tri_start = c.pts, c.cut, c.n_live, c.center, c.tri, c.tri_start
     ref = center[:, None, :].expand(P, n_links, 3).contiguous()
-    tri = torch.as_tensor(np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), device=dev)
     tri_start_host = np.asarray(robot.tri_start, np.int64)
-    tri_start = torch.as_tensor(tri_start_host, device=dev)
     # the tables of the update: which joint's step a joint's origin is pre-multiplied by, and which a triangle's; J = "none"
     child_joint = {int(c): j for j, c in enumerate(table["child"])}
     before = torch.as_tensor([child_joint.get(int(pa), J) for pa in table["parent"]], dtype=torch.int64, device=dev).reshape(J)
@@ -899,7 +904,7 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     u1, u2 = (torch.as_tensor(u, device=dev) for u in joint_frame_basis(table["axis"]))
     revolute = torch.as_tensor((kinds == 1).astype(np.float64), device=dev)[:, None]
     frames = torch.eye(4, dtype=dt, device=dev).expand(J, 4, 4).clone()
-    eye, eye_dev, dmax2 = np.eye(4), torch.eye(4, dtype=dt, device=dev), d_max * d_max
+    eye, eye_dev = np.eye(4), torch.eye(4, dtype=dt, device=dev)
     lam = float(lam0)
     active = bool((n_live > 0).any())
     stepped = small = False
@@ -911,10 +916,7 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     for it in range(max_iter + 1):
         tab = dict(table, _dev=fixed_tab + (origin.contiguous(), axis_dev))
         link_T = (G[:, None] @ ops.urdf_fk(tab, q, eye)).contiguous()
-        dist, tri_idx, _ = ops.point_mesh_distance(tri, tri_start, link_T, pts, cut, d_max)
-        d2 = torch.where(live, torch.clamp(dist * dist, max=dmax2), torch.zeros_like(dist))
-        cost = torch.zeros(P, dtype=dt, device=dev).index_add_(0, pose_of, d2)
-        within = torch.zeros(P, dtype=torch.int64, device=dev).index_add_(0, pose_of, (live & torch.isfinite(dist)).to(torch.int64))
+        tri_idx, cost, within = _truncated_cost(c, tri, link_T, d_max)
         total = float(cost.sum())
         if it == 0:
             accept, total_cur, cost_cur, n_cur, cost_first, link_T_cur = True, total, cost, within, cost, link_T
@@ -973,15 +975,13 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
         shifted = torch.einsum("fij,fvj->fvi", Ei[:, :3, :3], tri) + Ei[:, None, :3, 3]
         tri = torch.where(torch.cat([turned, torch.zeros(1, dtype=torch.bool, device=dev)])[tri_joint][:, None, None], shifted, tri).contiguous()
     n_live_h = n_live.cpu().numpy()
-    with np.errstate(invalid="ignore", divide="ignore"):
-        rms = lambda c: np.where(n_live_h > 0, np.sqrt(c.cpu().numpy() / np.maximum(n_live_h, 1.0)), np.nan)
-        rms_all = lambda c: float(np.sqrt(c / n_live_h.sum())) if n_live_h.sum() > 0 else float("nan")
-        out = {"q": q.cpu().numpy(), "base": G.cpu().numpy(), "cost_history": history, "iterations": iters,
-               "rms_before": rms(cost_first), "rms_after": rms(cost_cur), "rms_all_before": rms_all(history[0]),
-               "rms_all_after": rms_all(history[-1]), "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names,
-               "frames": frames.cpu().numpy(), "unobserved_frames": unobserved_s.reshape(J, 4).cpu().numpy(),
-               "origin": origin.cpu().numpy(), "tri": tri.cpu().numpy(), "link_T": link_T_cur.cpu().numpy()}
-    return out
+    rms_all = lambda total: float(np.sqrt(total / n_live_h.sum())) if n_live_h.sum() > 0 else float("nan")
+    return {"q": q.cpu().numpy(), "base": G.cpu().numpy(), "cost_history": history, "iterations": iters,
+            "rms_before": _rms(n_live_h, cost_first.cpu().numpy()), "rms_after": _rms(n_live_h, cost_cur.cpu().numpy()),
+            "rms_all_before": rms_all(history[0]), "rms_all_after": rms_all(history[-1]), "unobserved": unobserved.cpu().numpy(),
+            "n": n_cur.cpu().numpy(), "names": names, "frames": frames.cpu().numpy(),
+            "unobserved_frames": unobserved_s.reshape(J, 4).cpu().numpy(), "origin": origin.cpu().numpy(), "tri": tri.cpu().numpy(),
+            "link_T": link_T_cur.cpu().numpy()}
 
 
 def _xyz_rpy(T):

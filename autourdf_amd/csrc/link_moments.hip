@@ -3,45 +3,28 @@
 // pose, joint value, joint frame) is a twist field Omega x (c - rho) + V, so the normal system H, g, cost follows from
 //   sum d d^T (6) | sum d (3) | sum d x r (3) | sum r (3) | sum r.r (1),  d = c - ref[p, l],  and the count
 // whatever the parameter count is (compute_joints.twist_system assembles it in torch; compute_joints.refine_joint_frames is the
-// bundle adjustment on top).  The contract is in include/creg.h in full; contributes, r and c are word for word those of
-// creg_pose_fit_system_f64 (pose_fit.hip), so dot(r, r) has the bits of creg_point_mesh_f64's dist2.
+// bundle adjustment on top).  The contract is in include/creg.h in full; contributes, r and c are those of
+// creg_pose_fit_system_f64 by the same function (matched_row of point_rows.h), so dot(r, r) has the bits of creg_point_mesh_f64's dist2.
 //
 // Passes (LM_TILE = 64 points, LM_E = 17 entries: the 16 sums and the count as a double):
-//   k_link_moments_tiles   one launch, 256 threads, one block per (pose, tile of 64 of that pose's rows), found as k_pose_fit_tiles
-//                          finds its tile.  Wave 0 computes r, c, the link and the row's 17 terms into LDS ([row][17]: a row's terms
+//   k_link_moments_tiles   one launch, 256 threads, one block per (pose, tile of 64 of that pose's rows), found by find_tile of
+//                          point_rows.h.  Wave 0 computes r, c, the link and the row's 17 terms into LDS ([row][17]: a row's terms
 //                          are 136 bytes apart, and the readers below take consecutive entries of one row).  Then thread (l, e),
 //                          l over ALL links, sums entry e over the tile's rows 0 .. 63 in ascending order, skipping the rows of
 //                          other links, into the tile slot's partial [slot][l][e]: a link absent from the tile gets exact zeros, so
 //                          the finishing pass needs no list of present links.  4.4 KiB of LDS.
 //   k_link_moments_finish  thread per (pose, link, entry): the pose's tile partials in ascending tile order into four running sums
-//                          (tile t into sum t mod 4), result (s0 + s1) + (s2 + s3).  Adding the +0.0 of a tile without the link
+//                          (tile t into sum t mod 4), result (s0 + s1) + (s2 + s3): tile_sum4.  Adding the +0.0 of a tile without the link
 //                          changes no bit (a running sum starts from +0.0 and never becomes -0.0).
 // No atomics.  The order of every sum is a function of the pose's own row count and of which rows belong to the link: two runs give
 // the same bits, a pose alone in a call gives the bits it has among others, and the rows of other links do not enter.  fp64 VALU work;
 // no MFMA shape is hidden in 17 running sums.
-#include "mesh_dist.h"
+#include "point_rows.h"
 
 namespace creg {
 
-constexpr int LM_TILE = 64;
-constexpr int LM_TILE_SHIFT = 6;
+constexpr int LM_SHIFT = 6, LM_TILE = 1 << LM_SHIFT;
 constexpr int LM_E = 17;
-
-__device__ __forceinline__ void lm_pose_rows(const int64_t* __restrict__ pt_start, int64_t p, int64_t N, int64_t& s, int64_t& e) {
-    s = pt_start[p];
-    e = pt_start[p + 1];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < s ? s : (e > N ? N : e);
-}
-__device__ __forceinline__ int64_t lm_tile_slot(const int64_t* __restrict__ pt_start, int64_t p, int64_t N) {
-    int64_t s = pt_start[p];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    return (s >> LM_TILE_SHIFT) + p;
-}
-__device__ __forceinline__ int64_t lm_clamped_start(const int64_t* __restrict__ tri_start, int l, int64_t F) {
-    const int64_t s = tri_start[l];
-    return s < 0 ? 0 : (s > F ? F : s);
-}
 
 __global__ __launch_bounds__(256) void k_link_moments_tiles(const double* __restrict__ tri, const int64_t* __restrict__ tri_start, int64_t F,
                                                             const double* __restrict__ link_T, int L, const double* __restrict__ pts,
@@ -52,16 +35,8 @@ __global__ __launch_bounds__(256) void k_link_moments_tiles(const double* __rest
     __shared__ int s_link[LM_TILE];                              // the row's link, -1 where it does not contribute
     const int tid = threadIdx.x;
     const int64_t blk = blockIdx.x;
-    if (lm_tile_slot(pt_start, 0, N) > blk) return;
-    int64_t p = 0, hi = P;
-    while (hi - p > 1) {
-        const int64_t mid = p + ((hi - p) >> 1);
-        if (lm_tile_slot(pt_start, mid, N) <= blk) p = mid; else hi = mid;
-    }
-    int64_t ps, pe;
-    lm_pose_rows(pt_start, p, N, ps, pe);
-    const int64_t tile = blk - lm_tile_slot(pt_start, p, N);
-    if (tile >= (pe - ps + LM_TILE - 1) / LM_TILE) return;       // the same for every thread
+    int64_t p, ps, pe, tile;                                     // the same for every thread
+    if (!find_tile<LM_SHIFT>(pt_start, N, P, blk, p, ps, pe, tile)) return;
     if (tid < LM_TILE) {
         const int64_t i = ps + tile * LM_TILE + tid;
         int link = -1;
@@ -72,46 +47,22 @@ __global__ __launch_bounds__(256) void k_link_moments_tiles(const double* __rest
             double x[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) x[k] = pts[(size_t)i * 3 + k];
-            const bool live = x[0] == x[0] && x[1] == x[1] && x[2] == x[2];
-            const int64_t f = tri_idx[i];
-            if (live && f >= 0 && f < F) {
-                int lo = 0, up = L;                              // the largest l whose clamped start is not above f
-                while (up - lo > 1) {
-                    const int mid = lo + ((up - lo) >> 1);
-                    if (lm_clamped_start(tri_start, mid, F) <= f) lo = mid; else up = mid;
-                }
-                int64_t sl, el;
-                link_rows(tri_start, lo, F, sl, el);
-                if (f >= sl && f < el) {
-                    const double* T = link_T + ((size_t)p * L + lo) * 16;
-                    double v[9], w[9], r[3];
+            matched_row(tri, tri_start, F, link_T, L, p, x, tri_idx[i], dmax2, [&](int l, const double* r, double rr) {
+                link = l;
+                const double* rf = ref + ((size_t)p * L + l) * 3;
+                double d[3];
 #pragma unroll
-                    for (int k = 0; k < 9; ++k) v[k] = tri[(size_t)f * 9 + k];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j)
-#pragma unroll
-                        for (int a = 0; a < 3; ++a)
-                            w[3 * j + a] = ((T[4 * a] * v[3 * j] + T[4 * a + 1] * v[3 * j + 1]) + T[4 * a + 2] * v[3 * j + 2]) + T[4 * a + 3];
-                    pt_tri_vec(x, w, w + 3, w + 6, r);
-                    const double rr = dot3(r, r);
-                    if (rr <= dmax2) {
-                        link = lo;
-                        const double* rf = ref + ((size_t)p * L + lo) * 3;
-                        double d[3];
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) d[k] = (x[k] - r[k]) - rf[k];
-                        t[0] = d[0] * d[0]; t[1] = d[0] * d[1]; t[2] = d[0] * d[2];
-                        t[3] = d[1] * d[1]; t[4] = d[1] * d[2]; t[5] = d[2] * d[2];
-                        t[6] = d[0]; t[7] = d[1]; t[8] = d[2];
-                        t[9] = d[1] * r[2] - d[2] * r[1];
-                        t[10] = d[2] * r[0] - d[0] * r[2];
-                        t[11] = d[0] * r[1] - d[1] * r[0];
-                        t[12] = r[0]; t[13] = r[1]; t[14] = r[2];
-                        t[15] = rr;
-                        t[16] = 1.0;
-                    }
-                }
-            }
+                for (int k = 0; k < 3; ++k) d[k] = (x[k] - r[k]) - rf[k];
+                t[0] = d[0] * d[0]; t[1] = d[0] * d[1]; t[2] = d[0] * d[2];
+                t[3] = d[1] * d[1]; t[4] = d[1] * d[2]; t[5] = d[2] * d[2];
+                t[6] = d[0]; t[7] = d[1]; t[8] = d[2];
+                t[9] = d[1] * r[2] - d[2] * r[1];
+                t[10] = d[2] * r[0] - d[0] * r[2];
+                t[11] = d[0] * r[1] - d[1] * r[0];
+                t[12] = r[0]; t[13] = r[1]; t[14] = r[2];
+                t[15] = rr;
+                t[16] = 1.0;
+            });
         }
 #pragma unroll
         for (int k = 0; k < LM_E; ++k) s_term[tid * LM_E + k] = t[k];
@@ -140,31 +91,19 @@ __global__ __launch_bounds__(256) void k_link_moments_finish(const int64_t* __re
     const int64_t l = le / LM_E;
     const int e = (int)(le - l * LM_E);
     int64_t ps, pe;
-    lm_pose_rows(pt_start, p, N, ps, pe);
+    pose_rows(pt_start, p, N, ps, pe);
     const int64_t tiles = (pe - ps + LM_TILE - 1) / LM_TILE;
     const size_t E = (size_t)per_pose;
-    const double* src = part + (size_t)lm_tile_slot(pt_start, p, N) * E + le;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int64_t t = 0;
-    for (; t + 4 <= tiles; t += 4) {
-        s0 += src[(size_t)t * E];
-        s1 += src[(size_t)(t + 1) * E];
-        s2 += src[(size_t)(t + 2) * E];
-        s3 += src[(size_t)(t + 3) * E];
-    }
-    if (t < tiles) s0 += src[(size_t)t * E];
-    if (t + 1 < tiles) s1 += src[(size_t)(t + 1) * E];
-    if (t + 2 < tiles) s2 += src[(size_t)(t + 2) * E];
-    const double v = (s0 + s1) + (s2 + s3);
+    const double v = tile_sum4(part + (size_t)tile_slot<LM_SHIFT>(pt_start, p, N) * E + le, E, tiles);
     if (e < 16) mom[((size_t)p * L + l) * 16 + e] = v;
     else cnt[(size_t)p * L + l] = (int64_t)v;
 }
 
 static inline bool link_moments_counts_ok(int64_t n_poses, int64_t n_pts, int32_t n_links) {
     return n_poses >= 1 && n_pts >= 0 && n_pts < (1ll << 31) && n_links >= 1 && n_links <= 65535 &&
-           (n_pts >> LM_TILE_SHIFT) + n_poses < (1ll << 31);
+           (n_pts >> LM_SHIFT) + n_poses < (1ll << 31);
 }
-static inline int64_t link_moments_blocks(int64_t n_poses, int64_t n_pts) { return (n_pts >> LM_TILE_SHIFT) + n_poses; }   // past the last slot in use
+static inline int64_t link_moments_blocks(int64_t n_poses, int64_t n_pts) { return (n_pts >> LM_SHIFT) + n_poses; }   // past the last slot in use
 static inline size_t link_moments_bytes(int64_t n_poses, int64_t n_pts, int32_t n_links) {
     return align_up(sizeof(double) * (size_t)link_moments_blocks(n_poses, n_pts) * (size_t)n_links * LM_E, 256);
 }
@@ -182,17 +121,14 @@ extern "C" int creg_link_moments_f64(const double* tri, const int64_t* tri_start
                                      const int32_t* tri_idx, const double* ref, double* mom, int64_t* cnt, void* workspace,
                                      size_t workspace_bytes, creg_stream_t stream) {
     const char* who = "creg_link_moments_f64";
-    CREG_REQUIRE(d_max >= 0.0, "%s: d_max must be >= 0 (+inf allowed), got %g", who, d_max);                    // NaN fails too
-    CREG_REQUIRE(n_pts >= 0 && n_pts < (1ll << 31), "%s: 0 <= n_pts < 2^31 (got %lld)", who, (long long)n_pts);
-    CREG_REQUIRE(n_poses >= 1 && (n_pts >> LM_TILE_SHIFT) + n_poses < (1ll << 31), "%s: n_poses >= 1 and (n_pts >> 6) + n_poses < 2^31 (got %lld)",
-                 who, (long long)n_poses);
+    if (const int rc = point_query_check(who, d_max, n_pts, n_poses, LM_SHIFT, pt_start, ref && mom && cnt, "ref, mom or cnt",
+                                         pts && tri_idx, "pts / tri_idx"))
+        return rc;
     CREG_REQUIRE(n_links >= 1 && n_links <= 65535, "%s: 1 <= n_links <= 65535 (got %d)", who, (int)n_links);
     const size_t need = link_moments_bytes(n_poses, n_pts, n_links);
     if (const int rc = mesh_pair_check(who, tri, tri_start, n_tri, link_T, n_links, n_poses, nullptr, 0, nullptr, nullptr,
                                        "tri_idx", workspace, workspace_bytes, need))
         return rc;
-    CREG_REQUIRE(pt_start && ref && mom && cnt, "%s: null pt_start, ref, mom or cnt", who);
-    CREG_REQUIRE(n_pts == 0 || (pts && tri_idx), "%s: null pts / tri_idx with n_pts %lld", who, (long long)n_pts);
     const int64_t finish_blocks = (n_poses * (int64_t)n_links * LM_E + 255) / 256;
     CREG_REQUIRE(finish_blocks < (1ll << 31), "%s: too many (pose, link) pairs (%lld x %d)", who, (long long)n_poses, (int)n_links);
     hipStream_t s = (hipStream_t)stream;

@@ -1,8 +1,9 @@
 // mesh_pair.h -- what the mesh pair queries share: collide.hip (do two posed link meshes intersect), clearance.hip (how far apart
 // are they) and contain.hip (is one wholly inside the other).
 //   posing stage   mesh_pose.hip: the workspace prefix posed | chunk_box | link_box (pose_layout), the argument checks of the three
-//                  entries (mesh_pair_check) and the pose and link-box passes of one pose slice (mesh_pose_launch)
-//   device helpers boxes, the link's rows, the chunk-box slots, the block compaction and the piercing predicate, for the pair kernels
+//                  entries (mesh_pair_check) and the pose and link-box passes of one pose slice (mesh_pose_launch); the point
+//                  queries (point_mesh.hip, pose_fit.hip, link_moments.hip) add their own checks (point_query_check)
+//   device helpers boxes, the link's rows, the vertex formula (pose_tri), the chunk-box slots, the block compaction and the piercing predicate, for the pair kernels
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -76,6 +77,14 @@ __device__ __forceinline__ void link_rows(const int64_t* __restrict__ tri_start,
     s = s < 0 ? 0 : (s > F ? F : s);
     e = e < s ? s : (e > F ? F : e);
 }
+// the posed triangle w (9 doubles, vertex-major) of the link-frame triangle v under the row-major 4x4 T: the one vertex formula
+__device__ __forceinline__ void pose_tri(const double* T, const double* v, double* w) {
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+            w[3 * j + a] = ((T[4 * a] * v[3 * j] + T[4 * a + 1] * v[3 * j + 1]) + T[4 * a + 2] * v[3 * j + 2]) + T[4 * a + 3];
+}
 // the chunk boxes of link l start at this slot: distinct links never share one (floor(s / 256) + l is strictly increasing by at
 // least the link's chunk count), and the last slot in use is below floor(F / 256) + L + 1
 __device__ __forceinline__ int64_t chunk_slot(int64_t s, int l) { return (s >> 8) + l; }
@@ -100,6 +109,11 @@ static inline bool mesh_pair_counts_ok(int64_t n_tri, int32_t n_links, int64_t n
 int mesh_pair_check(const char* who, const void* tri, const void* tri_start, int64_t n_tri, const void* link_T, int32_t n_links,
                     int64_t n_poses, const void* pairs, int64_t n_pairs, const void* out_a, const void* out_b, const char* outs,
                     const void* workspace, size_t workspace_bytes, size_t need);
+// the point queries' own checks (tiles of 1 << shift rows), before mesh_pair_check: d_max >= 0, 0 <= n_pts < 2^31, (n_pts >> shift)
+// + n_poses < 2^31, pt_start and `rest` (the entry's other pointers, named in rest_names), `per_point` (its arrays of n_pts rows)
+// unless n_pts is 0.  creg_point_mesh_f64 passes no rest_names: n_poses >= 1 is mesh_pair_check's there, one message for its nulls.
+int point_query_check(const char* who, double d_max, int64_t n_pts, int64_t n_poses, int shift, const void* pt_start, bool rest,
+                      const char* rest_names, bool per_point, const char* per_point_names);
 // k_collide_pose and k_collide_boxes for the poses [p0, p0 + np), np <= 65535; link_box_out may be null
 int mesh_pose_launch(hipStream_t s, const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
                      int64_t p0, unsigned np, const PoseLayout& w, void* workspace, double* link_box_out);

@@ -1,5 +1,5 @@
 // mesh_pose.hip -- the posing stage of the mesh pair queries (collide.hip, clearance.hip, contain.hip; mesh_pair.h declares it): the
-// argument checks the three entries share, and the two passes that fill the workspace prefix posed | chunk_box | link_box with
+// argument checks the three entries share, those the three point queries add, and the two passes that fill the workspace prefix posed | chunk_box | link_box with
 // w_i = ((R_i0 v_0 + R_i1 v_1) + R_i2 v_2) + t_i and the exact min / max boxes of it per 256-triangle chunk and per link.
 #include "mesh_pair.h"
 
@@ -25,11 +25,7 @@ __global__ __launch_bounds__(256) void k_collide_pose(const double* __restrict__
             double v[9], w[9];
 #pragma unroll
             for (int k = 0; k < 9; ++k) v[k] = tri[(size_t)f * 9 + k];
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    w[3 * j + i] = ((T[4 * i] * v[3 * j] + T[4 * i + 1] * v[3 * j + 1]) + T[4 * i + 2] * v[3 * j + 2]) + T[4 * i + 3];
+            pose_tri(T, v, w);
             double* dst = posed + ((size_t)p * F + f) * 9;
 #pragma unroll
             for (int k = 0; k < 9; ++k) dst[k] = w[k];
@@ -82,6 +78,24 @@ int mesh_pair_check(const char* who, const void* tri, const void* tri_start, int
     CREG_REQUIRE(tri_start && link_T && workspace && (tri || n_tri == 0), "%s: null pointer", who);
     CREG_REQUIRE(n_pairs == 0 || (pairs && out_a && out_b), "%s: null pairs / %s with n_pairs %lld", who, outs, (long long)n_pairs);
     CREG_REQUIRE(workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    return CREG_OK;
+}
+
+int point_query_check(const char* who, double d_max, int64_t n_pts, int64_t n_poses, int shift, const void* pt_start, bool rest,
+                      const char* rest_names, bool per_point, const char* per_point_names) {
+    CREG_REQUIRE(d_max >= 0.0, "%s: d_max must be >= 0 (+inf allowed), got %g", who, d_max);                    // NaN fails too
+    CREG_REQUIRE(n_pts >= 0 && n_pts < (1ll << 31), "%s: 0 <= n_pts < 2^31 (got %lld)", who, (long long)n_pts);
+    const int64_t slots = (n_pts >> shift) + n_poses;              // past the last tile slot in use
+    if (!rest_names) {
+        CREG_REQUIRE(slots < (1ll << 31), "%s: (n_pts >> %d) + n_poses < 2^31 (got %lld)", who, shift, (long long)slots);
+        CREG_REQUIRE(pt_start && (n_pts == 0 || per_point), "%s: null pt_start, or null %s with n_pts %lld", who, per_point_names,
+                     (long long)n_pts);
+        return CREG_OK;
+    }
+    CREG_REQUIRE(n_poses >= 1 && slots < (1ll << 31), "%s: n_poses >= 1 and (n_pts >> %d) + n_poses < 2^31 (got %lld)", who, shift,
+                 (long long)n_poses);
+    CREG_REQUIRE(pt_start && rest, "%s: null pt_start, %s", who, rest_names);
+    CREG_REQUIRE(n_pts == 0 || per_point, "%s: null %s with n_pts %lld", who, per_point_names, (long long)n_pts);
     return CREG_OK;
 }
 

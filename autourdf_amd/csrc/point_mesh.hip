@@ -15,8 +15,8 @@
 // Passes (CHUNK = 256 triangles, tile = PM_TILE = 64 points):
 //   posing stage     mesh_pose.hip, every pose slice: posed vertices (P,F,9), chunk boxes and link boxes into the workspace
 //   k_point_mesh     one launch, 256 threads, one block per (pose, tile of that pose's points): block b belongs to the pose p with
-//                    the largest tile_slot(p) = (pt_start[p] >> 6) + p not above b (found by bisection; the slots of distinct poses
-//                    never overlap, as chunk_slot's), and to tile b - tile_slot(p) of it.  Lane l of each of the four waves holds
+//                    the largest tile_slot(p) = (pt_start[p] >> 6) + p not above b (find_tile of point_rows.h, by bisection; the slots
+//                    of distinct poses never overlap, as chunk_slot's), and to tile b - tile_slot(p) of it.  Lane l of each of the four waves holds
 //                    point l of the tile and that wave's running (d2, idx) in registers.  The block forms the union box of its live
 //                    points, walks the links and their chunks, skips those beyond d_max of the union box, ballot-compacts the
 //                    surviving chunk's triangles within d_max of the union box into LDS as SoA (stable, so rows stay ascending), and
@@ -27,25 +27,11 @@
 //                    still fetched and tested by 256 threads.
 // No atomics.  A point's result is a function of its coordinates and its pose's mesh alone: not of the other points or poses of the
 // call, their order, or scheduling.  fp64 VALU work throughout; nothing here has the shape of a matrix product.
-#include "mesh_dist.h"
+#include "point_rows.h"
 
 namespace creg {
 
-constexpr int PM_TILE = 64;                                      // points per block: one per lane, the four waves split the triangles
-constexpr int PM_TILE_SHIFT = 6;
-
-// rows [s, e) of pose p, clamped into [0, N] as link_rows clamps tri_start
-__device__ __forceinline__ void pose_rows(const int64_t* __restrict__ pt_start, int64_t p, int64_t N, int64_t& s, int64_t& e) {
-    s = pt_start[p];
-    e = pt_start[p + 1];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < s ? s : (e > N ? N : e);
-}
-__device__ __forceinline__ int64_t tile_slot(const int64_t* __restrict__ pt_start, int64_t p, int64_t N) {
-    int64_t s = pt_start[p];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    return (s >> PM_TILE_SHIFT) + p;
-}
+constexpr int PM_SHIFT = 6, PM_TILE = 1 << PM_SHIFT;             // points per block: one per lane, the four waves split the triangles
 
 __global__ __launch_bounds__(256) void k_point_mesh(const int64_t* __restrict__ tri_start, int64_t F, int L,
                                                     const double* __restrict__ pts, const int64_t* __restrict__ pt_start, int64_t N,
@@ -59,18 +45,8 @@ __global__ __launch_bounds__(256) void k_point_mesh(const int64_t* __restrict__ 
     __shared__ double s_bd[4][PM_TILE];                          // the four waves' results, merged at the end
     __shared__ int s_bi[4][PM_TILE];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t blk = blockIdx.x;
-    // ---- the pose this block belongs to: the largest p with tile_slot(p) <= blk (the same for every thread)
-    if (tile_slot(pt_start, 0, N) > blk) return;
-    int64_t p = 0, hi = P;                                       // tile_slot(p) <= blk < tile_slot(hi), with tile_slot(P) = +inf
-    while (hi - p > 1) {
-        const int64_t mid = p + ((hi - p) >> 1);
-        if (tile_slot(pt_start, mid, N) <= blk) p = mid; else hi = mid;
-    }
-    int64_t ps, pe;
-    pose_rows(pt_start, p, N, ps, pe);
-    const int64_t tile = blk - tile_slot(pt_start, p, N);
-    if (tile >= (pe - ps + PM_TILE - 1) / PM_TILE) return;
+    int64_t p, ps, pe, tile;                                     // the same for every thread
+    if (!find_tile<PM_SHIFT>(pt_start, N, P, blockIdx.x, p, ps, pe, tile)) return;
     // ---- this lane's point (the same in all four waves)
     const int64_t i = ps + tile * PM_TILE + lane;
     const bool has = i < pe;
@@ -174,16 +150,14 @@ extern "C" int creg_point_mesh_f64(const double* tri, const int64_t* tri_start, 
                                    double* dist2, int32_t* tri_idx, double* link_box, void* workspace, size_t workspace_bytes,
                                    creg_stream_t stream) {
     const char* who = "creg_point_mesh_f64";
-    CREG_REQUIRE(d_max >= 0.0, "%s: d_max must be >= 0 (+inf allowed), got %g", who, d_max);                    // NaN fails too
-    CREG_REQUIRE(n_pts >= 0 && n_pts < (1ll << 31), "%s: 0 <= n_pts < 2^31 (got %lld)", who, (long long)n_pts);
+    if (const int rc = point_query_check(who, d_max, n_pts, n_poses, PM_SHIFT, pt_start, true, nullptr, pts && dist2 && tri_idx,
+                                         "pts / dist2 / tri_idx"))
+        return rc;
     const PoseLayout w = pose_layout(n_tri, n_links, n_poses);
     if (const int rc = mesh_pair_check(who, tri, tri_start, n_tri, link_T, n_links, n_poses, nullptr, 0, nullptr, nullptr,
                                        "dist2 / tri_idx", workspace, workspace_bytes, w.end))
         return rc;
-    CREG_REQUIRE(pt_start && (n_pts == 0 || (pts && dist2 && tri_idx)), "%s: null pt_start, or null pts / dist2 / tri_idx with n_pts %lld",
-                 who, (long long)n_pts);
-    const int64_t blocks = (n_pts >> PM_TILE_SHIFT) + n_poses;     // past the last tile slot in use
-    CREG_REQUIRE(blocks < (1ll << 31), "%s: (n_pts >> 6) + n_poses < 2^31 (got %lld)", who, (long long)blocks);
+    const int64_t blocks = (n_pts >> PM_SHIFT) + n_poses;          // past the last tile slot in use
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     for (int64_t p0 = 0; p0 < n_poses; p0 += 65535) {              // gridDim.y / .z hold at most 65535

@@ -5,14 +5,15 @@
 // system on the device.  The contract is in include/creg.h in full; in short
 //   frames      per pose, once: W_j = link_T[p, parent[j]] * origin[j] (affine 3x4), o_j = W_j[:3,3], a_j = W_j[:3,:3] axis[j]
 //   point i     contributes iff live, 0 <= f = tri_idx[i] < n_tri, row f in a link l's rows, dot(r, r) <= d_max^2, where r is
-//               pt_tri_vec of mesh_dist.h against the row's three vertices posed in the thread (the vertex formula of mesh-collide, so
-//               dot(r, r) has the bits of creg_point_mesh_f64's dist2); c = p_i - r
+//               pt_tri_vec of mesh_dist.h against the row's three vertices posed in the thread by pose_tri of mesh_pair.h, the
+//               posing stage's formula, so dot(r, r) has the bits of creg_point_mesh_f64's dist2 (matched_row of point_rows.h,
+//               which link_moments.hip calls too); c = p_i - r
 //   columns     e_k x (c - center_p) | e_k | a_j x (c - o_j) (revolute) or a_j (prismatic) where bit j of chain[l] is set, else 0
 //
 // Passes (PF_TILE = 32 points):
 //   k_pose_fit_frames   one thread per (pose, joint): o_j | a_j into the workspace
-//   k_pose_fit_tiles    one launch, 256 threads, one block per (pose, tile of 32 of that pose's points), found as k_point_mesh finds
-//                       its tile: block b belongs to the pose p with the largest (pt_start[p] >> 5) + p not above b.  Lanes 0 .. 31
+//   k_pose_fit_tiles    one launch, 256 threads, one block per (pose, tile of 32 of that pose's points), found by find_tile of
+//                       point_rows.h: block b belongs to the pose p with the largest (pt_start[p] >> 5) + p not above b.  Lanes 0 .. 31
 //                       compute r, c and the link of the tile's points while the other threads fetch the pose's frames into LDS; then
 //                       all 256 threads fill the tile's 32 x D x 3 Jacobian in LDS ([point][column][xyz]: consecutive lanes write
 //                       consecutive columns, 24 bytes apart, no bank conflict), and thread e, e + 256, ... sums entry e of H | g | cost
@@ -21,34 +22,17 @@
 //                       does not contribute, and a row past the pose's end, has r = 0 and J = 0: its terms are exact zeros.  H's
 //                       upper triangle is summed and stored to both halves.
 //   k_pose_fit_finish   thread per (pose, entry): the pose's tile partials in ascending tile order into four running sums (tile t
-//                       into sum t mod 4), result (s0 + s1) + (s2 + s3).
+//                       into sum t mod 4), result (s0 + s1) + (s2 + s3): tile_sum4 of point_rows.h.
 // No atomics.  The order of every sum is a function of the pose's own row count alone: two runs give the same bits, and a pose alone in
 // a call gives the bits it has among others.  fp64 VALU work with partials in LDS and in the workspace; the Jacobian of a tile is
 // 3 x D x 32 doubles, 48 KiB at D = 64 (dynamic LDS, 52.6 KiB in all at D = 64, 8.6 KiB at the toy robot's D = 10).  Nothing here has
 // the shape of an MFMA product worth forcing: K = 32 x 3 per tile against D x D outputs that are reduced again across tiles.
-#include "mesh_dist.h"
+#include "point_rows.h"
 
 namespace creg {
 
-constexpr int PF_TILE = 32;
-constexpr int PF_TILE_SHIFT = 5;
+constexpr int PF_SHIFT = 5, PF_TILE = 1 << PF_SHIFT;
 constexpr int PF_MAX_D = 64;
-
-__device__ __forceinline__ void pf_pose_rows(const int64_t* __restrict__ pt_start, int64_t p, int64_t N, int64_t& s, int64_t& e) {
-    s = pt_start[p];
-    e = pt_start[p + 1];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    e = e < s ? s : (e > N ? N : e);
-}
-__device__ __forceinline__ int64_t pf_tile_slot(const int64_t* __restrict__ pt_start, int64_t p, int64_t N) {
-    int64_t s = pt_start[p];
-    s = s < 0 ? 0 : (s > N ? N : s);
-    return (s >> PF_TILE_SHIFT) + p;
-}
-__device__ __forceinline__ int64_t pf_clamped_start(const int64_t* __restrict__ tri_start, int l, int64_t F) {
-    const int64_t s = tri_start[l];
-    return s < 0 ? 0 : (s > F ? F : s);
-}
 
 __global__ __launch_bounds__(64) void k_pose_fit_frames(const double* __restrict__ link_T, int L, int64_t P, const int* __restrict__ parent,
                                                         const int* __restrict__ child, const double* __restrict__ origin,
@@ -100,16 +84,8 @@ __global__ __launch_bounds__(256) void k_pose_fit_tiles(const double* __restrict
     int* s_type = s_link + PF_TILE;                              // [J]
     const int tid = threadIdx.x;
     const int64_t blk = blockIdx.x;
-    if (pf_tile_slot(pt_start, 0, N) > blk) return;
-    int64_t p = 0, hi = P;
-    while (hi - p > 1) {
-        const int64_t mid = p + ((hi - p) >> 1);
-        if (pf_tile_slot(pt_start, mid, N) <= blk) p = mid; else hi = mid;
-    }
-    int64_t ps, pe;
-    pf_pose_rows(pt_start, p, N, ps, pe);
-    const int64_t tile = blk - pf_tile_slot(pt_start, p, N);
-    if (tile >= (pe - ps + PF_TILE - 1) / PF_TILE) return;       // the same for every thread
+    int64_t p, ps, pe, tile;                                     // the same for every thread
+    if (!find_tile<PF_SHIFT>(pt_start, N, P, blk, p, ps, pe, tile)) return;
     if (tid < PF_TILE) {
         const int64_t i = ps + tile * PF_TILE + tid;
         double r[3] = {0.0, 0.0, 0.0}, c[3] = {0.0, 0.0, 0.0};
@@ -118,34 +94,11 @@ __global__ __launch_bounds__(256) void k_pose_fit_tiles(const double* __restrict
             double x[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) x[k] = pts[(size_t)i * 3 + k];
-            const bool live = x[0] == x[0] && x[1] == x[1] && x[2] == x[2];
-            const int64_t f = tri_idx[i];
-            if (live && f >= 0 && f < F) {
-                int lo = 0, up = L;                              // the largest l whose clamped start is not above f
-                while (up - lo > 1) {
-                    const int mid = lo + ((up - lo) >> 1);
-                    if (pf_clamped_start(tri_start, mid, F) <= f) lo = mid; else up = mid;
-                }
-                int64_t sl, el;
-                link_rows(tri_start, lo, F, sl, el);
-                if (f >= sl && f < el) {
-                    const double* T = link_T + ((size_t)p * L + lo) * 16;
-                    double v[9], w[9], rr[3];
+            matched_row(tri, tri_start, F, link_T, L, p, x, tri_idx[i], dmax2, [&](int l, const double* rr, double) {
+                link = l;
 #pragma unroll
-                    for (int k = 0; k < 9; ++k) v[k] = tri[(size_t)f * 9 + k];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j)
-#pragma unroll
-                        for (int a = 0; a < 3; ++a)
-                            w[3 * j + a] = ((T[4 * a] * v[3 * j] + T[4 * a + 1] * v[3 * j + 1]) + T[4 * a + 2] * v[3 * j + 2]) + T[4 * a + 3];
-                    pt_tri_vec(x, w, w + 3, w + 6, rr);
-                    if (dot3(rr, rr) <= dmax2) {
-                        link = lo;
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) { r[k] = rr[k]; c[k] = x[k] - rr[k]; }
-                    }
-                }
-            }
+                for (int k = 0; k < 3; ++k) { r[k] = rr[k]; c[k] = x[k] - rr[k]; }
+            });
         }
 #pragma unroll
         for (int k = 0; k < 3; ++k) { s_r[tid * 3 + k] = r[k]; s_c[tid * 3 + k] = c[k]; }
@@ -222,21 +175,9 @@ __global__ __launch_bounds__(256) void k_pose_fit_finish(const int64_t* __restri
     const int e = (int)(blockIdx.x % chunks) * 256 + threadIdx.x;
     if (e >= E) return;
     int64_t ps, pe;
-    pf_pose_rows(pt_start, p, N, ps, pe);
+    pose_rows(pt_start, p, N, ps, pe);
     const int64_t tiles = (pe - ps + PF_TILE - 1) / PF_TILE;
-    const double* src = part + (size_t)pf_tile_slot(pt_start, p, N) * E + e;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int64_t t = 0;
-    for (; t + 4 <= tiles; t += 4) {
-        s0 += src[(size_t)t * E];
-        s1 += src[(size_t)(t + 1) * E];
-        s2 += src[(size_t)(t + 2) * E];
-        s3 += src[(size_t)(t + 3) * E];
-    }
-    if (t < tiles) s0 += src[(size_t)t * E];
-    if (t + 1 < tiles) s1 += src[(size_t)(t + 1) * E];
-    if (t + 2 < tiles) s2 += src[(size_t)(t + 2) * E];
-    const double v = (s0 + s1) + (s2 + s3);
+    const double v = tile_sum4(part + (size_t)tile_slot<PF_SHIFT>(pt_start, p, N) * E + e, E, tiles);
     if (e < DD) H[(size_t)p * DD + e] = v;
     else if (e < DD + D) g[(size_t)p * D + (e - DD)] = v;
     else if (e == DD + D) cost[p] = v;
@@ -246,13 +187,13 @@ __global__ __launch_bounds__(256) void k_pose_fit_finish(const int64_t* __restri
 struct PoseFitLayout { size_t frames, part, end; int64_t blocks; int E; };
 static inline bool pose_fit_counts_ok(int64_t n_poses, int64_t n_pts, int32_t n_joints) {
     return n_poses >= 1 && n_pts >= 0 && n_pts < (1ll << 31) && n_joints >= 0 && 6 + n_joints <= PF_MAX_D &&
-           (n_pts >> PF_TILE_SHIFT) + n_poses < (1ll << 31);
+           (n_pts >> PF_SHIFT) + n_poses < (1ll << 31);
 }
 static inline PoseFitLayout pose_fit_layout(int64_t n_poses, int64_t n_pts, int32_t n_joints) {
     PoseFitLayout w;
     const int D = 6 + n_joints;
     w.E = D * D + D + 2;
-    w.blocks = (n_pts >> PF_TILE_SHIFT) + n_poses;               // past the last tile slot in use
+    w.blocks = (n_pts >> PF_SHIFT) + n_poses;               // past the last tile slot in use
     w.frames = 0;
     w.part = align_up(w.frames + sizeof(double) * 6 * (size_t)n_poses * (size_t)n_joints, 256);
     w.end = align_up(w.part + sizeof(double) * (size_t)w.blocks * (size_t)w.E, 256);
@@ -274,18 +215,15 @@ extern "C" int creg_pose_fit_system_f64(const double* tri, const int64_t* tri_st
                                         const double* center, double* H, double* g, double* cost, int64_t* n, void* workspace,
                                         size_t workspace_bytes, creg_stream_t stream) {
     const char* who = "creg_pose_fit_system_f64";
-    CREG_REQUIRE(d_max >= 0.0, "%s: d_max must be >= 0 (+inf allowed), got %g", who, d_max);                    // NaN fails too
-    CREG_REQUIRE(n_pts >= 0 && n_pts < (1ll << 31), "%s: 0 <= n_pts < 2^31 (got %lld)", who, (long long)n_pts);
+    if (const int rc = point_query_check(who, d_max, n_pts, n_poses, PF_SHIFT, pt_start, chain && center && H && g && cost && n,
+                                         "chain, center, H, g, cost or n", pts && tri_idx, "pts / tri_idx"))
+        return rc;
     CREG_REQUIRE(n_joints >= 0 && 6 + n_joints <= PF_MAX_D, "%s: 0 <= n_joints and D = 6 + n_joints <= %d (got n_joints %d)", who,
                  PF_MAX_D, (int)n_joints);
-    CREG_REQUIRE(n_poses >= 1 && (n_pts >> PF_TILE_SHIFT) + n_poses < (1ll << 31), "%s: n_poses >= 1 and (n_pts >> 5) + n_poses < 2^31 (got %lld)",
-                 who, (long long)n_poses);
     const PoseFitLayout w = pose_fit_layout(n_poses, n_pts, n_joints);
     if (const int rc = mesh_pair_check(who, tri, tri_start, n_tri, link_T, n_links, n_poses, nullptr, 0, nullptr, nullptr,
                                        "tri_idx", workspace, workspace_bytes, w.end))
         return rc;
-    CREG_REQUIRE(pt_start && chain && center && H && g && cost && n, "%s: null pt_start, chain, center, H, g, cost or n", who);
-    CREG_REQUIRE(n_pts == 0 || (pts && tri_idx), "%s: null pts / tri_idx with n_pts %lld", who, (long long)n_pts);
     CREG_REQUIRE(n_joints == 0 || (parent && child && type && origin && axis), "%s: null joint table with n_joints %d", who, (int)n_joints);
     const int D = 6 + n_joints;
     const int chunks = (w.E + 255) / 256;

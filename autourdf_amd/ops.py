@@ -544,16 +544,30 @@ def urdf_fk(table, q, base, want_lines: bool = False):
     return (link_T, lines) if want_lines else link_T
 
 
-def _mesh_pair_args(who, tri, tri_start, link_T, pairs):
-    """The argument checks ``mesh_collide`` and ``mesh_clearance`` share -> (tri, tri_start, link_T (P,L,4,4), pairs, F, P, L, M)."""
-    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
-    tri_start, pairs = _need(tri_start, torch.int64, "tri_start"), _need(pairs, torch.int32, "pairs")
+def _mesh_args(tri, tri_start, link_T):
+    """tri, tri_start and link_T as every mesh query takes them -> ([(name, expected shape, tensor)] with link_T (L,4,4) lifted to
+    (1,L,4,4), whether the three shapes fit)."""
+    tri, link_T, tri_start = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T"), _need(tri_start, torch.int64, "tri_start")
     if link_T.dim() == 3:
         link_T = link_T[None]
-    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
-            or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pairs.dim() != 2 or pairs.shape[1] != 2:
-        raise ValueError(f"{who}: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pairs (M,2) expected, got "
-                         f"{tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, {tuple(pairs.shape)}")
+    ok = tri.dim() == 3 and tuple(tri.shape[1:]) == (3, 3) and link_T.dim() == 4 and tuple(link_T.shape[2:]) == (4, 4) \
+        and link_T.shape[0] >= 1 and tri_start.dim() == 1 and tri_start.shape[0] == link_T.shape[1] + 1
+    return [("tri", "(F,3,3)", tri), ("tri_start", "(L+1)", tri_start), ("link_T", "(P,L,4,4)", link_T)], ok
+
+
+def _shapes_expected(who, arrays):
+    """The ValueError that names every array with the expected and the received shape."""
+    return ValueError(f"{who}: {' / '.join(f'{name} {want}' for name, want, _ in arrays)} expected, got "
+                      f"{', '.join(str(tuple(t.shape)) for _, _, t in arrays)}")
+
+
+def _mesh_pair_args(who, tri, tri_start, link_T, pairs):
+    """The argument checks ``mesh_collide`` and ``mesh_clearance`` share -> (tri, tri_start, link_T (P,L,4,4), pairs, F, P, L, M)."""
+    arrays, ok = _mesh_args(tri, tri_start, link_T)
+    arrays.append(("pairs", "(M,2)", _need(pairs, torch.int32, "pairs")))
+    tri, tri_start, link_T, pairs = (t for _, _, t in arrays)
+    if not (ok and pairs.dim() == 2 and pairs.shape[1] == 2):
+        raise _shapes_expected(who, arrays)
     F, (P, n_links), M = tri.shape[0], link_T.shape[:2], pairs.shape[0]
     if n_links < 1:
         raise ValueError(f"{who}: at least one link")
@@ -666,6 +680,26 @@ def _morton_order(pts, pt_start, P):
     return torch.argsort(key)
 
 
+def _point_query_args(who, tri, tri_start, link_T, pts, pt_start, d_max, more=()):
+    """The argument checks the three point queries share: ``d_max`` >= 0, dtypes, contiguity and shapes of the mesh, of pts (N,3)
+    and pt_start (P+1), and of ``more`` = ((name, tensor, dtype, expected shape in N, P, L), ...) -> (d_max, tri, tri_start, link_T
+    (P,L,4,4), pts, pt_start, *more's tensors, F, P, L, N, device).  Nothing is read back."""
+    d_max = float(d_max)
+    if not d_max >= 0.0:
+        raise ValueError(f"{who}: d_max must be >= 0 (inf allowed), got {d_max}")
+    arrays, ok = _mesh_args(tri, tri_start, link_T)
+    arrays += [("pts", "(N,3)", _need(pts, torch.float64, "pts")), ("pt_start", "(P+1)", _need(pt_start, torch.int64, "pt_start"))]
+    arrays += [(name, want, _need(t, dtype, name)) for name, t, dtype, want in more]
+    tri, tri_start, link_T, pts, pt_start = (t for _, _, t in arrays[:5])
+    ok = ok and link_T.shape[1] >= 1 and pts.dim() == 2 and pts.shape[1] == 3 and pt_start.dim() == 1 and pt_start.shape[0] == link_T.shape[0] + 1
+    if ok:
+        size = {"N": pts.shape[0], "P": link_T.shape[0], "L": link_T.shape[1], "3": 3}
+        ok = all(tuple(t.shape) == tuple(size[d] for d in want[1:-1].split(",")) for _, want, t in arrays[5:])
+    if not ok:
+        raise _shapes_expected(who, arrays)
+    return (d_max,) + tuple(t for _, _, t in arrays) + (tri.shape[0], link_T.shape[0], link_T.shape[1], pts.shape[0], tri.device)
+
+
 def point_mesh_distance(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"), sort: bool = True, want_boxes: bool = False):
     """Distance from world points to posed link meshes (creg_point_mesh_f64; the contract is in include/creg.h): tri (F,3,3) f64
     link-frame triangles, tri_start (L+1) int64, link_T (P,L,4,4) f64 -- or (L,4,4) for P = 1 --, pts (N,3) f64 world points and
@@ -680,20 +714,8 @@ def point_mesh_distance(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"
     ValueError before any launch: a bad shape or dtype, a tri_start that does not run 0 .. F or a pt_start that does not run
     0 .. N without decreasing (both are read back: the one synchronisation), a negative or NaN ``d_max``."""
     L = _lib.load()
-    d_max = float(d_max)
-    if not d_max >= 0.0:
-        raise ValueError(f"point_mesh_distance: d_max must be >= 0 (inf allowed), got {d_max}")
-    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
-    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
-    if link_T.dim() == 3:
-        link_T = link_T[None]
-    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
-            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
-            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1:
-        raise ValueError(f"point_mesh_distance: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) expected, "
-                         f"got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, {tuple(pts.shape)}, "
-                         f"{tuple(pt_start.shape)}")
-    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    d_max, tri, tri_start, link_T, pts, pt_start, F, P, n_links, N, dev = _point_query_args(
+        "point_mesh_distance", tri, tri_start, link_T, pts, pt_start, d_max)
     ok = (tri_start[0] == 0) & (tri_start[-1] == F) & (tri_start[1:] >= tri_start[:-1]).all() \
         & (pt_start[0] == 0) & (pt_start[-1] == N) & (pt_start[1:] >= pt_start[:-1]).all()
     if not bool(ok):
@@ -743,22 +765,9 @@ def pose_fit_system(tri, tri_start, link_T, pts, pt_start, tri_idx, table, cente
     ``urdf_fk`` keeps ``_dev``): change a copy of a table without those keys.  tri_start and pt_start are not read back; the
     kernel clamps them.  ValueError before any launch: a bad shape or dtype, a negative or NaN ``d_max``, D > 64."""
     L = _lib.load()
-    d_max = float(d_max)
-    if not d_max >= 0.0:
-        raise ValueError(f"pose_fit_system: d_max must be >= 0 (inf allowed), got {d_max}")
-    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
-    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
-    tri_idx, center = _need(tri_idx, torch.int32, "tri_idx"), _need(center, torch.float64, "center")
-    if link_T.dim() == 3:
-        link_T = link_T[None]
-    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
-            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
-            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1 \
-            or tuple(tri_idx.shape) != (pts.shape[0],) or tuple(center.shape) != (link_T.shape[0], 3):
-        raise ValueError(f"pose_fit_system: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) / tri_idx (N) / "
-                         f"center (P,3) expected, got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, "
-                         f"{tuple(pts.shape)}, {tuple(pt_start.shape)}, {tuple(tri_idx.shape)}, {tuple(center.shape)}")
-    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    d_max, tri, tri_start, link_T, pts, pt_start, tri_idx, center, F, P, n_links, N, dev = _point_query_args(
+        "pose_fit_system", tri, tri_start, link_T, pts, pt_start, d_max,
+        (("tri_idx", tri_idx, torch.int32, "(N)"), ("center", center, torch.float64, "(P,3)")))
     J = len(table["parent"])
     if n_links != int(table["n_links"]) or 6 + J > POSE_FIT_MAX_D:
         raise ValueError(f"pose_fit_system: the table has {table['n_links']} links and {J} joints; link_T has {n_links} links and "
@@ -793,22 +802,9 @@ def link_moments(tri, tri_start, link_T, pts, pt_start, tri_idx, ref, d_max=floa
     into a normal system).  tri_start and pt_start are not read back; the kernel clamps them.  ValueError before any launch: a bad
     shape or dtype, a negative or NaN ``d_max``."""
     L = _lib.load()
-    d_max = float(d_max)
-    if not d_max >= 0.0:
-        raise ValueError(f"link_moments: d_max must be >= 0 (inf allowed), got {d_max}")
-    tri, link_T = _need(tri, torch.float64, "tri"), _need(link_T, torch.float64, "link_T")
-    tri_start, pts, pt_start = _need(tri_start, torch.int64, "tri_start"), _need(pts, torch.float64, "pts"), _need(pt_start, torch.int64, "pt_start")
-    tri_idx, ref = _need(tri_idx, torch.int32, "tri_idx"), _need(ref, torch.float64, "ref")
-    if link_T.dim() == 3:
-        link_T = link_T[None]
-    if tri.dim() != 3 or tuple(tri.shape[1:]) != (3, 3) or link_T.dim() != 4 or tuple(link_T.shape[2:]) != (4, 4) or link_T.shape[0] < 1 \
-            or link_T.shape[1] < 1 or tri_start.dim() != 1 or tri_start.shape[0] != link_T.shape[1] + 1 or pts.dim() != 2 \
-            or pts.shape[1] != 3 or pt_start.dim() != 1 or pt_start.shape[0] != link_T.shape[0] + 1 \
-            or tuple(tri_idx.shape) != (pts.shape[0],) or tuple(ref.shape) != (link_T.shape[0], link_T.shape[1], 3):
-        raise ValueError(f"link_moments: tri (F,3,3) / tri_start (L+1) / link_T (P,L,4,4) / pts (N,3) / pt_start (P+1) / tri_idx (N) / "
-                         f"ref (P,L,3) expected, got {tuple(tri.shape)}, {tuple(tri_start.shape)}, {tuple(link_T.shape)}, "
-                         f"{tuple(pts.shape)}, {tuple(pt_start.shape)}, {tuple(tri_idx.shape)}, {tuple(ref.shape)}")
-    F, (P, n_links), N, dev = tri.shape[0], link_T.shape[:2], pts.shape[0], tri.device
+    d_max, tri, tri_start, link_T, pts, pt_start, tri_idx, ref, F, P, n_links, N, dev = _point_query_args(
+        "link_moments", tri, tri_start, link_T, pts, pt_start, d_max,
+        (("tri_idx", tri_idx, torch.int32, "(N)"), ("ref", ref, torch.float64, "(P,L,3)")))
     mom = torch.empty(P, n_links, 16, dtype=torch.float64, device=dev)
     cnt = torch.empty(P, n_links, dtype=torch.int64, device=dev)
     ws_bytes = L.creg_link_moments_workspace_bytes(P, N, n_links)
