@@ -18,6 +18,7 @@ constexpr int JOINT_MAX_SAMPLES = 4096;      // samples per joint of k_joint_axe
 constexpr double JOINT_THETA_MIN = 2e-4;     // see creg.h: below ~1.4e-4 rad the reference's own 4x4 eigen test breaks down
 
 // Top eigenvector of a symmetric N x N matrix (cyclic Jacobi, fp64, registers).  Ties: the first largest diagonal.
+// A matrix with an entry that is not finite gives NaN.
 template <int N>
 __device__ void jacobi_top(double A[N][N], double v[N]) {
     double V[N][N];
@@ -32,6 +33,11 @@ __device__ void jacobi_top(double A[N][N], double v[N]) {
             diag += A[p][p] * A[p][p];
 #pragma unroll
             for (int q = p + 1; q < N; ++q) off += A[p][q] * A[p][q];
+        }
+        if (!isfinite(off + diag)) {                      // a NaN or Inf entry: no eigenvector, not the unit vector the
+#pragma unroll
+            for (int i = 0; i < N; ++i) v[i] = NAN;       // comparisons below would pick from the untouched V
+            return;
         }
         if (!(off > 1e-36 * diag)) break;
 #pragma unroll

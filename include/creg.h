@@ -312,7 +312,8 @@ int creg_coord_mst_f64(const double* coords, int32_t T, int32_t K, int32_t* edge
  *   Per sample (J,NS): sample_axis (3) unit direction, sample_angle in [0, pi], sample_point (3) the canonical point of the
  *   axis (init_position, compute_joints.py:68-77), sample_usable int32.  Each sample's angle is >= 0 (axis and angle as
  *   one pair (d, theta); the reference may return (-d, -theta)).  A sample is usable iff theta >= 2e-4 rad and the
- *   outputs are finite; an unusable sample has NaN axis and point.
+ *   outputs are finite; an unusable sample has NaN axis and point.  A link whose cluster poses at a step hold a NaN or an
+ *   Inf -- in a position or in a quaternion, whose average is then NaN -- makes the samples that touch that step unusable.
  *   Per joint: local_axis (J,3) = the principal axis, local_pos (J,4) = optimize_joint_axis's principal_pos (homogeneous),
  *   global_pos (J,3), global_axis (J,3) = R_child(first pose) @ local_axis, count (J) int32 usable samples,
  *   first_pose (J,2,7) or NULL = get_cluster_pose_mean of the parent and the child at sequence 0, step start_step
