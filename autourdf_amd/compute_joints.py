@@ -898,8 +898,6 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     before = torch.as_tensor([child_joint.get(int(pa), J) for pa in table["parent"]], dtype=torch.int64, device=dev).reshape(J)
     tri_joint = torch.as_tensor(np.repeat([child_joint.get(l, J) for l in range(n_links)], np.diff(tri_start_host).clip(0)),
                                 dtype=torch.int64, device=dev)
-    fixed_tab = tuple(torch.as_tensor(np.ascontiguousarray(table[k]), device=dev) for k in ("parent", "child", "type"))
-    axis_dev = torch.as_tensor(np.ascontiguousarray(table["axis"]), device=dev)
     origin = torch.as_tensor(np.ascontiguousarray(table["origin"]), dtype=dt, device=dev).clone()
     u1, u2 = (torch.as_tensor(u, device=dev) for u in joint_frame_basis(table["axis"]))
     revolute = torch.as_tensor((kinds == 1).astype(np.float64), device=dev)[:, None]
@@ -914,8 +912,7 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     H_cur = g_cur = total_cur = cost_cur = n_cur = prev = cost_first = None
     history = []
     for it in range(max_iter + 1):
-        tab = dict(table, _dev=fixed_tab + (origin.contiguous(), axis_dev))
-        link_T = (G[:, None] @ ops.urdf_fk(tab, q, eye)).contiguous()
+        link_T = (G[:, None] @ ops.urdf_fk(table, q, eye, origin=origin)).contiguous()
         tri_idx, cost, within = _truncated_cost(c, tri, link_T, d_max)
         total = float(cost.sum())
         if it == 0:

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from .ops._common import _workspace
 
 
 def farthest_point_sample(points, num_samples: int) -> np.ndarray:
@@ -19,6 +20,6 @@ def farthest_point_sample(points, num_samples: int) -> np.ndarray:
     if not (1 <= num_samples <= n):
         raise ValueError("need 1 <= num_samples <= number of points")
     sel = torch.empty(num_samples, dtype=torch.int64, device=X.device)
-    scratch = torch.empty(L.creg_fps_scratch_bytes(n), dtype=torch.uint8, device=X.device)
+    scratch = _workspace(X.device, L.creg_fps_scratch_bytes(n))
     _lib.check(L.creg_fps_f64(ops._p(X), n, num_samples, ops._p(sel), ops._p(scratch), ops._stream()), "creg_fps_f64")
     return sel.cpu().numpy()

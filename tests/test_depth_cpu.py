@@ -92,3 +92,40 @@ def test_restatement_removes_exactly_the_ground_from_oracle_depth_buffers(tmp_pa
     assert ref.fit_plane(np.array([[0.0, 0, 2], [-1, 0, 2], [0, 3, 2], [5, 5, 2]]) * [1, 1, -1])[2] == 1.0
     assert np.isnan(ref.fit_plane(np.array([[0.0, 0, 0], [1, 1, 2], [2, 2, 4], [3, 3, 6]]))).all()
     assert np.isnan(ref.fit_plane(np.tile([0.3, 0.1, 0.7], (6, 1)))).all()
+
+
+def test_segment_plane_hands_over_a_buffer_of_the_bytes_it_names(monkeypatch):
+    """S = 1, H = 1, n = 3: creg_segment_plane_workspace_bytes is 8 (4 SH + 9 SB) + 4 SH = 108 bytes, an odd count of 4-byte
+    words, so a buffer counted in whole doubles must round up.  A stub library, CPU tensors: the wrapper's own arithmetic alone."""
+    import torch
+    from autourdf_amd import _lib, ops
+    seen, held = {}, {}
+
+    class Stub:
+        @staticmethod
+        def creg_segment_plane_workspace_bytes(N, S, H):
+            seen["size_args"] = (N, S, H)
+            return 8 * (4 * S * H + 9 * S * 1) + 4 * S * H
+
+        @staticmethod
+        def creg_segment_plane_f64(*args):
+            seen["ws"], seen["ws_bytes"] = args[14].value, args[15]
+            return 0
+
+    def need(t, dtype, name):
+        assert isinstance(t, torch.Tensor) and t.dtype == dtype, name
+        return t.contiguous()
+
+    def pointer(t):                                                    # every pointer the wrapper extracts, with its tensor
+        if t is not None:
+            held[t.data_ptr()] = t
+        return ops._p(t)
+    monkeypatch.setattr(_lib, "load", lambda *a, **k: Stub())
+    monkeypatch.setattr(ops.sim, "_need", need)
+    monkeypatch.setattr(ops.sim, "_p", pointer)
+    monkeypatch.setattr(ops.sim, "_stream", lambda: None)
+    points = torch.tensor([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0], [0.5, 0.5, 1]], dtype=torch.float64)
+    out = ops.segment_plane(points, None, 0.01, ransac_n=3, samples=torch.tensor([[[0, 1, 2]]]))
+    assert len(out) == 4 and seen["size_args"] == (5, 1, 1) and seen["ws_bytes"] == 108 and (seen["ws_bytes"] // 4) % 2 == 1
+    ws = held[seen["ws"]]
+    assert ws.numel() * ws.element_size() >= seen["ws_bytes"] and seen["ws"] % 8 == 0

@@ -261,3 +261,31 @@ def test_last_link_carries_the_chain_above_bit_32(robot):
     keep = np.arange(64) != k
     np.testing.assert_array_equal(bits(less["H"][0][np.ix_(keep, keep)]), bits(got["H"][0][np.ix_(keep, keep)]))
     np.testing.assert_array_equal(bits(less["g"][0][keep]), bits(got["g"][0][keep]))
+
+
+# ------------------------------------------------------------------------------------------ the table's one upload
+def test_table_on_uploads_once_per_table_and_keeps_the_two_keys_apart(robot):
+    """ops._common._table_on on CPU tensors: the second call returns the kept tuple itself, the chain masks go under their own
+    key and leave the plain upload alone, and a copy stripped of the keys goes up afresh."""
+    import torch
+    from autourdf_amd import ops
+    from autourdf_amd.ops._common import _table_on
+    cpu = torch.device("cpu")
+    table = E.table_of_width(robot, 58)
+    assert not [k for k in table if k.startswith("_dev")]
+    plain = _table_on(cpu, table)
+    assert _table_on(cpu, table) is plain and table["_dev"] is plain and "_dev_fit" not in table
+    assert len(plain) == 5 and [tuple(t.shape) for t in plain] == [(58,), (58,), (58,), (58, 4, 4), (58, 3)]
+    for t, k in zip(plain, ("parent", "child", "type", "origin", "axis")):
+        assert t.dtype == torch.from_numpy(np.ascontiguousarray(table[k])).dtype and np.array_equal(t.numpy(), table[k])
+    fit = _table_on(cpu, table, chains=True)
+    assert _table_on(cpu, table, chains=True) is fit and table["_dev_fit"] is fit and table["_dev"] is plain
+    assert len(fit) == 6 and fit[5].dtype == torch.int64
+    assert np.array_equal(fit[5].numpy().view(np.uint64), ops.joint_chains(table))
+    for a, b in zip(fit[:5], plain):
+        assert a is not b and torch.equal(a, b)
+    copy = {k: v for k, v in table.items() if not k.startswith("_dev")}
+    again = _table_on(cpu, copy)
+    assert again is not plain and copy["_dev"] is again and "_dev_fit" not in copy and table["_dev"] is plain
+    for a, b in zip(again, plain):
+        assert torch.equal(a, b)

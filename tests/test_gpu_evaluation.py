@@ -169,6 +169,35 @@ def test_fk_refuses_bad_shapes(tmp_path):
         ops.urdf_fk(robot.fk_table(), np.zeros((2, 4)), np.eye(3))
 
 
+def test_fk_origin_keyword_stands_in_for_the_tables_origins_for_one_call(monkeypatch):
+    """Three links, a revolute and a prismatic joint, P = 2: ``origin=O`` gives the bits of a table whose origins are O, the next
+    call without it gives the table's own bits again (the kept upload was not written), and a wrong shape raises before a launch."""
+    from autourdf_amd import _lib, ops
+    rng = np.random.default_rng(7)
+    rigid = lambda: _base(rng.uniform(-1, 1, 3), rng.uniform(-0.2, 0.2, 3))
+    axis = np.array([[0.6, 0.0, 0.8], [0.0, 1.0, 0.0]])
+    table = {"parent": np.array([0, 1], np.int32), "child": np.array([1, 2], np.int32), "type": np.array([1, 2], np.int32),
+             "origin": np.stack([rigid(), rigid()]), "axis": axis, "names": ["turn", "slide"], "root": 0, "n_links": 3}
+    q, base = np.array([[0.7, -0.05], [-1.9, 0.11]]), rigid()
+    O = table["origin"] @ rigid()
+    own = [t.cpu().numpy() for t in ops.urdf_fk(table, q, base, want_lines=True)]
+    assert own[0].shape == (2, 3, 4, 4) and own[1].shape == (2, 2, 6)
+    moved = dict({k: v for k, v in table.items() if not k.startswith("_dev")}, origin=O)
+    want = [t.cpu().numpy() for t in ops.urdf_fk(moved, q, base, want_lines=True)]
+    assert np.abs(want[0] - own[0]).max() > 1e-3                       # the step is no identity
+    got = [t.cpu().numpy() for t in ops.urdf_fk(table, q, base, want_lines=True, origin=torch.as_tensor(O, device=_lib.device()))]
+    after = [t.cpu().numpy() for t in ops.urdf_fk(table, q, base, want_lines=True)]
+    for a, b, c, d in zip(got, want, after, own):
+        assert a.tobytes() == b.tobytes() and c.tobytes() == d.tobytes()
+    class NoLaunch:
+        def __getattr__(self, name):
+            pytest.fail(f"{name} reached with an origin that must raise first")
+    monkeypatch.setattr(_lib, "load", lambda *a, **k: NoLaunch())
+    for bad in (O[:1], O[:, :3], O.reshape(2, 16)):
+        with pytest.raises(ValueError, match="origin"):
+            ops.urdf_fk(table, q, base, origin=torch.as_tensor(np.ascontiguousarray(bad), device=_lib.device()))
+
+
 # ------------------------------------------------------------------------------------------ the optional keyword
 def test_sample_surface_and_visible_take_device_poses(tmp_path):
     from autourdf_amd import ops

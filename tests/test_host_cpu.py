@@ -666,7 +666,7 @@ def test_kmeans_lloyd_each_takes_the_batch_launch_exactly_up_to_its_limits(monke
     import torch
     from autourdf_amd import ops
     assert (ops.KMEANS_BATCH_MAX, ops.KMEANS_BATCH_MAX_N, ops.KMEANS_BATCH_MAX_K) == (16, 16384, 128)
-    calls = _record(monkeypatch, ops, ["kmeans_lloyd_batch", "kmeans_lloyd"])
+    calls = _record(monkeypatch, ops.segment, ["kmeans_lloyd_batch", "kmeans_lloyd"])
 
     def case(B, n, k, ns=None):
         Xs = [torch.zeros(n if ns is None else ns[b], 3, dtype=torch.float64) for b in range(B)]
@@ -690,7 +690,7 @@ def test_group_to_local_each_takes_the_batch_launch_exactly_up_to_its_limit(monk
     import torch
     from autourdf_amd import ops
     assert ops.GROUP_BATCH_MAX == 16
-    calls = _record(monkeypatch, ops, ["group_to_local_batch", "group_to_local"])
+    calls = _record(monkeypatch, ops.segment, ["group_to_local_batch", "group_to_local"])
 
     def case(ns, inverse):
         Xs = [torch.zeros(n, 3, dtype=torch.float64) for n in ns]
@@ -717,7 +717,7 @@ def test_masked_icp_each_takes_the_batch_launch_exactly_up_to_its_limit(monkeypa
     from autourdf_amd import ops
     assert ops.ICP_BATCH_MAX == 16
     signature = inspect.signature(ops.masked_icp)
-    calls = _record(monkeypatch, ops, ["masked_icp_batch", "masked_icp", "cluster_transform"])
+    calls = _record(monkeypatch, ops.icp, ["masked_icp_batch", "masked_icp", "cluster_transform"])
 
     def problems(ns, world="given", woff=False):
         out = []
@@ -752,3 +752,40 @@ def test_masked_icp_each_takes_the_batch_launch_exactly_up_to_its_limit(monkeypa
             assert bound.arguments["world"] == ("cluster_transform", 2 * b) and bound.arguments.get("world_offsets") is None
             assert "scale" not in bound.arguments
             assert [bound.arguments[k] is p[i] for k, i in (("local", 0), ("offsets", 2), ("frame", 3), ("M", 4))] == [True] * 4
+
+
+#: the public names of autourdf_amd/ops.py when it was one file: every one of them stays reachable as ops.<name>
+OPS_PUBLIC = [
+    "DQ_PARAM_ORDER", "GROUP_BATCH_MAX", "HULL_MAX_COORD", "HULL_STATUS", "ICP_BATCH_MAX", "JOINT_MAX_SAMPLES", "JOINT_THETA_MIN",
+    "KMEANS_BATCH_MAX", "KMEANS_BATCH_MAX_K", "KMEANS_BATCH_MAX_N", "KMEANS_ND_MAX_K", "KMEANS_ND_MAX_N", "LINK_SWEEP_MAX_K",
+    "MESH_CONTAIN_MAX_POINTS", "MESH_INERTIA_KEYS", "MESH_MAX_NEIGHBORS", "POSE_FIT_MAX_D", "Q_PARAM_ORDER", "TRAIN_HIDDEN_TILES",
+    "TRAIN_ROT", "TrainPlan", "aabb_mask", "chamfer_distance", "cluster_transform", "coord_dist_map", "coord_mst", "depth_points",
+    "dq_invert", "dq_multiply", "dq_to_quat_trans", "dq_to_se3", "dq_to_se3_bwd", "group_to_local", "group_to_local_batch",
+    "group_to_local_each", "icp_nn_counters", "icp_p2p", "icp_p2p_batch", "joint_axes", "joint_axes_prepare", "joint_chains",
+    "joint_positions", "joint_samples", "joint_slides", "joint_types", "kabsch", "kmeans_assign", "kmeans_lloyd", "kmeans_lloyd_batch",
+    "kmeans_lloyd_each", "kmeans_lloyd_nd", "knn_normals", "lattice_hull", "link_clouds", "link_clouds_bytes", "link_clouds_prepare",
+    "link_moments", "link_poses", "link_sweep", "masked_icp", "masked_icp_batch", "masked_icp_each", "masked_icp_regime",
+    "matrix_to_quat", "mesh_clearance", "mesh_collide", "mesh_contain", "mesh_inertia", "motion_error", "nn_l1_bidir", "pack_clusters",
+    "point_mesh_distance", "pose_coords", "pose_fit_system", "quat_to_matrix", "quat_trans_to_dq", "raster_depth", "sample_mesh",
+    "se3_to_dq", "segment_plane", "statistical_outlier", "urdf_fk", "visibility", "voxel_layout", "voxel_mesh"]
+
+
+def test_ops_package_keeps_the_one_file_surface():
+    import types
+    from autourdf_amd import ops
+    assert len(OPS_PUBLIC) == 85 and OPS_PUBLIC == sorted(OPS_PUBLIC)
+    public = sorted(n for n, v in vars(ops).items() if not n.startswith("_") and not isinstance(v, types.ModuleType))
+    assert public == OPS_PUBLIC
+    for private in ("_p", "_stream", "_need", "_morton_order"):                   # used from outside the package
+        assert callable(getattr(ops, private))
+    assert os.path.isdir(os.path.dirname(ops.__file__)) and os.path.basename(ops.__file__) == "__init__.py"
+    assert not os.path.exists(os.path.join(ROOT, "autourdf_amd", "ops.py"))
+
+
+def test_workspace_holds_the_bytes_asked_for_at_an_8_byte_boundary():
+    import torch
+    from autourdf_amd.ops._common import _workspace
+    for nbytes in (0, 1, 4, 7, 8, 12, 257):
+        ws = _workspace(torch.device("cpu"), nbytes)
+        assert ws.dtype == torch.uint8 and ws.device.type == "cpu" and ws.is_contiguous()
+        assert ws.numel() * ws.element_size() >= max(nbytes, 1) and ws.data_ptr() % 8 == 0

@@ -25,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from autourdf_amd import _lib, evaluation, ops  # noqa: E402
+from autourdf_amd.ops._common import _table_on  # noqa: E402
 from autourdf_amd.sim_data import UrdfRobot  # noqa: E402
 from _robots import unpack_robots  # noqa: E402
 from _toy_urdf import write_toy_robot  # noqa: E402
@@ -54,7 +55,7 @@ def time_fk(name, path, reps):
         rows = [{j["name"]: float(rng.uniform(*sorted(j["limit"]))) for j in robot.joints} for _ in range(P)]
         q = robot.q_rows(rows)
         ops.urdf_fk(table, q, base, want_lines=True)                     # the table goes up here
-        parent, child, kind, origin, axis = table["_dev"]
+        parent, child, kind, origin, axis = _table_on(dev, table)
         qd, bd = torch.as_tensor(q, device=dev), torch.as_tensor(base, device=dev)
         J, nl = len(table["names"]), table["n_links"]
         link_T = torch.empty(P, nl, 4, 4, dtype=torch.float64, device=dev)
