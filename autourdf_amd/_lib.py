@@ -98,6 +98,8 @@ SIGNATURES = {
                                                 vp, vp, vp, sz, vp]),
     "creg_link_moments_workspace_bytes": (sz, [i64, i64, i32]),
     "creg_link_moments_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, f64, vp, vp, vp, vp, vp, sz, vp]),
+    "creg_feature_moments_workspace_bytes": (sz, [i64, i64, i32]),
+    "creg_feature_moments_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, f64, vp, vp, vp, vp, vp, vp, sz, vp]),
     "creg_mesh_contain_workspace_bytes": (sz, [i64, i32, i64, i64, i32]),
     "creg_mesh_contain_f64": (ctypes.c_int, [vp, vp, i64, vp, vp, i64, vp, i32, i64, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
     "creg_mesh_inertia_workspace_bytes": (sz, [i64, i32]),

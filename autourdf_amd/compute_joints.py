@@ -569,6 +569,7 @@ def cloud_fit(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps
     return fit
 
 
+FIT_METRICS = ("point", "feature")                                              # the curvature of the two Levenberg-Marquardt drivers
 FIT_LAMBDA_MIN, FIT_LAMBDA_STOP = 1e-12, 1e8                                   # the floor of the damping, and where a pose gives up
 
 
@@ -650,7 +651,14 @@ def _rms(n_live, cost):
         return np.where(n_live > 0, np.sqrt(cost / np.maximum(n_live, 1.0)), np.nan)
 
 
-def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10):
+def _fit_metric(who, metric):
+    if metric not in FIT_METRICS:
+        raise ValueError(f"{who}: metric must be one of {FIT_METRICS}, got {metric!r}")
+    return metric
+
+
+def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10,
+                    metric="point"):
     """Fit a robot's joint values and base pose to one cloud per pose by Levenberg-Marquardt on the point-to-mesh distance (this
     project's own): robot a ``UrdfRobot`` loaded with its meshes, clouds a list of P (n_p,3) arrays of world points, q0 (P,J) the
     starting joint values in ``robot.fk_table()``'s order, base0 (4,4) or (P,4,4) the starting root poses (identity when None).
@@ -671,7 +679,15 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
     (P,J), base (P,4,4), cost_history (P lists, non-increasing by construction: the first entry is the start, one more per step
     tried), iterations (P) steps tried, rms_before and rms_after (P) = sqrt(cost / live points), unobserved (P,6+J) bool in the
     order rotation, translation, joints, n (P) the points within ``d_max`` at the returned state, and names (the joints' names in
-    the table's order).  Not done here: joint limits, a point-to-plane metric, warm starts from a neighbouring frame."""
+    the table's order).
+    ``metric`` chooses the curvature of step 5 alone; the cost, the gradient, the accept rule, the stops and every returned figure
+    are the same.  "point": H = sum J^T J of ``ops.pose_fit_system`` (6 + J <= 64), which converges linearly along a surface.
+    "feature": H = sum J^T Pi J, Pi the projector onto the normal space of the vertex, edge or face each point matched -- the exact
+    Hessian of the squared distance to that feature -- from one ``ops.link_moments(metric="feature")`` call about center_p,
+    ``link_twists(structure=False)`` and ``twist_system``; no cap on the joint count.  With a ``d_max`` well below the starting
+    misalignment the feature step has been seen to jump far while the truncated cost still fell: keep ``d_max`` above it.
+    Not done here: joint limits, warm starts from a neighbouring frame."""
+    metric = _fit_metric("fit_cloud_poses", metric)
     table = robot.fk_table()
     names, kinds = list(table["names"]), np.asarray(table["type"])
     J, D = len(names), 6 + len(names)
@@ -706,7 +722,12 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
         history.append(cost_cur)
         if it == max_iter or not bool(active.any()):
             break
-        H, g, _, _ = ops.pose_fit_system(tri, tri_start, link_T, pts, cut, tri_idx, table, center, d_max)
+        if metric == "feature":
+            ref = center[:, None, :].expand(P, link_T.shape[1], 3).contiguous()
+            mom, cnt, fmom = ops.link_moments(tri, tri_start, link_T, pts, cut, tri_idx, ref, d_max, metric="feature")
+            H, g, _ = twist_system(mom, cnt, link_twists(table, link_T, q, center, ref, structure=False), fmom)
+        else:
+            H, g, _, _ = ops.pose_fit_system(tri, tri_start, link_T, pts, cut, tri_idx, table, center, d_max)
         if H_cur is None:
             H_cur, g_cur = H, g
         else:
@@ -737,18 +758,19 @@ def fit_cloud_poses(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fi
             "unobserved": unobserved.cpu().numpy(), "n": n_cur.cpu().numpy(), "names": names}
 
 
-def fit_positions(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf, max_iter=30):
+def fit_positions(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf, max_iter=30,
+                  metric="point"):
     """Fit the written URDF's joint positions to the raw clouds, frame by frame (this project's own): the poses of ``cloud_fit``
     -- the replay's ``q`` rows and the registered root motion G -- are the start, every frame is fitted with the base free
-    (``fit_cloud_poses``), ``d_max`` is the cloud fit's limit.  Returns ``fit_cloud_poses``' dict with "positions" added, the
-    fitted values (J,S,num_steps) in the order of ``motion`` (the layout of ``joint_positions.npy``), and "shift" (J), per joint
+    (``fit_cloud_poses``, which states ``metric``), ``d_max`` is the cloud fit's limit.  Returns ``fit_cloud_poses``' dict with
+    "positions" added, the fitted values (J,S,num_steps) in the order of ``motion`` (the layout of ``joint_positions.npy``), and "shift" (J), per joint
     the largest |q_fit - q_registered|.  The URDF and its limits are not touched."""
     from .cluster_icp import read_point_cloud
     robot, q, G = _cloud_fit_state(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
     S, n = len(cm_list), int(num_steps)
     clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
               for s in range(S) for k in range(n)]
-    fit = fit_cloud_poses(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True)
+    fit = fit_cloud_poses(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True, metric=metric)
     positions = np.array([np.asarray(m["positions"], np.float64).reshape(S, n) for m in motion]).reshape(len(motion), S, n)
     shift = np.zeros(len(motion))
     for j, m in enumerate(motion):
@@ -837,27 +859,36 @@ def link_twists(table, link_T, q, center, ref, origin=None, structure=True):
     return Tw
 
 
-def twist_system(mom, cnt, Tw):
+_UPPER6 = [(a, b) for a in range(6) for b in range(a, 6)]           # the order of fmom's 21 sums
+_UNPACK6 = [_UPPER6.index((min(a, b), max(a, b))) for a in range(6) for b in range(6)]      # entry (a, b) of M6 <- which of the 21
+
+
+def twist_system(mom, cnt, Tw, fmom=None):
     """The normal system of twist columns from link moments (this project's own; plain torch on the device): mom (P,L,16) and cnt
     (P,L) of ``ops.link_moments`` taken about the point the twists Tw (P,L,6,M) of ``link_twists`` are given about ->
     (H (P,M,M), g (P,M), cost (P)).  With S2 = sum d d^T, S1 = sum d, n, Sx = sum d x r, Sr = sum r of (p, l):
     H[a][b] = sum_l Om_a^T (tr(S2) I - S2) Om_b + (Om_a x S1).V_b + (Om_b x S1).V_a + n V_a.V_b, g[a] = sum_l Om_a.Sx + V_a.Sr,
-    cost = sum_l mom[15] -- per link one 6 x 6 matrix [[tr(S2) I - S2, [S1]x], [-[S1]x, n I]] between the twists."""
+    cost = sum_l mom[15] -- per link one 6 x 6 matrix [[tr(S2) I - S2, [S1]x], [-[S1]x, n I]] between the twists.  With fmom
+    (P,L,21) of ``ops.link_moments(metric="feature")`` that matrix is instead M6 = sum A^T Pi A, unpacked from its upper triangle:
+    the curvature of the matched features in place of the point-to-point one; g and the cost come from mom either way."""
     P, L = mom.shape[:2]
-    S2 = mom[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(P, L, 3, 3)
-    eye3 = torch.eye(3, dtype=mom.dtype, device=mom.device)
-    X = _cross_matrix(mom[..., 6:9])
-    M6 = torch.zeros(P, L, 6, 6, dtype=mom.dtype, device=mom.device)
-    M6[..., :3, :3] = (mom[..., 0] + mom[..., 3] + mom[..., 5])[..., None, None] * eye3 - S2
-    M6[..., :3, 3:], M6[..., 3:, :3] = X, -X
-    M6[..., 3:, 3:] = cnt.to(mom.dtype)[..., None, None] * eye3
+    if fmom is not None:
+        M6 = fmom[..., _UNPACK6].reshape(P, L, 6, 6)
+    else:
+        M6 = torch.zeros(P, L, 6, 6, dtype=mom.dtype, device=mom.device)
+        S2 = mom[..., [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(P, L, 3, 3)
+        eye3 = torch.eye(3, dtype=mom.dtype, device=mom.device)
+        X = _cross_matrix(mom[..., 6:9])
+        M6[..., :3, :3] = (mom[..., 0] + mom[..., 3] + mom[..., 5])[..., None, None] * eye3 - S2
+        M6[..., :3, 3:], M6[..., 3:, :3] = X, -X
+        M6[..., 3:, 3:] = cnt.to(mom.dtype)[..., None, None] * eye3
     H = (Tw.transpose(-1, -2) @ M6 @ Tw).sum(1)
     g = (Tw.transpose(-1, -2) @ mom[..., 9:15, None]).sum(1)[..., 0]
     return H, g, mom[..., 15].sum(1)
 
 
 def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lock_frames=(), lam0=1e-3,
-                        tol=1e-10):
+                        tol=1e-10, metric="point"):
     """Refine the frames of a robot's movable joints against one cloud per pose: a bundle adjustment by Levenberg-Marquardt on the
     point-to-mesh distance (this project's own).  Shared by all poses: per revolute joint four frame parameters, per prismatic
     joint two (``link_twists``).  Per pose: its joint values and base pose, as in ``fit_cloud_poses``, whose arguments, settings
@@ -876,7 +907,9 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
     Returns ``fit_cloud_poses``' dict with one cost_history of totals (non-increasing by construction), iterations the steps
     tried, rms_before / rms_after per pose and rms_all_before / rms_all_after over all live points, frames (J,4,4) the accumulated
     E_j = E_j(1) E_j(2) ... (``set_joint_frames`` writes them into a URDF), unobserved_frames (J,4) bool, and the final origin
-    (J,4,4), tri (F,3,3) and link_T (P,L,4,4).  ``robot`` is not changed."""
+    (J,4,4), tri (F,3,3) and link_T (P,L,4,4).  ``robot`` is not changed.  ``metric`` is ``fit_cloud_poses``': "feature" takes
+    step 5's curvature from ``ops.link_moments(metric="feature")`` and ``twist_system(..., fmom)``, everything else as it is."""
+    metric = _fit_metric("refine_joint_frames", metric)
     table0 = robot.fk_table()
     table = {k: v for k, v in table0.items() if not k.startswith("_dev")}
     names, kinds = list(table["names"]), np.asarray(table["type"])
@@ -930,8 +963,8 @@ def refine_joint_frames(robot, clouds, q0, base0=None, d_max=np.inf, max_iter=30
         if it == max_iter or not active:
             break
         if accept:                                                # a rejected step keeps the system of the state it went back to
-            mom, cnt = ops.link_moments(tri, tri_start, link_T, pts, cut, tri_idx, ref, d_max)
-            H_cur, g_cur, _ = twist_system(mom, cnt, link_twists(table, link_T, q, center, ref, origin))
+            mom, cnt, *fmom = ops.link_moments(tri, tri_start, link_T, pts, cut, tri_idx, ref, d_max, metric=metric)
+            H_cur, g_cur, _ = twist_system(mom, cnt, link_twists(table, link_T, q, center, ref, origin), *fmom)
         dp = torch.diagonal(H_cur[:, :Dp, :Dp], dim1=1, dim2=2)
         ds = torch.diagonal(H_cur[:, Dp:, Dp:], dim1=1, dim2=2).sum(0)
         free_p, free_s = free_p0[None] & (dp != 0.0), free_s0 & (ds != 0.0)
@@ -1057,9 +1090,10 @@ def frame_shift(frame, axis, kind=1):
 
 
 def refine_urdf_joints(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, output_file, time_step=0, d_max=np.inf,
-                       max_iter=30):
+                       max_iter=30, metric="point"):
     """Refine the written URDF's joint frames against the raw clouds and write the result beside it (this project's own): the
-    poses of ``cloud_fit`` are the start, all loaded frames are fitted at once with the base free (``refine_joint_frames``),
+    poses of ``cloud_fit`` are the start, all loaded frames are fitted at once with the base free (``refine_joint_frames``,
+    with its ``metric``),
     ``d_max`` is the cloud fit's limit, and ``set_joint_frames`` writes ``output_file``; ``urdf_file`` is only read.  Returns
     ``refine_joint_frames``' dict with "positions" (J,S,num_steps) and "shift" (J) as ``fit_positions`` adds them, and "joints",
     per joint of ``motion`` a dict of joint, axis_angle and line_distance (``frame_shift`` of its accumulated step) and
@@ -1069,7 +1103,7 @@ def refine_urdf_joints(urdf_file, links, motion, cm_list, raw_dirs, start_step, 
     S, n = len(cm_list), int(num_steps)
     clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
               for s in range(S) for k in range(n)]
-    fit = refine_joint_frames(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True)
+    fit = refine_joint_frames(robot, clouds, q, G, d_max=d_max, max_iter=max_iter, fit_base=True, metric=metric)
     table = robot.fk_table()
     set_joint_frames(urdf_file, {name: fit["frames"][j] for j, name in enumerate(fit["names"])
                                  if not np.array_equal(fit["frames"][j], np.eye(4))}, output_file)

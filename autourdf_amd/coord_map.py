@@ -399,7 +399,8 @@ def _cli_parser():
     --fit_iters without --fit_positions, are usage errors.  --refine_joints refines the URDF's joint frames against all loaded
     raw clouds after the cloud fit and writes <name>.refined.urdf and <name>.refined_positions.npy; --refine_iters (default
     30) caps its iterations.  --refine_joints without --cloud_fit, and --refine_iters without --refine_joints, are usage
-    errors."""
+    errors.  --fit_metric {point,feature} chooses the curvature of both fits (``compute_joints.fit_cloud_poses``); without
+    --fit_positions or --refine_joints it is a usage error."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
@@ -415,6 +416,7 @@ def _cli_parser():
     parser.add_argument('--fit_iters', type=int, default=None)
     parser.add_argument('--refine_joints', action='store_true')
     parser.add_argument('--refine_iters', type=int, default=None)
+    parser.add_argument('--fit_metric', choices=('point', 'feature'), default=None)
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -439,6 +441,8 @@ def _cli_parser():
             parser.error("--refine_joints needs --cloud_fit: it starts from the poses the cloud fit measures")
         if ns.refine_iters is not None and not ns.refine_joints:
             parser.error("--refine_iters needs --refine_joints")
+        if ns.fit_metric is not None and not (ns.fit_positions or ns.refine_joints):
+            parser.error("--fit_metric needs --fit_positions or --refine_joints: it is the curvature of their steps")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -475,7 +479,9 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
 def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None, refined=None):
     """Write <name>.cloud_fit.json next to the URDF -- the per-frame, per-sequence, per-link and overall figures of
     ``cloud_fit``, without the per-point arrays -- and print one line per sequence (rms, p95, unexplained share) and the worst
-    frame.  ``fit_max`` is written as null when it is inf.  With ``fitted`` (``fit_positions``' dict) the file gains a "fitted"
+    frame.  ``fit_max`` is written as null when it is inf.  A ``fitted`` or ``refined`` dict that carries a "metric" (the
+    command line's --fit_metric or the fit_metric key, when given) has it written into its block.  With
+    ``fitted`` (``fit_positions``' dict) the file gains a "fitted"
     block -- per frame the rms before and after the fit and the steps tried, per sequence and overall the rms before and
     after, per joint the largest |q_fit - q_registered| --, <name>.fitted_positions.npy (J,S,steps) is written beside
     joint_positions.npy, and one line per sequence and one per joint are printed.  With ``refined`` (``refine_urdf_joints``'
@@ -503,11 +509,15 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
             "all": {"rms_before": pooled(fitted["rms_before"], np.arange(S * num_steps)),
                     "rms_after": pooled(fitted["rms_after"], np.arange(S * num_steps))},
             "joints": [{"joint": name, "max_shift": float(d)} for name, d in zip(fitted["joint_names"], fitted["shift"])]}
+        if "metric" in fitted:
+            report["fitted"]["metric"] = fitted["metric"]
     if refined is not None:
         np.save(stem + '.refined_positions.npy', refined["positions"])
         report["refined"] = {"urdf": refined["urdf"], "iterations": int(refined["iterations"]),
                              "all": clean({"rms_before": float(refined["rms_all_before"]), "rms_after": float(refined["rms_all_after"])}),
                              "joints": [clean(dict(j)) for j in refined["joints"]]}
+        if "metric" in refined:
+            report["refined"]["metric"] = refined["metric"]
     with open(stem + '.cloud_fit.json', 'w') as f:
         json.dump(report, f, indent=1)
     for name, s in zip(seq_names, fit["sequences"]):
@@ -566,7 +576,9 @@ def main(argv=None):
     free, ``fit_max`` as the distance limit), ``<name>.refined.urdf`` and ``<name>.refined_positions.npy`` (J,S,steps) are
     written beside the URDF, ``cloud_fit.json`` gains a "refined" block and one line per joint is printed; the original URDF
     keeps every byte.  It needs the cloud fit, and a ``refine_iters`` needs it: ValueError before anything is written
-    otherwise."""
+    otherwise.  ``--fit_metric`` (or a ``fit_metric`` key, "point" or "feature"; the option wins) is the ``metric`` of both fits
+    and is written into their blocks of ``cloud_fit.json``; without it nothing changes, and without ``fit_positions`` or
+    ``refine_joints`` it is a ValueError before anything is written."""
     import json
     import os
 
@@ -646,6 +658,13 @@ def main(argv=None):
     refine_iters = 30 if refine_iters is None else int(refine_iters)
     if refine_iters < 0:
         raise ValueError(f"refine_iters must be >= 0, got {refine_iters}")
+    fit_metric = args.fit_metric if args.fit_metric is not None else robot_params.get('fit_metric')
+    if fit_metric is not None and not (want_positions or want_refine):
+        raise ValueError("a fit_metric is the curvature of fit_positions and refine_joints: give --fit_positions or --refine_joints "
+                         "(or their keys in parameters.json) with it")
+    if fit_metric not in (None, "point", "feature"):
+        raise ValueError(f"fit_metric must be 'point' or 'feature', got {fit_metric!r}")
+    metric = {} if fit_metric is None else {"metric": fit_metric}
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -725,13 +744,15 @@ def main(argv=None):
             fitted = None
             if want_positions:
                 fitted = fit_positions(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START,
-                                       d_max=fit_max, max_iter=fit_iters)
+                                       d_max=fit_max, max_iter=fit_iters, **metric)
+                fitted.update(metric)
                 fitted["joint_names"] = [f"joint_{m['child_link']}" for m in motion]
             refined = None
             if want_refine:
                 refined_path = urdf_path[:-len('.urdf')] + '.refined.urdf'
                 refined = refine_urdf_joints(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START,
-                                             refined_path, d_max=fit_max, max_iter=refine_iters)
+                                             refined_path, d_max=fit_max, max_iter=refine_iters, **metric)
+                refined.update(metric)
                 refined["urdf"] = refined_path
             _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path], fitted,
                               refined)

@@ -1,7 +1,8 @@
 // point_rows.h -- a pose's rows of points, in tiles: what the kernels over (pose, tile of that pose's points) share.  A header of its
-// own beside mesh_dist.h, which it includes; point_mesh.hip, pose_fit.hip and link_moments.hip include this one.
+// own beside mesh_dist.h, which it includes; point_mesh.hip, pose_fit.hip, link_moments.hip and feature_moments.hip include this one.
 //   rows and tiles   pose_rows (the one clamp of pt_start), tile_slot and find_tile (block -> pose and tile), for tiles of 1 << SHIFT
 //   matched_row      does a row with a nearest triangle contribute, with which link, r and r.r (pose_fit.hip, link_moments.hip)
+//   matched_feature_row   the same, with pt_tri_vec's case and the posed vertices as well (feature_moments.hip)
 //   tile_sum4        a pose's tile partials into one sum, in the order include/creg.h fixes
 // The contract of every function is in include/creg.h under creg_point_mesh_f64 and creg_pose_fit_system_f64.
 #pragma once
@@ -49,10 +50,12 @@ __device__ __forceinline__ int64_t clamped_start(const int64_t* __restrict__ tri
 // rows of a link l (the largest l whose clamped start is not above f), rr = dot3(r, r) <= dmax2 for r = pt_tri_vec of x against
 // the row's vertices posed by pose_tri, so rr has the bits of creg_point_mesh_f64's dist2.  The caller's code runs inside the gate,
 // where the kernels had it: a returned link tested again by the caller cost k_link_moments_tiles two SGPRs.
+// matched_feature_row is the same gate handing out more: use(l, r, rr, which, w) with which = the case pt_tri_vec returned (1 .. 7) and
+// w (9) the posed vertices a | b | c it was computed from (feature_moments.hip builds the feature's projector from them).
 template <class Use>
-__device__ __forceinline__ void matched_row(const double* __restrict__ tri, const int64_t* __restrict__ tri_start, int64_t F,
-                                            const double* __restrict__ link_T, int L, int64_t p, const double* x, int64_t f, double dmax2,
-                                            Use use) {
+__device__ __forceinline__ void matched_feature_row(const double* __restrict__ tri, const int64_t* __restrict__ tri_start, int64_t F,
+                                                    const double* __restrict__ link_T, int L, int64_t p, const double* x, int64_t f,
+                                                    double dmax2, Use use) {
     const bool live = x[0] == x[0] && x[1] == x[1] && x[2] == x[2];
     if (!(live && f >= 0 && f < F)) return;
     int lo = 0, up = L;
@@ -67,9 +70,16 @@ __device__ __forceinline__ void matched_row(const double* __restrict__ tri, cons
 #pragma unroll
     for (int k = 0; k < 9; ++k) v[k] = tri[(size_t)f * 9 + k];
     pose_tri(link_T + ((size_t)p * L + lo) * 16, v, w);
-    pt_tri_vec(x, w, w + 3, w + 6, r);
+    const int which = pt_tri_vec(x, w, w + 3, w + 6, r);
     const double rr = dot3(r, r);
-    if (rr <= dmax2) use(lo, r, rr);
+    if (rr <= dmax2) use(lo, r, rr, which, w);
+}
+template <class Use>
+__device__ __forceinline__ void matched_row(const double* __restrict__ tri, const int64_t* __restrict__ tri_start, int64_t F,
+                                            const double* __restrict__ link_T, int L, int64_t p, const double* x, int64_t f, double dmax2,
+                                            Use use) {
+    matched_feature_row(tri, tri_start, F, link_T, L, p, x, f, dmax2,
+                        [&](int l, const double* r, double rr, int, const double*) { use(l, r, rr); });
 }
 
 // a pose's tile partials src[t * stride], t = 0 .. tiles - 1 in ascending order, into four running sums (tile t into sum t mod 4)

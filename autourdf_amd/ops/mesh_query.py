@@ -255,26 +255,33 @@ def pose_fit_system(tri, tri_start, link_T, pts, pt_start, tri_idx, table, cente
     return H, g, cost, n
 
 
-def link_moments(tri, tri_start, link_T, pts, pt_start, tri_idx, ref, d_max=float("inf")):
+def link_moments(tri, tri_start, link_T, pts, pt_start, tri_idx, ref, d_max=float("inf"), metric="point"):
     """The 16 moment sums per (pose, link) of the correspondences (creg_link_moments_f64; the contract is in include/creg.h): tri,
     tri_start, link_T, pts, pt_start, tri_idx and ``d_max`` as ``pose_fit_system`` takes them, ref (P,L,3) f64 the point the
     moments of every (pose, link) are taken about -> (mom (P,L,16) f64, cnt (P,L) int64) on the device: per (pose, link) the sums
     of d d^T (6: xx xy xz yy yz zz), d (3), d x r (3), r (3) and r.r over its contributing points, d = c - ref, and their number.
     One call for all poses; no joint table and no limit on a parameter count (``compute_joints.twist_system`` turns the moments
-    into a normal system).  tri_start and pt_start are not read back; the kernel clamps them.  ValueError before any launch: a bad
-    shape or dtype, a negative or NaN ``d_max``."""
+    into a normal system).  With ``metric="feature"`` one call of creg_feature_moments_f64 instead -> (mom, cnt, fmom): the same
+    mom and cnt, bit for bit, and fmom (P,L,21) f64, the upper triangle (row-major, a <= b) of the 6 x 6 curvature sum A^T Pi A of
+    the matched features between the twists (Omega, V), Pi the projector onto the normal space of the vertex, edge or face the
+    point matched (``twist_system(..., fmom=fmom)``).  tri_start and pt_start are not read back; the kernel clamps them.
+    ValueError before any launch: a bad shape or dtype, a negative or NaN ``d_max``, a ``metric`` other than "point" or "feature"."""
+    if metric not in ("point", "feature"):
+        raise ValueError(f"link_moments: metric must be 'point' or 'feature', got {metric!r}")
     L = _lib.load()
     d_max, tri, tri_start, link_T, pts, pt_start, tri_idx, ref, F, P, n_links, N, dev = _point_query_args(
         "link_moments", tri, tri_start, link_T, pts, pt_start, d_max,
         (("tri_idx", tri_idx, torch.int32, "(N)"), ("ref", ref, torch.float64, "(P,L,3)")))
     mom = torch.empty(P, n_links, 16, dtype=torch.float64, device=dev)
     cnt = torch.empty(P, n_links, dtype=torch.int64, device=dev)
-    ws_bytes = L.creg_link_moments_workspace_bytes(P, N, n_links)
+    outs = (mom, cnt) + ((torch.empty(P, n_links, 21, dtype=torch.float64, device=dev),) if metric == "feature" else ())
+    name = "creg_feature_moments" if metric == "feature" else "creg_link_moments"
+    ws_bytes = getattr(L, name + "_workspace_bytes")(P, N, n_links)
     ws = _workspace(dev, ws_bytes)
-    _lib.check(L.creg_link_moments_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pts) if N else None,
-                                       _p(pt_start), N, d_max, _p(tri_idx) if N else None, _p(ref), _p(mom), _p(cnt), _p(ws), ws_bytes,
-                                       _stream()), "creg_link_moments_f64")
-    return mom, cnt
+    _lib.check(getattr(L, name + "_f64")(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(pts) if N else None,
+                                         _p(pt_start), N, d_max, _p(tri_idx) if N else None, _p(ref), *(_p(o) for o in outs), _p(ws),
+                                         ws_bytes, _stream()), name + "_f64")
+    return outs
 
 
 def mesh_inertia(tri, tri_start, density=1.0):

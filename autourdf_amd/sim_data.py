@@ -761,23 +761,24 @@ class SimEnv:
         out = ops.point_mesh_distance(tri, tri_start, link_T, pts, torch.as_tensor(cut, device=tri.device), d_max)
         return tuple([a[cut[p]:cut[p + 1]] for p in range(len(parts))] for a in (o.cpu().numpy() for o in out))
 
-    def fit_pose(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10):
+    def fit_pose(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10, metric="point"):
         """Where do the joints stand in these clouds?  Fit the robot's joint values, and its base pose when ``fit_base``, to one
         cloud of world points per pose, starting from q0 (P,J) in ``robot.fk_table()``'s order and ``base0`` (this environment's
-        base when None): ``compute_joints.fit_cloud_poses``, which states the algorithm, its settings and the returned dict."""
+        base when None): ``compute_joints.fit_cloud_poses``, which states the algorithm, its settings and the returned dict.
+        ``metric="feature"`` takes the curvature of the matched vertex, edge or face instead of the point-to-point one."""
         from .compute_joints import fit_cloud_poses
         return fit_cloud_poses(self.robot, clouds, q0, self.base if base0 is None else base0, d_max=d_max, max_iter=max_iter,
-                               fit_base=fit_base, lock=lock, lam0=lam0, tol=tol)
+                               fit_base=fit_base, lock=lock, lam0=lam0, tol=tol, metric=metric)
 
     def refine_joints(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lock_frames=(), lam0=1e-3,
-                      tol=1e-10):
+                      tol=1e-10, metric="point"):
         """Where do the joint axes and origins lie in these clouds?  Refine the frames of the robot's movable joints, shared by
-        all poses, together with every pose's joint values and base pose (``fit_pose``'s arguments; ``lock_frames`` names the
+        all poses, together with every pose's joint values and base pose (``fit_pose``'s arguments, ``metric`` included; ``lock_frames`` names the
         joints whose frame stays): ``compute_joints.refine_joint_frames``, which states the algorithm and the returned dict.
         The environment's robot is not changed; ``compute_joints.set_joint_frames`` writes the result's "frames" into a URDF."""
         from .compute_joints import refine_joint_frames
         return refine_joint_frames(self.robot, clouds, q0, self.base if base0 is None else base0, d_max=d_max, max_iter=max_iter,
-                                   fit_base=fit_base, lock=lock, lock_frames=lock_frames, lam0=lam0, tol=tol)
+                                   fit_base=fit_base, lock=lock, lock_frames=lock_frames, lam0=lam0, tol=tol, metric=metric)
 
     def self_collision_check(self, joint_positions, link_T=None, use_excluded=False, margin=0.0, containment=False):
         """(self_contact, floor_contact) of one pose, the reference's return pair (sim_data.py:200-208); see ``collisions``.

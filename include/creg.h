@@ -922,6 +922,48 @@ int creg_link_moments_f64(const double* tri, const int64_t* tri_start, int64_t n
                           size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Feature moments: the link moments above and, beside them, per pose and link the 21 sums of the curvature of the matched
+ * feature.  Half the squared distance from a point to a flat feature -- a vertex, the line of an edge, the plane of a face -- has
+ * an exact Hessian, the projector Pi onto the feature's normal space: I, I - t t^T (t the unit edge direction), n n^T (n the unit
+ * normal).  Pi r = r, so the gradient sum J^T r and the cost are those of the link moments; only the curvature sum J^T Pi J differs
+ * from the point-to-point sum J^T J, and restricted to the points of one link it is the 6 x 6 matrix M6 = sum A^T Pi A between the
+ * twists (Omega, V): H[a][b] = sum_l (Omega_a | V_a)^T M6 (Omega_b | V_b).  The reference has no such step; this contract is the
+ * project's own.
+ *   inputs     exactly those of creg_link_moments_f64.
+ *   contributes, residual   word for word those of the link-moments entry; which = the case pt_tri_vec returned for the row (1, 2, 3
+ *              vertex a, b, c; 4, 5, 6 edge ab, ac, bc; 7 the face), (a, b, c) the posed vertices it was computed from.
+ *   projector  of a contributing row, single operations with + - * / only (no square root), no contraction, dot and x as above:
+ *                which 1..3   Pi = I (1.0 on the diagonal, 0.0 off it)
+ *                which 4..6   e = b - a, c - a, c - b per component; ee = dot(e, e);
+ *                             Pi_ij = delta_ij - (e_i*e_j)/ee  with delta_ij = 1.0 or 0.0, when ee > 0, else Pi = I
+ *                which 7      N = (b - a) x (c - a); NN = dot(N, N);  Pi_ij = (N_i*N_j)/NN when NN > 0, else Pi = I
+ *              (i <= j computed, Pi_ji = Pi_ij: the products commute bit for bit).  A zero-area triangle takes the guards.
+ *   columns    d_k = c_k - ref[p,l][k] as in the link moments.  The six twist columns, as 3-vectors with their zeros:
+ *                A_0 = (0, -d_z, d_y), A_1 = (d_z, 0, -d_x), A_2 = (-d_y, d_x, 0)   (e_k x d),   A_3, A_4, A_5 = e_0, e_1, e_2
+ *              B_k[i] = dot(Pi_i, A_k) for Pi_i = (Pi_i0, Pi_i1, Pi_i2), every product and sum carried out, the zeros included.
+ *   terms      0..15 the link-moments terms in that order; 16..36 the upper triangle of M6, row-major over a <= b
+ *              ((0,0) (0,1) .. (0,5) (1,1) .. (5,5)): dot(A_a, B_b), again with the zeros; 37 the count's 1.0.
+ *   outputs    mom (n_poses,n_links,16) fp64 and cnt (n_poses,n_links) int64: the contract, the order and the bits of
+ *              creg_link_moments_f64.  fmom (n_poses,n_links,21) fp64: the 21 sums over the contributing rows of (p, l).  Every
+ *              (p, l) is written, with zeros where nothing contributes.
+ *   order      that of the link moments: tiles of 64 rows from the pose's first row; within a tile every sum of (p, l) starts
+ *              from 0.0 and runs over the tile's rows in ascending order, the rows that do not contribute to (p, l) skipped; the
+ *              tiles' partials in ascending tile order into four running sums, tile t into sum t mod 4, the result
+ *              (s0 + s1) + (s2 + s3).
+ * Determinism: no floating-point atomics.  Two runs give the same bits, a pose alone in a call gives the bits it has among
+ * others, and the result of (p, l) does not depend on the rows of other links in the same tiles.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, n_pts < 0 or >= 2^31,
+ * (n_pts >> 6) + n_poses >= 2^31, n_poses * n_links * 38 >= 2^39, a null tri (with n_tri > 0), tri_start, link_T, pt_start, ref,
+ * mom, cnt, fmom or workspace, a null pts or tri_idx with n_pts > 0, a NaN or negative d_max, a workspace smaller than
+ * creg_feature_moments_workspace_bytes(n_poses, n_pts, n_links) (38 doubles per tile slot and link; 0 for the counts refused
+ * here). */
+size_t creg_feature_moments_workspace_bytes(int64_t n_poses, int64_t n_pts, int32_t n_links);
+int creg_feature_moments_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                             int64_t n_poses, const double* pts, const int64_t* pt_start, int64_t n_pts, double d_max,
+                             const int32_t* tri_idx, const double* ref, double* mom, int64_t* cnt, double* fmom, void* workspace,
+                             size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Containment:is a link wholly inside another?  For every listed link pair of every pose, in both directions and in one
  * call, the generalized winding number of one link's posed triangle mesh at a few points of the other.  It closes the hole the
  * two entries above share (no edge pierces a face when a mesh lies wholly inside another); the reference rejects such a pose
