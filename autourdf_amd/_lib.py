@@ -93,6 +93,8 @@ SIGNATURES = {
     "creg_mesh_clearance_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, i64, f64, vp, vp, vp, vp, sz, vp]),
     "creg_point_mesh_workspace_bytes": (sz, [i64, i32, i64, i64]),
     "creg_point_mesh_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, f64, vp, vp, vp, vp, sz, vp]),
+    "creg_mesh_cover_workspace_bytes": (sz, [i64, i32, i64, i64]),
+    "creg_mesh_cover_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, vp, i64, f64, vp, vp, vp, vp, vp, sz, vp]),
     "creg_pose_fit_workspace_bytes": (sz, [i64, i64, i32]),
     "creg_pose_fit_system_f64": (ctypes.c_int, [vp, vp, i64, vp, i32, i64, vp, vp, i64, f64, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp,
                                                 vp, vp, vp, sz, vp]),

@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libcreg.so")
-SOURCES = ["core.hip", "nn_l1.hip", "transform.hip", "se3.hip", "kmeans.hip", "group.hip", "icp.hip", "icp_small.hip", "icp_large.hip", "kabsch.hip", "fps.hip", "coord_map.hip", "sample.hip", "kmeans_nd.hip", "normals.hip", "train_engine.hip", "train_setup.hip", "train_forward.hip", "train_nn.hip", "train_backward.hip", "urdf.hip", "joints.hip", "joint_types.hip", "joint_motion.hip", "mesh.hip", "fk.hip", "depth.hip", "mesh_pose.hip", "collide.hip", "clearance.hip", "point_mesh.hip", "pose_fit.hip", "link_moments.hip", "feature_moments.hip", "inertia.hip", "contain.hip", "hull.hip"]
+SOURCES = ["core.hip", "nn_l1.hip", "transform.hip", "se3.hip", "kmeans.hip", "group.hip", "icp.hip", "icp_small.hip", "icp_large.hip", "kabsch.hip", "fps.hip", "coord_map.hip", "sample.hip", "kmeans_nd.hip", "normals.hip", "train_engine.hip", "train_setup.hip", "train_forward.hip", "train_nn.hip", "train_backward.hip", "urdf.hip", "joints.hip", "joint_types.hip", "joint_motion.hip", "mesh.hip", "fk.hip", "depth.hip", "mesh_pose.hip", "collide.hip", "clearance.hip", "point_mesh.hip", "mesh_cover.hip", "pose_fit.hip", "link_moments.hip", "feature_moments.hip", "inertia.hip", "contain.hip", "hull.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-function",
          # MFMA accumulators in VGPRs: the default AGPR form costs 8 v_accvgpr_read per fp64 16x16x4 MFMA whose

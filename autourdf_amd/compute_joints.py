@@ -15,7 +15,8 @@ scope.  No CPU fallback.
 This project's own, beyond the reference: ``estimate_typed_joints_from_tree`` also tells prismatic and fixed joints
 (``creg_joint_types_f64``), and ``estimate_joint_motion``, ``set_joint_limits`` and ``replay_urdf`` recover every joint's
 positions, write the observed limits and check the written file against the registration; ``cloud_fit_poses`` and
-``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``); ``fit_cloud_poses`` and ``fit_positions``
+``cloud_fit`` check its meshes against the raw clouds (``ops.point_mesh_distance``), ``surface_cover_poses`` and ``cloud_cover``
+the raw clouds against its meshes (``ops.mesh_cover``: surface no point lies near); ``fit_cloud_poses`` and ``fit_positions``
 fit the joint positions and the base pose to clouds (``ops.pose_fit_system``, Levenberg-Marquardt); ``refine_joint_frames``,
 ``set_joint_frames`` and ``refine_urdf_joints`` refine the joint frames themselves against the clouds, a bundle adjustment on
 ``ops.link_moments`` (``link_twists``, ``twist_system``), and write them into a copy of the URDF.
@@ -483,7 +484,8 @@ def cloud_fit_poses(robot, link_T, clouds, d_max=np.inf):
     "links", one dict per link with link (name), n (finite points whose nearest triangle is the link's) and rms; "all", the
     pose figures over every point (max_at a (pose, row) pair); and "dist" / "link", lists of P host arrays with every point's
     distance and link index (-1 where no triangle was within ``d_max``).  No threshold turns a figure into a verdict.  Not seen
-    from this side: mesh surface that no point lies near, and a wrong link that happens to lie on the right surface."""
+    from this side: mesh surface that no point lies near (``surface_cover_poses`` measures that direction), and a wrong link
+    that happens to lie on the right surface."""
     dev = link_T.device
     if link_T.dim() == 3:
         link_T = link_T[None]
@@ -567,6 +569,136 @@ def cloud_fit(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps
             fig["max_at"] = (int(start_step + k), int(fig["max_at"] - cut[k]))
         fit["sequences"].append(fig)
     return fit
+
+
+def subdivide_mesh(tri, tri_start, max_edge):
+    """Split every triangle with an edge longer than ``max_edge`` into four at its edge midpoints, until none is left (host
+    numpy): tri (F,3,3), tri_start (L+1) -> (tri (F',3,3) f64, tri_start (L+1) int64, parent_row (F') int64 the input row every
+    output row is a part of).  A triangle's parts take its place, so the rows stay grouped by link and in the input's order; the
+    surface and its area are unchanged, and a mesh already fine comes back as it was.  ``mesh_cover`` counts a triangle as
+    covered when a point is near any part of it, so the triangle is the resolution of that measurement: a mesh with triangles
+    larger than the points' spacing is subdivided first (``surface_cover_poses(..., max_edge=...)``)."""
+    tri = np.array(tri, np.float64).reshape(-1, 3, 3)
+    tri_start = np.asarray(tri_start, np.int64)
+    max_edge = float(max_edge)
+    if not max_edge > 0.0:
+        raise ValueError(f"subdivide_mesh: max_edge must be > 0, got {max_edge}")
+    if not np.isfinite(tri).all():
+        raise ValueError("subdivide_mesh: the triangles must be finite")
+    parent = np.arange(len(tri), dtype=np.int64)
+    while True:
+        a, b, c = tri[:, 0], tri[:, 1], tri[:, 2]
+        longest = np.maximum(np.maximum(np.linalg.norm(b - a, axis=1), np.linalg.norm(c - b, axis=1)), np.linalg.norm(a - c, axis=1))
+        split = longest > max_edge
+        if not split.any():
+            break
+        count = np.where(split, 4, 1)
+        at = np.cumsum(count) - count                                          # the first output row of every input row
+        src = np.repeat(np.arange(len(tri)), count)
+        out, parent = tri[src], parent[src]
+        s = np.flatnonzero(split)
+        a, b, c = a[s], b[s], c[s]
+        ab, bc, ca = (a + b) * 0.5, (b + c) * 0.5, (c + a) * 0.5
+        for k, part in enumerate(((a, ab, ca), (ab, b, bc), (ca, bc, c), (ab, bc, ca))):
+            out[at[s] + k] = np.stack(part, 1)
+        tri = out
+    owner = np.searchsorted(tri_start, parent, side="right") - 1
+    return tri, np.searchsorted(owner, np.arange(len(tri_start)), side="left").astype(np.int64), parent
+
+
+def _cover_figures(area, dist, n_near):
+    """The figures of one set of poses: area (F) per triangle, dist and n_near (p,F) -> area (of the mesh, one pose), uncovered
+    (area share of the triangles with dist = inf, over all p poses), mean, rms, p95 and max over the covered triangles weighted
+    by area (p95: the smallest distance at which the covered area at or below it reaches 95 %), max_at ((pose, row), the first
+    such) and thin (area share of the triangles covered with n_near == 1)."""
+    area, dist, n_near = np.asarray(area, np.float64), np.asarray(dist, np.float64), np.asarray(n_near)
+    w = np.broadcast_to(area, dist.shape)
+    ok = np.isfinite(dist)
+    total = float(w.sum())
+    share = lambda mask: float(w[mask].sum() / total) if total > 0 else float("nan")
+    out = {"area": float(area.sum()), "uncovered": share(~ok), "thin": share(ok & (n_near == 1))}
+    wk, d = w[ok], dist[ok]
+    if wk.sum() > 0:
+        order = np.argsort(d, kind="stable")
+        cum = np.cumsum(wk[order])
+        k = min(int(np.searchsorted(cum, 0.95 * cum[-1], side="left")), len(order) - 1)
+        flat = int(np.flatnonzero(ok.reshape(-1))[np.argmax(d)])
+        out.update(mean=float((wk * d).sum() / wk.sum()), rms=float(np.sqrt((wk * d * d).sum() / wk.sum())), p95=float(d[order[k]]),
+                   max=float(d.max()), max_at=(flat // dist.shape[1], flat % dist.shape[1]))
+    else:
+        out.update(mean=float("nan"), rms=float("nan"), p95=float("nan"), max=float("nan"), max_at=None)
+    return out
+
+
+def surface_cover_poses(robot, link_T, clouds, d_max=np.inf, max_edge=None):
+    """How much of a robot's mesh surface, posed by ``link_T``, has a point of its pose's cloud near it (this project's own): the
+    other direction of ``cloud_fit_poses``, with its arguments; it sees a link posed where no cloud is, a link that exists twice
+    and a bloated mesh, which leave every cloud point explained.  ONE ``ops.mesh_cover`` call for all poses.  With ``max_edge`` the
+    meshes are subdivided first (``subdivide_mesh``): a triangle counts as covered when a point is within ``d_max`` of any part of
+    it.  All shares are shares of area (link-frame areas; poses are rigid).  Returns a dict:
+    "poses", one dict per pose with area, uncovered (area share of the triangles farther than ``d_max`` from every point; their
+    distance is ``inf``), mean, rms, p95 and max of the distance over the covered triangles, weighted by area, max_at (the
+    triangle's row) and thin (area share of the triangles covered by exactly one point within ``d_max``);
+    "links", one dict per link with link (name), area, uncovered (over all poses), rms, and never, the area share of its
+    triangles covered in NO pose -- the figure that survives a surface being out of a frame's sight;
+    "all", the pose figures over every pose (max_at a (pose, row) pair) and never;
+    "dist" and "n_near" (P,F) and "seen" (F: covered in some pose) as host arrays, "area" (F) and "tri_start" (L+1) of the mesh
+    that was measured, and "parent_row" (F) when it was subdivided.  No threshold turns a figure into a verdict.  Not seen from
+    this side either: which camera could have seen a surface; a surface none ever sees counts as uncovered."""
+    dev = link_T.device
+    if link_T.dim() == 3:
+        link_T = link_T[None]
+    if len(clouds) != link_T.shape[0]:
+        raise ValueError(f"surface_cover_poses: {link_T.shape[0]} poses need as many clouds, got {len(clouds)}")
+    tri, tri_start, parent = np.ascontiguousarray(robot.tri, np.float64).reshape(-1, 3, 3), np.asarray(robot.tri_start, np.int64), None
+    if max_edge is not None:
+        tri, tri_start, parent = subdivide_mesh(tri, tri_start, max_edge)
+    parts = [torch.as_tensor(c, dtype=torch.float64).reshape(-1, 3).to(dev) for c in clouds]
+    cut = np.concatenate([[0], np.cumsum([p.shape[0] for p in parts])]).astype(np.int64)
+    pts = torch.cat(parts) if parts else torch.zeros(0, 3, dtype=torch.float64, device=dev)
+    dist, _, n_near = ops.mesh_cover(torch.as_tensor(tri, device=dev), torch.as_tensor(tri_start, device=dev), link_T, pts,
+                                     torch.as_tensor(cut, device=dev), d_max)
+    dist, n_near = dist.cpu().numpy(), n_near.cpu().numpy()
+    area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
+    seen = np.isfinite(dist).any(0)
+    never = lambda rows: float(area[rows][~seen[rows]].sum() / area[rows].sum()) if area[rows].sum() > 0 else float("nan")
+    poses = []
+    for p in range(dist.shape[0]):
+        fig = _cover_figures(area, dist[p:p + 1], n_near[p:p + 1])
+        fig["max_at"] = None if fig["max_at"] is None else fig["max_at"][1]
+        poses.append(fig)
+    per_link = []
+    for l, name in enumerate(robot.links):
+        rows = slice(int(tri_start[l]), int(tri_start[l + 1]))
+        fig = _cover_figures(area[rows], dist[:, rows], n_near[:, rows])
+        per_link.append({"link": name, "area": fig["area"], "uncovered": fig["uncovered"], "rms": fig["rms"], "never": never(rows)})
+    overall = dict(_cover_figures(area, dist, n_near), never=never(slice(0, len(area))))
+    out = {"poses": poses, "links": per_link, "all": overall, "dist": dist, "n_near": n_near, "seen": seen, "area": area,
+           "tri_start": tri_start}
+    if parent is not None:
+        out["parent_row"] = parent
+    return out
+
+
+def cloud_cover(urdf_file, links, motion, cm_list, raw_dirs, start_step, num_steps, time_step=0, d_max=np.inf):
+    """The other direction of ``cloud_fit`` (this project's own): how much of the written URDF's mesh surface, at the poses of
+    ``cloud_fit_link_poses``, has a point of that step's raw cloud within ``d_max`` -- the clouds ``cloud_fit`` reads, in one
+    ``surface_cover_poses`` call, whose dict is returned with "sequences" added: the pose figures over each sequence's poses
+    (max_at a (step, row) pair).  Pose s * num_steps + k is step ``start_step + k`` of sequence s.  The meshes this project writes
+    have triangles no larger than a voxel and are measured as they are."""
+    from .cluster_icp import read_point_cloud
+    robot, link_T = cloud_fit_link_poses(urdf_file, links, motion, cm_list, start_step, num_steps, time_step)
+    S, n = len(cm_list), int(num_steps)
+    clouds = [np.asarray(read_point_cloud(os.path.join(raw_dirs[s], f"{start_step + k:04}", "robot.ply")).points, np.float64)
+              for s in range(S) for k in range(n)]
+    cover = surface_cover_poses(robot, link_T, clouds, d_max)
+    cover["sequences"] = []
+    for s in range(S):
+        fig = _cover_figures(cover["area"], cover["dist"][s * n:(s + 1) * n], cover["n_near"][s * n:(s + 1) * n])
+        if fig["max_at"] is not None:
+            fig["max_at"] = (int(start_step + fig["max_at"][0]), int(fig["max_at"][1]))
+        cover["sequences"].append(fig)
+    return cover
 
 
 FIT_METRICS = ("point", "feature")                                              # the curvature of the two Levenberg-Marquardt drivers

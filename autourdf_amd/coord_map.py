@@ -400,7 +400,9 @@ def _cli_parser():
     raw clouds after the cloud fit and writes <name>.refined.urdf and <name>.refined_positions.npy; --refine_iters (default
     30) caps its iterations.  --refine_joints without --cloud_fit, and --refine_iters without --refine_joints, are usage
     errors.  --fit_metric {point,feature} chooses the curvature of both fits (``compute_joints.fit_cloud_poses``); without
-    --fit_positions or --refine_joints it is a usage error."""
+    --fit_positions or --refine_joints it is a usage error.  --coverage measures the other direction after the cloud fit --
+    how much of the posed mesh surface has a raw point within --fit_max -- and adds a "coverage" block to
+    <name>.cloud_fit.json; --coverage without --cloud_fit is a usage error."""
     parser = _parser()
     parser.add_argument('--voxel_size', type=float, default=None)
     parser.add_argument('--density', type=float, default=None)
@@ -417,6 +419,7 @@ def _cli_parser():
     parser.add_argument('--refine_joints', action='store_true')
     parser.add_argument('--refine_iters', type=int, default=None)
     parser.add_argument('--fit_metric', choices=('point', 'feature'), default=None)
+    parser.add_argument('--coverage', action='store_true')
     parse = parser.parse_args
 
     def parse_args(args=None, namespace=None):
@@ -443,6 +446,8 @@ def _cli_parser():
             parser.error("--refine_iters needs --refine_joints")
         if ns.fit_metric is not None and not (ns.fit_positions or ns.refine_joints):
             parser.error("--fit_metric needs --fit_positions or --refine_joints: it is the curvature of their steps")
+        if ns.coverage and not ns.cloud_fit:
+            parser.error("--coverage needs --cloud_fit: it measures the other direction at the poses and clouds of the cloud fit")
         return ns
     parser.parse_args = parse_args
     return parser
@@ -476,7 +481,7 @@ def _joint_motion_report(urdf_path, motion, replay, pad_deg, start_step):
               f"pos_max {w['pos_max']:.3g} at {w['pos_max_at']}")
 
 
-def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None, refined=None):
+def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names, fitted=None, refined=None, coverage=None):
     """Write <name>.cloud_fit.json next to the URDF -- the per-frame, per-sequence, per-link and overall figures of
     ``cloud_fit``, without the per-point arrays -- and print one line per sequence (rms, p95, unexplained share) and the worst
     frame.  ``fit_max`` is written as null when it is inf.  A ``fitted`` or ``refined`` dict that carries a "metric" (the
@@ -487,7 +492,10 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
     joint_positions.npy, and one line per sequence and one per joint are printed.  With ``refined`` (``refine_urdf_joints``'
     dict, "urdf" naming the file it wrote) the file gains a "refined" block -- the overall rms before and after, the steps tried,
     per joint the angle between the old and the new axis, the distance of the old joint point from the new line and the largest
-    |q - q_registered| --, <name>.refined_positions.npy (J,S,steps) is written, and one line per joint is printed."""
+    |q - q_registered| --, <name>.refined_positions.npy (J,S,steps) is written, and one line per joint is printed.  With
+    ``coverage`` (``cloud_cover``'s dict) the file gains a "coverage" block -- per frame, per sequence, per link and overall the
+    figures of ``surface_cover_poses``, without the arrays --, and one line per sequence (uncovered share, rms) and one per link
+    (uncovered, never) are printed."""
     import json
     stem = urdf_path[:-len('.urdf')] if urdf_path.endswith('.urdf') else urdf_path
     clean = lambda d: {k: (None if isinstance(v, float) and not np.isfinite(v) else v) for k, v in d.items()}
@@ -518,6 +526,11 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
                              "joints": [clean(dict(j)) for j in refined["joints"]]}
         if "metric" in refined:
             report["refined"]["metric"] = refined["metric"]
+    if coverage is not None:
+        report["coverage"] = {
+            "all": clean(coverage["all"]), "sequences": [clean(s) for s in coverage["sequences"]],
+            "links": [clean(l) for l in coverage["links"]],
+            "frames": [dict(clean(f), sequence=i // num_steps, step=start_step + i % num_steps) for i, f in enumerate(coverage["poses"])]}
     with open(stem + '.cloud_fit.json', 'w') as f:
         json.dump(report, f, indent=1)
     for name, s in zip(seq_names, fit["sequences"]):
@@ -538,6 +551,11 @@ def _cloud_fit_report(urdf_path, fit, fit_max, start_step, num_steps, seq_names,
             line = "no line" if j["line_distance"] is None else f"old point {j['line_distance']:.3g} from the new line"
             print(f"refine_joints {j['joint']}: axis turned by {j['axis_angle']:.3g} rad, {line}, "
                   f"largest |q - q_registered| {j['max_shift']:.3g}")
+    if coverage is not None:
+        for name, s in zip(seq_names, coverage["sequences"]):
+            print(f"coverage {name}: uncovered {s['uncovered']:.2%} of the surface, rms {s['rms']:.3g}")
+        for l in coverage["links"]:
+            print(f"coverage {l['link']}: uncovered {l['uncovered']:.2%}, never covered {l['never']:.2%}")
 
 
 def main(argv=None):
@@ -578,13 +596,16 @@ def main(argv=None):
     keeps every byte.  It needs the cloud fit, and a ``refine_iters`` needs it: ValueError before anything is written
     otherwise.  ``--fit_metric`` (or a ``fit_metric`` key, "point" or "feature"; the option wins) is the ``metric`` of both fits
     and is written into their blocks of ``cloud_fit.json``; without it nothing changes, and without ``fit_positions`` or
-    ``refine_joints`` it is a ValueError before anything is written."""
+    ``refine_joints`` it is a ValueError before anything is written.  With ``--coverage`` (or a boolean ``coverage`` key; the
+    option wins) the other direction is measured after the cloud fit (``cloud_cover``: one ``ops.mesh_cover`` call, ``fit_max`` as
+    its ``d_max``): ``cloud_fit.json`` gains a "coverage" block and one line per sequence and per link is printed.  It needs the
+    cloud fit: ValueError before anything is written otherwise.  Without it no such launch is made and every written byte stays."""
     import json
     import os
 
     from . import prefer_device_kernargs
     prefer_device_kernargs()                    # (the command-line entry point: before the first device call)
-    from .compute_joints import (cloud_fit, create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
+    from .compute_joints import (cloud_cover, cloud_fit, create_urdf, estimate_joint_axes_from_tree, estimate_joint_motion,
                                  estimate_typed_joints_from_tree, fit_positions, refine_urdf_joints, replay_urdf, set_collision_meshes,
                                  set_inertials, set_joint_limits)
     from .link import link_inertia, link_mesh, refine_links_clusters, save_links, visualize_links
@@ -665,6 +686,10 @@ def main(argv=None):
     if fit_metric not in (None, "point", "feature"):
         raise ValueError(f"fit_metric must be 'point' or 'feature', got {fit_metric!r}")
     metric = {} if fit_metric is None else {"metric": fit_metric}
+    want_cover = bool(args.coverage or robot_params.get('coverage'))
+    if want_cover and not want_fit:
+        raise ValueError("coverage measures the other direction at the poses and clouds of the cloud fit: give --cloud_fit (or a "
+                         "cloud_fit key in parameters.json) with --coverage")
     ROBOT, NUM_SEG = args.robot, robot_params['num_seg']
     STEP, CAMS, START, END = args.step_size, args.num_cameras, args.start_steps, args.end_steps
     part_path = f'data/part/{ROBOT}_{NUM_SEG}_seg/{STEP}_deg_{CAMS}_cams/'
@@ -754,8 +779,11 @@ def main(argv=None):
                                              refined_path, d_max=fit_max, max_iter=refine_iters, **metric)
                 refined.update(metric)
                 refined["urdf"] = refined_path
+            cover = None
+            if want_cover:
+                cover = cloud_cover(urdf_path, links, motion, cm_list, sub_raw_path[:len(cm_list)], START, END - START, d_max=fit_max)
             _cloud_fit_report(urdf_path, fit, fit_max, START, END - START, [p.rstrip('/').split('/')[-1] for p in sub_raw_path], fitted,
-                              refined)
+                              refined, cover)
     return urdf_path
 
 

@@ -222,6 +222,38 @@ def point_mesh_distance(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"
     return (dist, tri_idx, link) + ((boxes,) if want_boxes else ())
 
 
+def mesh_cover(tri, tri_start, link_T, pts, pt_start, d_max=float("inf"), sort: bool = True, want_boxes: bool = False):
+    """The other direction of ``point_mesh_distance`` (creg_mesh_cover_f64; the contract is in include/creg.h): the same inputs
+    -> dist (P,F) f64, the distance from every posed triangle to its pose's points, ``+inf`` where it exceeds ``d_max`` (no
+    point within ``d_max`` by the box test, or a found minimum above it: surface no point lies near), pt_idx (P,F) int32 the
+    row of pts that attains the kernel's minimum (the smallest on equal bits) or -1 where no point was within ``d_max`` by the
+    box test, n_near (P,F) int32 the number of the pose's points within ``d_max`` of the triangle, and link_box (P,L,6) when
+    ``want_boxes``.  One call for all poses.
+    ``sort=True`` hands the kernel every pose's points in Morton order with their own rows as labels, so that a tile of 64
+    points is compact and the kernel's box cull bites; the outputs are a function of the set of (point, row) pairs, so no bit
+    of any output changes.
+    ValueError before any launch: ``point_mesh_distance``'s."""
+    L = _lib.load()
+    d_max, tri, tri_start, link_T, pts, pt_start, F, P, n_links, N, dev = _point_query_args(
+        "mesh_cover", tri, tri_start, link_T, pts, pt_start, d_max)
+    if not bool(_device_offsets_ok(tri_start, F) & _device_offsets_ok(pt_start, N)):
+        raise ValueError(f"mesh_cover: tri_start must run from 0 to {F} and pt_start from 0 to {N} without decreasing")
+    order = _morton_order(pts, pt_start, P) if sort and N else None
+    dist2 = torch.empty(P, F, dtype=torch.float64, device=dev)
+    pt_idx = torch.empty(P, F, dtype=torch.int32, device=dev)
+    n_near = torch.empty(P, F, dtype=torch.int32, device=dev)
+    boxes = torch.empty(P, n_links, 6, dtype=torch.float64, device=dev) if want_boxes else None
+    ws_bytes = L.creg_mesh_cover_workspace_bytes(F, n_links, P, N)
+    ws = _workspace(dev, ws_bytes)
+    sent = pts if order is None else pts[order].contiguous()
+    rows = None if order is None else order.to(torch.int32)
+    _lib.check(L.creg_mesh_cover_f64(_p(tri) if F else None, _p(tri_start), F, _p(link_T), n_links, P, _p(sent) if N else None,
+                                     _p(pt_start), _p(rows), N, d_max, _p(dist2) if F else None, _p(pt_idx) if F else None,
+                                     _p(n_near) if F else None, _p(boxes), _p(ws), ws_bytes, _stream()), "creg_mesh_cover_f64")
+    dist = torch.where(dist2 > d_max * d_max, torch.full_like(dist2, float("inf")), torch.sqrt(dist2))
+    return (dist, pt_idx, n_near) + ((boxes,) if want_boxes else ())
+
+
 def pose_fit_system(tri, tri_start, link_T, pts, pt_start, tri_idx, table, center, d_max=float("inf")):
     """The Gauss-Newton system of fitting a robot's base pose and joint values to clouds (creg_pose_fit_system_f64; the contract
     is in include/creg.h): tri, tri_start, link_T, pts, pt_start and ``d_max`` as ``point_mesh_distance`` takes them, tri_idx (N)

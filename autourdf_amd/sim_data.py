@@ -748,7 +748,7 @@ class SimEnv:
         arrays or device tensors).  Returns (dist, tri, link), each a list with one host array per pose: the distance of every
         point from the posed meshes (``inf`` beyond ``d_max``), the row of ``robot.tri`` that attains it and the index in
         ``robot.links`` of the link that owns that row (-1 where no triangle was within ``d_max``): a part segmentation of the
-        cloud.  The other direction -- mesh surface that no point lies near -- is not measured."""
+        cloud.  The other direction -- mesh surface that no point lies near -- is ``surface_coverage``'s."""
         tri = self._device_mesh()[0]
         if link_T.dim() == 3:
             link_T = link_T[None]
@@ -760,6 +760,15 @@ class SimEnv:
         tri_start = self._collide_inputs(False)[2]
         out = ops.point_mesh_distance(tri, tri_start, link_T, pts, torch.as_tensor(cut, device=tri.device), d_max)
         return tuple([a[cut[p]:cut[p + 1]] for p in range(len(parts))] for a in (o.cpu().numpy() for o in out))
+
+    def surface_coverage(self, link_T, clouds, d_max=np.inf, max_edge=None):
+        """How much of the robot's mesh surface at P poses has a point of that pose's cloud within ``d_max``, in one launch
+        (creg_mesh_cover_f64): ``surface_distance``'s arguments, and ``max_edge`` to subdivide the meshes first (a triangle is the
+        resolution of the measurement).  ``compute_joints.surface_cover_poses``, which states the returned dict: per pose, per
+        link and overall the uncovered share of area and the distance figures, and per link ``never``, the share covered in no
+        pose.  The environment's ground is not part of the measurement."""
+        from .compute_joints import surface_cover_poses
+        return surface_cover_poses(self.robot, link_T, clouds, d_max, max_edge)
 
     def fit_pose(self, clouds, q0, base0=None, d_max=np.inf, max_iter=30, fit_base=True, lock=(), lam0=1e-3, tol=1e-10, metric="point"):
         """Where do the joints stand in these clouds?  Fit the robot's joint values, and its base pose when ``fit_base``, to one

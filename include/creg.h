@@ -826,6 +826,57 @@ int creg_point_mesh_f64(const double* tri, const int64_t* tri_start, int64_t n_t
                         int32_t* tri_idx, double* link_box, void* workspace, size_t workspace_bytes, creg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Mesh cover: the transposed reduction of point-to-mesh distance.  For every posed triangle of every pose, in one call, the minimum
+ * squared distance to the pose's points, the point that attains it and the number of points within d_max.  It sees what the other
+ * direction cannot: mesh surface that no point lies near (a link posed where no cloud is, a link that exists twice, a bloated
+ * mesh).  The reference has no such step; this contract is the project's own.
+ *   inputs     tri, tri_start (with its clamping), n_tri, link_T, n_links, n_poses, pts, pt_start (with its clamping), n_pts, d_max
+ *              and link_box are exactly those of creg_point_mesh_f64: the same posed vertices w_i in the same operation order, the
+ *              same exact min / max boxes.  pt_row (n_pts) int32 may be NULL.
+ *   live, box gap, contributes, d2(i, f)   word for word those of creg_point_mesh_f64: a point is live iff none of its coordinates
+ *              is NaN; triangle f of pose p contributes to live point i of pose p iff gap2(p_i, box_f) <= d_max*d_max;
+ *              d2(i, f) = pt_tri2(p_i; a, b, c) with its seven cases, no contraction, no square root.  The matrix d2 is the same;
+ *              creg_point_mesh_f64 takes its minimum over the triangles for every point, this entry over the points for every
+ *              triangle.
+ *   label      label(i) = pt_row ? pt_row[i] : (int32) i.  A caller that reorders the points of a pose passes each point's own row
+ *              here.  Labels are read, not checked; those of the live points of one pose are expected distinct and >= 0.
+ *   outputs    (n_poses, n_tri), row-major.  For row f of pose p that some link owns: best = +inf, idx = -1, near = 0; then for
+ *              every live point i of pose p to which f contributes, in any order,
+ *                replace (best, idx) by (d2, label(i))  iff  d2 < best || (d2 == best && idx >= 0 && label(i) < idx)
+ *                near += (d2 < +inf && d2 <= d_max*d_max)
+ *              So
+ *              dist2 fp64: the minimum of d2 over the points to which f contributes, +inf when there is none;
+ *              pt_idx int32: the smallest label among the points whose d2 has exactly the bits of that minimum, or -1;
+ *              n_near int32 (may be NULL): the number of points to which f contributes whose d2 is at most d_max*d_max, the
+ *              triangle's support (with d_max = +inf: the pose's points with a finite d2).
+ *              (A d2 that is not below +inf -- a point with an infinite coordinate -- replaces nothing and is not counted.)
+ *              The replacement is the lexicographic minimum over (d2, label), which no order of the walk changes.
+ *              link_box as in creg_mesh_collide_f64; may be NULL.
+ *              A row of tri that no link owns is not written.  n_pts == 0 writes +inf / -1 / 0 to every owned row and fills
+ *              link_box.  tri_start is expected to run 0 .. n_tri without decreasing; with another one nothing outside the arrays
+ *              is touched, and which rows count as owned is not defined.
+ * A value above d_max*d_max can appear: the box gap was small and the point farther away; callers read it as "beyond d_max".  If a
+ * triangle's true distance to the pose's points is at most d_max, the point that attains it contributes.  Nothing is pruned by a
+ * running best: d_max is the cull.
+ * Culling: by the monotonicity stated in the clearance contract, culling with the box-box gap2 and the same d_max*d_max by the
+ * union box of a tile of 64 live points against the 256-triangle chunk box (a chunk box lies inside its link's box, so a test
+ * against the link box skips nothing more) drops no contributing pair: culling changes no output.
+ * Determinism: no atomics, floating-point or integer.  The outputs of a pose are a function of its set of (point, label) pairs and
+ * of its posed mesh alone: they do not depend on the order of pts, on the other poses of the call, or on scheduling; two runs give
+ * the same bits.
+ * CREG_EINVAL, nothing launched: n_poses < 1, n_links < 1 or > 65535, n_tri < 0 or >= 2^31, n_pts < 0 or >= 2^31,
+ * (n_pts >> 6) + n_poses >= 2^31, n_poses * n_tri > 2^56 (the (pose, row) offsets are 64-bit, and 72 bytes of posed vertices per
+ * row must stay inside 64 bits too), a null tri (with n_tri > 0), tri_start, link_T, pt_start or workspace, a null pts with
+ * n_pts > 0, a null dist2 or pt_idx with n_tri > 0, a NaN or negative d_max, a workspace smaller than
+ * creg_mesh_cover_workspace_bytes(...): the posing stage's posed vertices, chunk and link boxes, then 48 bytes (one box) per
+ * point-tile slot, (n_pts >> 6) + n_poses slots; 0 for the counts refused here.  Poses are worked in slices of 65535. */
+size_t creg_mesh_cover_workspace_bytes(int64_t n_tri, int32_t n_links, int64_t n_poses, int64_t n_pts);
+int creg_mesh_cover_f64(const double* tri, const int64_t* tri_start, int64_t n_tri, const double* link_T, int32_t n_links,
+                        int64_t n_poses, const double* pts, const int64_t* pt_start, const int32_t* pt_row, int64_t n_pts,
+                        double d_max, double* dist2, int32_t* pt_idx, int32_t* n_near, double* link_box, void* workspace,
+                        size_t workspace_bytes, creg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Pose-fit system: from the correspondences of creg_point_mesh_f64 (every point's nearest triangle, hence its link), per pose the
  * Gauss-Newton system of fitting the robot's base pose and joint values to that pose's cloud.  The parameters of a pose are
  * D = 6 + n_joints numbers: a rotation vector about center_p (0..2), a translation (3..5) and one value per joint of the table
