@@ -142,6 +142,12 @@ LATTICE = {                                                      # name -> (seco
     "coplanar": ([[1, 1, 0], [5, 1, 0], [1, 5, 0]], 0),
     "edge_through_vertex": ([[0, 0, -1], [0, 0, 1], [-1, -1, 0]], 0),
     "edge_through_edge": ([[2, 0, -1], [2, 0, 1], [2, -2, 0]], 0),
+    "identical": (BASE, 0),
+    "shared_edge": ([[0, 0, 0], [4, 0, 0], [0, 0, 4]], 0),
+    "shared_vertex": ([[0, 0, 0], [-1, -1, 3], [-1, 1, 3]], 0),
+    "point_on_face": ([[1, 1, 0]] * 3, 0),
+    "collinear_piercing": ([[1, 1, -1], [1, 1, 1], [1, 1, 3]], 1),           # zero area, and its edge properly pierces the base
+    "two_edges_pierce": ([[1, 1, -1], [2, 1, -1], [1.5, 1, 5]], 1),          # one pair, counted once
 }
 
 
